@@ -2,7 +2,7 @@
 """Headline bench: contigs/s over eref + generateGraph + matching on the 1M-contig synthetic
 (BASELINE.json `metric`), inputs resident in HBM, one process per GPU.
 
-  python bench.py [--gpus N --steps K --warmup W] [--contigs 1000000] [--workload default|long]
+  python bench.py [--gpus N --steps K --warmup W] [--contigs 1000000] [--workload default|long] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 (`python bench.py --gpus N` without a launcher starts its N ranks itself, as child processes, before this process
 touches a GPU, relays rank 0's JSON line and exits with their status.)
@@ -11,9 +11,11 @@ One "step" = one full pass of the hot path over the whole synthetic sample:
   eref:   zero the count table, count every read of both FASTQ sides, scan every phage ref
   (generateGraph and matching stages are added to the step as they land; `config.stages` names
    what the printed number covers.)
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` for the dominant
-kernel (live HIP-event timing on the kernel's own stream) and `cpu_baseline` (the oracle, i.e.
+Rank 0 prints ONE JSON line with `roofline` for the dominant kernel (live HIP-event timing on the
+kernel's own stream).  A plain run sets up, warms up, times the K steps and prints that line; with
+--full it also runs the soak, the files -> files leg (`e2e`) and `cpu_baseline` (the oracle, i.e.
 the CPU restatement of the reference algorithm, timed on a bounded sample on this host).
+--dump-outputs DIR writes the results of the last timed step as DIR/<name>.npy (float32 / float64).
 """
 import argparse
 import ctypes
@@ -45,12 +47,18 @@ def parse_args():
     ap.add_argument("--reads", choices=("packed", "ascii"), default="packed",
                     help="form of the reads resident in HBM: packed = two bits per base + 32-mer start mask (what the eref executable's "
                          "parser threads produce; palace_eref_count_reads_packed), ascii = a byte per base (palace_eref_count_reads)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the files -> files leg (CLI chain on generated files)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the soak, the files -> files leg (e2e) and the CPU baseline, with the checks they carry")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (eref rows, depth sums, copy numbers, edges, components) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the files -> files leg (CLI chain on generated files)")
     ap.add_argument("--soak-seconds", type=float, default=2.0,
-                    help="after the K timed steps keep stepping (untimed for `value`) until this much wall time has passed")
+                    help="with --full: after the K timed steps keep stepping (untimed for `value`) until this much wall time has passed")
     ap.add_argument("--cpu-sample-frac", type=float, default=0.05, help="share of the reads the CPU baseline's eref term is timed on (the compiled reference: ~30 s)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.contigs is None:
         a.contigs = 100_000 if a.workload == "long" else 1_000_000
     return a
@@ -106,7 +114,7 @@ def run_all_schemes(args) -> int:
     plan, res = scheme_plan(world), {}
     for k, (label, env_add) in enumerate(plan):
         port = base + 64 * (k + 1) if base + 64 * (len(plan) + 1) < 65536 else base - 64 * (k + 1)      # (a rendezvous port of its own, away from the launcher's)
-        env = dict(os.environ, PALACE_BENCH_CHILD="1", MASTER_PORT=str(port), **env_add)
+        env = dict(os.environ, PALACE_BENCH_CHILD="1", MASTER_PORT=str(port), PALACE_BENCH_DUMP_SUBDIR=f"scheme_{k}", **env_add)
         for v in ("TORCHELASTIC_USE_AGENT_STORE", "TORCHELASTIC_RUN_ID"):      # the child's rank 0 hosts the store of ITS group on ITS port
             env.pop(v, None)
         t0 = time.perf_counter()
@@ -160,6 +168,15 @@ def run_all_schemes(args) -> int:
         out = res[best]["line"]
         out.pop("failed_checks", None)
         out["config"]["parallelism"] = f"{world} GPUs, one sample: {best} (the fastest valid one of the configurations measured in this run)"
+    if args.dump_outputs:                                  # every child wrote its outputs to a subdirectory: the chosen one's become DIR's
+        import shutil
+        subs = [os.path.join(args.dump_outputs, f"scheme_{k}") for k in range(len(plan))]
+        if best is not None:
+            src = subs[[label for label, _ in plan].index(best)]
+            for f in os.listdir(src):
+                os.replace(os.path.join(src, f), os.path.join(args.dump_outputs, f))
+        for s in subs:
+            shutil.rmtree(s, ignore_errors=True)
     out["parallelism_measured"] = measured
     out["parallelism_measured_note"] = ("every configuration is a child process per rank (own process group, the scheme forced) timing exactly --steps steps of the SAME sample; "
                                         "valid = its eref rows and graph / component digests equal the one-GPU step's (the weak leg's); `value` is the fastest valid one's")

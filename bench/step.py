@@ -25,6 +25,28 @@ def roofline_stages(stages, traffic):
     return out
 
 
+DUMP_BYTES_MAX = 60_000_000          # --dump-outputs: the arrays' bytes in all (the .npy headers stay well inside 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """{name: integer array} -> path/<name>.npy, float32 where every value is exact in it (|x| < 2^24), else float64.  When the
+    arrays come to more than DUMP_BYTES_MAX, each keeps the same share of its rows, at fixed seeded positions (the same ones in
+    every run of the same arguments)."""
+    out = {}
+    for k, a in arrays.items():
+        a = np.asarray(a)
+        exact32 = a.size == 0 or int(np.abs(a.astype(np.int64)).max()) < (1 << 24)
+        out[k] = a.astype(np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_BYTES_MAX:
+        for k, a in out.items():
+            n = len(a) * DUMP_BYTES_MAX // total
+            out[k] = a[np.sort(np.random.Generator(np.random.PCG64(SEED)).choice(len(a), size=n, replace=False))]
+    os.makedirs(path, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+
+
 def profiled_traffic(args, world, version, fused):
     """HBM bytes per step from the committed PMC profile (profiles/phase_a_traffic.json, written by tools/prof_full.sh +
     tools/traffic_json.py): FETCH_SIZE x 2 (gfx950 correction) + WRITE_SIZE, per count launch and per stage.  Only quoted for
@@ -384,6 +406,7 @@ def measure(args, E, leg):
                     cons_for_quirk = scratch_consumed
         capi._check(L.palace_graph_resolve_ex(g.h, P(all_c), n_cands, n_border, gs["n_total"], ctypes.byref(prm), P(cons_for_quirk),
                                               P(e_buf), max(1, n_cands), P(n_edges_dev), None), "resolve")
+        h_last["e_buf"] = e_buf
         if exch:
             with on_b():
                 exch.reduce_sum(consumed)
@@ -503,10 +526,33 @@ def measure(args, E, leg):
         dt = float(tmax.item())
     ms_step = 1e3 * dt / args.steps
     if rank == 0: progress(f"{leg}: {args.steps} timed steps, {ms_step:.2f} ms each")
-    # soak: the K timed steps above are what `value` is computed from; when they took less than --soak-seconds the same
+
+    def last_step_to_host():
+        """generateGraph's results of the step that ran last, into h_last.  Resolve writes its edges in an order that changes from step
+        to step, and stage 04's edge flags and components are of the step that ran last: the host copies must be of that step too
+        (the bookkeeping of the untimed steps leaves them at the last UNTIMED step's)."""
+        n_e = int(n_edges_dev.item())
+        h_last.update(edges=h_last["e_buf"][:n_e].cpu().numpy().view(capi.EDGE_DTYPE).reshape(-1).copy(),
+                      cn=cn_dev.cpu().numpy().copy(), consumed=consumed.cpu().numpy().copy())
+
+    if args.dump_outputs and stage04 is not None and not solo:
+        # what a caller of the timed path receives from its last step: the eref rows, generateGraph's depth sums, copy numbers and
+        # edges (in a canonical order: lexsorted on all fields), stage 04's components and the filtered graph's bare segments
+        last_step_to_host()
+        e = h_last["edges"]
+        e = np.column_stack([e["left"], e["right"], e["oL"], e["oR"], e["counts"]]).astype(np.int64)
+        e = e[np.lexsort(e.T[::-1])]
+        res, contig_of = h_last["result"]
+        bare = np.unpackbits(np.asarray(res.bare).view(np.uint8), bitorder="little")[:len(contig_of)]
+        dump_outputs(os.path.join(args.dump_outputs, os.environ.get("PALACE_BENCH_DUMP_SUBDIR", "")),
+                     dict(eref_rows=rows_host.numpy(), depth_sums=h_last["consumed"], copy_numbers=h_last["cn"], edges=e,
+                          component_offsets=res.off, component_verts=res.verts, component_kind=res.kind, component_iter=res.iter,
+                          segment_contig=contig_of, segment_bare=bare))
+        progress(f"{leg}: outputs of the last timed step written to {args.dump_outputs}")
+    # soak (--full): the K timed steps above are what `value` is computed from; when they took less than --soak-seconds the same
     # step keeps running (untimed for `value`) so that an outside GPU-activity sampler has something to see
     soak = None
-    if dt < args.soak_seconds and not exch and sync_world == 1:
+    if args.full and dt < args.soak_seconds and not exch and sync_world == 1:
         t1, n_soak = time.perf_counter(), 0
         while time.perf_counter() - t1 < args.soak_seconds - dt:
             for _ in range(10):
@@ -515,6 +561,8 @@ def measure(args, E, leg):
             n_soak += 10
         soak = dict(steps=n_soak, seconds=time.perf_counter() - t1, ms_per_step=1e3 * (time.perf_counter() - t1) / max(1, n_soak),
                     note="untimed steps also lexsort and sha256 the results for `result_digest` (bookkeeping): not comparable with ms_per_step")
+    if args.full and stage04 is not None and not solo:
+        last_step_to_host()                           # (the e2e leg and cpu_baseline hold these against stage 04's flags and result)
     K = range(args.steps)
     if harvest:
         count_each, between_ms = acc["count"], (float(np.mean(acc["between"])) if acc["between"] else None)
@@ -618,7 +666,7 @@ def measure(args, E, leg):
         }
         if soak:
             out["soak"] = soak
-        if world == 1 and not solo and not args.no_e2e:
+        if world == 1 and not solo and args.full and not args.no_e2e:
             import shutil
             import tempfile
             work = os.environ.get("PALACE_BENCH_WORK_DIR")          # (tools/e2e_repeat.sh: the directory it made for this run)
@@ -649,7 +697,7 @@ def measure(args, E, leg):
         else:
             work = paths = None
         try:
-            if world == 1 and not solo and not args.no_cpu_baseline:         # (rank 0 at N = 1 only: the contract; the other ranks would wait for it)
+            if world == 1 and not solo and args.full and not args.no_cpu_baseline:     # (rank 0 at N = 1 only: the other ranks would wait for it)
                 progress("cpu_baseline")
                 res_v, contig_of = h_last["result"]
                 seg_flags, edge_flags = stage04.flags(len(h_last["edges"]))

@@ -1,6 +1,6 @@
 """The bench workloads at their own size (driver-visible: `pytest -m gpu`).
 
-  configs[2]  500k contigs: `bench.py --contigs 500000` must exit 0 -- it exits non-zero when its own cross-checks fail (the
+  configs[2]  500k contigs: `bench.py --full --contigs 500000` must exit 0 -- it exits non-zero when its own cross-checks fail (the
               executables on the generated files disagreeing with the HBM-resident step, the fused generateGraph process
               writing other files than the five-process chain, results that differ from step to step) -- and every read of
               the workload counted through the packed entry (the bench's data path) equals the oracle's table.
@@ -27,13 +27,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def run_bench(contigs, work=None, workload="default"):
-    """bench.py as the driver runs it (its own cross-checks decide the exit status); work: the directory its files -> files leg
-    writes the sample's files into and leaves them in"""
+    """bench.py --full (its own cross-checks decide the exit status); work: the directory its files -> files leg writes the
+    sample's files into and leaves them in"""
     env = dict(os.environ)
     if work is not None:
         env.update(PALACE_BENCH_WORK_DIR=str(work), PALACE_BENCH_KEEP="1")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--contigs", str(contigs), "--workload", workload, "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--soak-seconds", "0.5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT, timeout=900, env=env)
+                        "--full", "--no-cpu-baseline", "--soak-seconds", "0.5"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT, timeout=900, env=env)
     lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
     assert len(lines) == 1, (p.returncode, p.stdout[-2000:], p.stderr[-2000:])
     line = json.loads(lines[0])

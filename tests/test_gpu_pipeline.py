@@ -52,6 +52,46 @@ def test_stage4_chain_equals_oracle_chain(tmp_path):
     assert all_result.startswith(lin) and len(lin) > 0
 
 
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """A plain run (no --full): exactly --steps timed steps, no soak, e2e or cpu_baseline; --dump-outputs writes the last timed
+    step's results as float arrays, the same for every run of the same arguments, and the eref rows are the ones the line's digest is of."""
+    import hashlib
+
+    import numpy as np
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--contigs", "20000", "--refs", "200", "--warmup", "1"]
+    lines = []
+    for d, k in (("a", 3), ("b", 1)):
+        lines.append(json.loads(sh(base + ["--steps", str(k), "--dump-outputs", str(tmp_path / d)]).decode().strip().splitlines()[-1]))
+        assert lines[-1]["steps"] == k and lines[-1]["ms_per_step"] > 0 and "failed_checks" not in lines[-1]
+        assert not {"soak", "e2e", "cpu_baseline"} & set(lines[-1])
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) and len(names) == 10
+    total = 0
+    for n in names:
+        x, y = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and np.array_equal(x, y), n
+        total += os.path.getsize(tmp_path / "a" / n)
+    assert total <= 64 << 20
+    rows = np.load(tmp_path / "a" / "eref_rows.npy").astype(np.int32)
+    assert hashlib.sha256(rows.tobytes()).hexdigest()[:16] == lines[0]["config"]["result_digest"]["eref_rows"]
+    assert len(np.load(tmp_path / "a" / "edges.npy")) == lines[0]["config"]["graph"]["n_edges"] > 0
+
+
+def test_bench_full_legs_after_a_timed_last_step():
+    """--full with no soak: the step that ran last is a timed one (no bookkeeping).  The e2e leg and cpu_baseline hold the host's copies
+    of its edges against stage 04's flags and components of that same step -- resolve's edge order changes from step to step."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--contigs", "20000", "--refs", "200", "--steps", "3",
+                        "--warmup", "1", "--soak-seconds", "0"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, cwd=ROOT, timeout=600)
+    lines = [l for l in p.stdout.decode().splitlines() if l.startswith("{")]
+    assert len(lines) == 1, (p.returncode, p.stderr.decode()[-2000:])
+    line = json.loads(lines[0])
+    assert p.returncode == 0 and "failed_checks" not in line, (line.get("failed_checks"), p.stderr.decode()[-2000:])
+    assert "soak" not in line and line["steps"] == 3
+    parity = line["cpu_baseline"]["parity"]
+    assert parity["all_result_identical_to_resident_step"] is True and all(v is True for v in parity.values()), parity
+    assert line["e2e"]["agrees_with_resident_step"] is True and line["e2e"]["all_result_identical_to_resident_step"] is True
+
+
 def test_bench_exchange_path_rehearsal():
     """world_size 1 over RCCL: same results as the plain single-GPU run."""
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--contigs", "20000", "--refs", "200", "--steps", "1",

@@ -293,10 +293,17 @@ def test_the_walk_ahead_gives_the_serial_walk_on_streams_full_of_fake_record_cha
     assert want[0] == 0 and want[1].count(b"\n") == len(recs) + len(TARGETS)
     for threads in (1, 3, 8):
         assert run_mode(full, threads, False) == want, threads
-    tr = subprocess.run([HOSTDUMP, "bamtime", full, "8"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, PALACE_TRACE="1"), timeout=300)
+    # whether the walker adopts a walked-ahead segment in a given run is up to the scheduler (in about one run of three on a fast host
+    # it never does): traced runs are repeated until one shows the speculation taking part, and every one of them prints the serial walk's records
     import re
-    m = re.search(r"(\d+) of (\d+) record boundaries came from the segments walked ahead", tr.stderr.decode())
-    assert m and int(m.group(2)) == len(recs) and int(m.group(1)) > 0, tr.stderr.decode()[-500:]      # (the speculation did take part)
+    for _ in range(100):
+        tr = subprocess.run([HOSTDUMP, "bam", full, "8"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(os.environ, PALACE_TRACE="1"), timeout=300)
+        m = re.search(r"(\d+) of (\d+) record boundaries came from the segments walked ahead", tr.stderr.decode())
+        assert m and int(m.group(2)) == len(recs), tr.stderr.decode()[-500:]
+        assert (tr.returncode, tr.stdout) == want[:2]
+        if int(m.group(1)) > 0:
+            break
+    assert int(m.group(1)) > 0, tr.stderr.decode()[-500:]      # (the speculation did take part)
     asan = run(HOSTDUMP_ASAN, full, "4")                                    # (and under AddressSanitizer + UBSan)
     assert asan[0] == 0 and asan[1].encode() == want[1]
     # cut short: whole members missing (no EOF block), and the stream ending inside a record
