@@ -402,6 +402,38 @@ int palace_graph_copy_numbers(palace_ctx *ctx, const uint64_t *d_consumed, const
 int palace_bgzf_inflate(palace_ctx *ctx, const uint8_t *d_in, int64_t n_members, const int64_t *d_in_off, const int32_t *d_in_len,
                         const int64_t *d_out_off, const int32_t *d_out_len, uint8_t *d_out, int32_t *d_status);
 
+/* ---- compressed FASTQ for eref: inflated text parsed in HBM -------------------------------------------------------------- */
+
+/* CRC-32 (the gzip polynomial) of n_members byte ranges of device memory, one wavefront each: d_crc[m] = crc32 of the d_len[m]
+ * bytes at d_data + d_off[m] -- what zlib checks against a gzip member's trailer, for the members palace_bgzf_inflate decoded
+ * (it checks none).  Enqueues only. */
+int palace_crc32_members(palace_ctx *ctx, const uint8_t *d_data, int64_t n_members, const int64_t *d_off, const int32_t *d_len,
+                         uint32_t *d_crc);
+
+/* Where a FASTQ parse stands between two windows of one file (device memory, 32 bytes).  line: 0-based index of the line the
+ * next byte belongs to; reads / bases: the read set so far (d_offsets[reads] = bases); open: line `line` has begun in an earlier
+ * window; error: a window did not fit the capacities given with it (it and every later window are then not parsed).  A file
+ * starts at {0, R, B, 0, 0}: its reads follow R reads of B bases of an earlier file in the same read set. */
+typedef struct {
+    int64_t line, reads, bases;
+    int32_t open, error;
+} palace_fastq_cursor;
+
+/* The sequence lines of FASTQ text in device memory appended to an ASCII read set (the form palace_eref_count_reads and
+ * palace_eref_pack_reads take), with the line semantics of the reference's std::getline loop (extract_ref.cpp:940-1004) that
+ * the host's parser has (host/fastx.hpp): a line ends at '\n' only ('\r' stays in the sequence); sequence lines are the lines
+ * whose index is 1 mod 4, an empty one included; bytes are copied unchanged.  d_text[0 .. n) (16-byte aligned) is the next
+ * window of the file: any cut will do, a line may span any number of windows.  final_window != 0: the file ends with this window,
+ * and a last line without '\n' is a line (the empty text behind a final '\n' is not).  Writes the new reads' bytes to
+ * d_bases[cursor.bases ..] and their end offsets to d_offsets[cursor.reads + 1 ..] (d_offsets[0] = 0 is the caller's), and moves
+ * *d_cursor past the window.  bases_cap / offsets_cap: bytes of d_bases, entries of d_offsets; a window that would write past them
+ * writes nothing and sets cursor.error (a read set has at most 1 + n / 4 reads and n bases more after a window of n bytes).
+ * d_scratch: palace_fastq_scratch_bytes(n) bytes of device memory, not shared with calls in flight.  Enqueues only. */
+size_t palace_fastq_scratch_bytes(int64_t max_window);
+int palace_fastq_parse(palace_ctx *ctx, const uint8_t *d_text, int64_t n, int final_window, palace_fastq_cursor *d_cursor,
+                       uint8_t *d_bases, int64_t bases_cap, int64_t *d_offsets, int64_t offsets_cap, void *d_scratch,
+                       size_t scratch_bytes);
+
 /* ---- depth stage: `samtools depth <bam> | awk '{sum+=$3} END {print sum/NR}'` (palace:538-552) ------------------ */
 
 /* The two numbers of that mean.  A match segment is one M / = / X CIGAR operation of a record whose UNMAP, SECONDARY,

@@ -60,6 +60,7 @@ CAND_DTYPE = np.dtype([("ord", np.int64), ("qkey", np.uint64), ("left", np.int32
                        ("oL", np.uint8), ("oR", np.uint8), ("pad0", np.uint8), ("pad1", np.uint8), ("sa_index", np.int32)])
 EDGE_DTYPE = np.dtype([("left", np.int32), ("right", np.int32), ("counts", np.uint32, 4), ("oL", np.uint8),
                        ("oR", np.uint8), ("pad", np.uint8, 6)])
+FASTQ_CURSOR_DTYPE = np.dtype([("line", np.int64), ("reads", np.int64), ("bases", np.int64), ("open", np.int32), ("error", np.int32)])
 assert CAND_DTYPE.itemsize == 64 and EDGE_DTYPE.itemsize == 32 and SA_ITEM_DTYPE.itemsize == 32
 
 _SIGS = {
@@ -144,6 +145,10 @@ _SIGS = {
                                  C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "palace_graph_fastg_offsets": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p],
     "palace_bgzf_inflate": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_fastq_scratch_bytes": [C.c_int64],          # (returns size_t: restype set below)
+    "palace_crc32_members": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_fastq_parse": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                           C.c_void_p, C.c_size_t],
     "palace_graph_score_border": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(GraphParams)],
     "palace_graph_resolve_ex": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(GraphParams), C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)],
@@ -190,6 +195,7 @@ def lib() -> C.CDLL:
             fn = getattr(_LIB, name)
             fn.argtypes = sig
             fn.restype = C.c_int
+        _LIB.palace_fastq_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -423,6 +429,70 @@ class Ctx:
 
     def eref_plane_unpack(self, buckets, counts_ptr: int, keys_ptr: int, cap_keys: int, first_ptr: int):
         _check(lib().palace_eref_plane_unpack(self.h, self._bucket_mask(buckets), counts_ptr, keys_ptr, cap_keys, first_ptr), "palace_eref_plane_unpack")
+
+    # -- compressed FASTQ for eref ---------------------------------------------------------
+    def crc32_members(self, d_data_ptr: int, n_members: int, d_off: DevBuf, d_len: DevBuf, d_crc: DevBuf):
+        _check(lib().palace_crc32_members(self.h, d_data_ptr, n_members, d_off.ptr, d_len.ptr, d_crc.ptr), "palace_crc32_members")
+
+    def fastq_parse(self, d_text_ptr: int, n: int, final_window: bool, d_cursor: DevBuf, d_bases: DevBuf, bases_cap: int,
+                    d_offsets: DevBuf, offsets_cap: int, d_scratch: DevBuf):
+        _check(lib().palace_fastq_parse(self.h, d_text_ptr, n, int(final_window), d_cursor.ptr, d_bases.ptr, bases_cap, d_offsets.ptr,
+                                        offsets_cap, d_scratch.ptr, d_scratch.nbytes), "palace_fastq_parse")
+
+
+def fastq_scratch_bytes(max_window: int) -> int:
+    return int(lib().palace_fastq_scratch_bytes(max_window))
+
+
+def crc32_members(ctx: Ctx, data: bytes, lengths) -> np.ndarray:
+    """CRC-32 of consecutive members of `data` (lengths in bytes) computed on the device."""
+    lens = np.asarray(lengths, dtype=np.int32)
+    offs = np.concatenate([[0], np.cumsum(lens, dtype=np.int64)[:-1]]).astype(np.int64) if len(lens) else np.zeros(0, np.int64)
+    d_data = ctx.upload(np.frombuffer(bytes(data), dtype=np.uint8) if len(data) else np.zeros(1, np.uint8))
+    d_off, d_len, d_crc = ctx.upload(offs), ctx.upload(lens), ctx.empty(max(1, len(lens)), np.uint32)
+    try:
+        ctx.crc32_members(d_data.ptr, len(lens), d_off, d_len, d_crc)
+        return d_crc.to_host()[:len(lens)]
+    finally:
+        for b in (d_data, d_off, d_len, d_crc):
+            b.free()
+
+
+def fastq_read_set(ctx: Ctx, text: bytes, cuts=(), reads0: int = 0, bases0: int = 0):
+    """The sequence lines of FASTQ `text` as an ASCII read set made by palace_fastq_parse, the text handed over in windows cut at
+    the ascending positions `cuts`.  Returns (bases uint8, offsets int64 of reads + 1 entries starting at bases0, final cursor);
+    the first reads0 entries a real caller would have are not part of the result."""
+    text = bytes(text)
+    bounds = [0] + [c for c in cuts if 0 < c < len(text)] + [len(text)]
+    widest = max(b - a for a, b in zip(bounds, bounds[1:])) if len(bounds) > 1 else 0
+    bases_cap = bases0 + len(text) + 1
+    offsets_cap = reads0 + len(text) // 4 + 3
+    d_win = DevBuf(ctx, max(16, widest + 16))
+    d_bases, d_offsets = DevBuf(ctx, bases_cap), ctx.empty(offsets_cap, np.int64)
+    d_scratch = DevBuf(ctx, fastq_scratch_bytes(widest))
+    cur = np.zeros(1, FASTQ_CURSOR_DTYPE)
+    cur["reads"], cur["bases"] = reads0, bases0
+    d_cur = ctx.upload(cur)
+    try:
+        first = np.zeros(1, np.int64)
+        first[0] = bases0
+        _check(lib().palace_h2d(ctx.h, d_offsets.ptr + 8 * reads0, first.ctypes.data, 8), "palace_h2d")
+        for k, (a, b) in enumerate(zip(bounds, bounds[1:])):
+            chunk = np.frombuffer(text[a:b], dtype=np.uint8)
+            if len(chunk):
+                _check(lib().palace_h2d(ctx.h, d_win.ptr, chunk.ctypes.data, len(chunk)), "palace_h2d")
+            ctx.fastq_parse(d_win.ptr, len(chunk), k == len(bounds) - 2, d_cur, d_bases, bases_cap, d_offsets, offsets_cap, d_scratch)
+            ctx.sync()
+        cur = d_cur.to_host()[0]
+        if cur["error"]:
+            raise PalaceError("palace_fastq_parse: capacity exceeded")
+        n_reads = int(cur["reads"]) - reads0
+        offsets = d_offsets.to_host()[reads0:reads0 + n_reads + 1].copy()
+        bases = d_bases.to_host()[bases0:int(cur["bases"])].copy()
+        return bases, offsets, cur
+    finally:
+        for buf in (d_win, d_bases, d_offsets, d_scratch, d_cur):
+            buf.free()
 
 
 _ARC_BUFFERS = {}

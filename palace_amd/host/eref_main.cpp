@@ -26,6 +26,7 @@
 
 #include "../../include/palace_hip.h"
 #include "fastx.hpp"
+#include "fastq_gz.hpp"
 #include "trace.hpp"
 #include "fast_exit.hpp"
 #include "device_pick.hpp"
@@ -115,6 +116,78 @@ int upload(palace_ctx *ctx, const T *src, size_t n, T **d)
     return palace_h2d(ctx, p, src, n * sizeof(T));
 }
 
+// E3 subsampling (extract_ref.cpp:1124-1148, 1230, 955-960): the ratio from side 1's sequence bytes, one draw per read
+int down_sampling_ratio(int64_t fq1_bases)
+{
+    long sample = static_cast<long>(fq1_bases) * 2;                             // cal_sam_ratio (:1124-1148)
+    long target = 2000000000L;                                                  // down_sampling_size (:1230)
+#ifdef PALACE_TEST_HOOKS
+    if (const char *t = std::getenv("PALACE_EREF_SAMPLE_TARGET")) target = std::atol(t);   // test builds only (bin/eref_testhooks)
+#endif
+    return sample > 0 ? static_cast<int>(100L * target / sample) : 100;
+}
+
+// Phase A for inputs of which at least one is gzip (fastq_gz.hpp): both sides parsed on the device into one ASCII read set, packed
+// there, the ASCII set freed before the count's scratch is reserved, then the count.  Non-zero: the message is out.
+int count_device_parsed(palace_ctx *ctx, const MappedText fq_txt[2], const FqKind kind[2], const std::vector<BgzfMember> members[2],
+                        const std::string &fq1, const std::string &fq2, Trace &tr)
+{
+    int64_t window = 32ll << 20;                                                // text in flight on the device / per staging buffer
+#ifdef PALACE_TEST_HOOKS
+    if (const char *w = std::getenv("PALACE_EREF_GZ_WINDOW")) window = std::max(16ll, std::atoll(w));   // test builds only
+#endif
+    window = std::max<int64_t>(16, window & ~int64_t{15});                      // windows start 16-byte aligned
+    const bool trace = tr.on;
+    int64_t n_reads = 0, n_bases = 0, fq1_bases = 0;
+    uint8_t *d_b = nullptr; int64_t *d_o = nullptr;
+    DeviceReadSet rs(ctx, window, trace);
+    try {
+        int64_t guess = 0;                                                      // bases: about half the text (BGZF: known from ISIZE)
+        for (int side = 0; side < 2; side++) {
+            int64_t text = static_cast<int64_t>(fq_txt[side].size) * (kind[side] == FqKind::Gzip ? 6 : 1);
+            if (kind[side] == FqKind::Bgzf) { text = 0; for (const BgzfMember &m : members[side]) text += static_cast<int64_t>(m.out_len); }
+            guess += text / 2;
+        }
+        rs.init(guess);
+        for (int side = 0; side < 2; side++) {
+            const std::string &path = side == 0 ? fq1 : fq2;
+            if (kind[side] == FqKind::Bgzf) ingest_bgzf(rs, ctx, fq_txt[side], members[side], path);
+            else if (kind[side] == FqKind::Gzip) ingest_gzip(rs, ctx, fq_txt[side], path);
+            else ingest_plain(rs, ctx, fq_txt[side]);
+            if (side == 0) fq1_bases = rs.cursor().bases;
+        }
+        rs.release_window();
+    } catch (const std::exception &e) { std::cerr << "eref: " << e.what() << "\n"; return 1; }
+    n_reads = rs.cursor().reads; n_bases = rs.cursor().bases;
+    d_b = rs.bases(); d_o = rs.offsets();
+    if (trace)
+        std::fprintf(stderr, "[eref] fastq on the device: %lld reads, %lld bases; inflate %.1f ms, crc %.1f ms, parse %.1f ms, h2d %.1f ms\n",
+                     static_cast<long long>(n_reads), static_cast<long long>(n_bases), rs.times.inflate, rs.times.crc, rs.times.parse, rs.times.h2d);
+    tr.lap("fastq inflate + crc + parse");
+    const int down_sam_ratio = down_sampling_ratio(fq1_bases);
+    uint8_t *d_k = nullptr;
+    if (down_sam_ratio < 100 && n_reads) {
+        GlibcRand rng(1);
+        std::vector<uint8_t> keep(static_cast<size_t>(n_reads));
+        for (int64_t i = 0; i < n_reads; i++) keep[static_cast<size_t>(i)] = (rng.next() % 100) < down_sam_ratio;
+        CK(upload(ctx, keep.data(), keep.size(), &d_k));
+    }
+    const size_t stream_bytes = palace_eref_packed_bytes(n_bases);
+    uint32_t *d_s[3] = {nullptr, nullptr, nullptr};
+    for (int q = 0; q < 3; q++) { void *p = nullptr; CK(palace_malloc(ctx, stream_bytes, &p)); d_s[q] = static_cast<uint32_t *>(p); }
+    if (n_reads && n_bases) CK(palace_eref_pack_reads(ctx, d_b, d_o, n_reads, d_k, n_bases, d_s[0], d_s[1], d_s[2]));
+    CK(palace_sync(ctx));
+    rs.release_set();                                                            // the ASCII set is gone before the count's scratch comes
+    if (d_k) CK(palace_free(ctx, d_k));
+    tr.lap("pack_reads");
+    CK(palace_eref_reserve(ctx, n_bases));
+    if (n_bases) CK(palace_eref_count_reads_packed(ctx, d_s[0], d_s[1], d_s[2], n_bases, n_reads));
+    CK(palace_sync(ctx));
+    for (int q = 0; q < 3; q++) CK(palace_free(ctx, d_s[q]));
+    tr.lap("count_reads_packed");
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -140,12 +213,18 @@ int main(int argc, char **argv)
     std::string ctx_err, in_err;
     MappedText fq_txt[2];
     FastqPlan plan[2];
+    // a gzip input (by its first bytes) sends BOTH sides through the device parser (fastq_gz.hpp); two plain files take the host path
+    FqKind fq_kind[2] = {FqKind::Plain, FqKind::Plain};
+    std::vector<BgzfMember> fq_members[2];
+    bool compressed = false;
     std::shared_future<void> scan_done = std::async(std::launch::async, [&] {   // pass 1 over both FASTQ files: parts, line phases, sizes
         try {
             for (int side = 0; side < 2; side++) {
                 fq_txt[side].open(side == 0 ? fq1 : fq2);
-                plan_fastq(fq_txt[side], threads, plan[side]);
+                fq_kind[side] = classify_fastq(fq_txt[side], &fq_members[side]);
             }
+            compressed = fq_kind[0] != FqKind::Plain || fq_kind[1] != FqKind::Plain;
+            for (int side = 0; side < 2 && !compressed; side++) plan_fastq(fq_txt[side], threads, plan[side]);
         } catch (const std::exception &e) { in_err = e.what(); }
     }).share();
     std::thread hip_up([&] {
@@ -164,7 +243,7 @@ int main(int argc, char **argv)
         if (!ctx_rc) {                                      // ... and the scratch memory of the count, as soon as its size is known
             scan_done.wait();
             th.lap("fastq pass 1 (waited)");
-            if (in_err.empty()) ctx_rc = palace_eref_reserve(ctx, plan[0].n_bases + plan[1].n_bases);
+            if (in_err.empty() && !compressed) ctx_rc = palace_eref_reserve(ctx, plan[0].n_bases + plan[1].n_bases);
             th.lap("scratch reserved");
         }
         if (ctx_rc) ctx_err = palace_last_error();          // (the message is per thread)
@@ -256,6 +335,9 @@ int main(int argc, char **argv)
     scan_done.wait();
     tr.lap("fastq pass 1 (joined)");
     if (!in_err.empty()) { std::cerr << "eref: " << in_err << "\n"; return 1; }
+    if (compressed) {
+        if (count_device_parsed(ctx, fq_txt, fq_kind, fq_members, fq1, fq2, tr)) return 1;
+    } else {
     const int64_t n_reads = plan[0].n_reads + plan[1].n_reads, n_bases = plan[0].n_bases + plan[1].n_bases;
     long sample = static_cast<long>(plan[0].n_bases) * 2;                       // cal_sam_ratio (:1124-1148)
     long target = 2000000000L;                                                  // down_sampling_size (:1230)
@@ -371,6 +453,7 @@ int main(int argc, char **argv)
         tr.lap("count_reads enqueued");
         for (int k = 0; k < 2; k++) CK(palace_host_free(ctx, stage[k]));
         CK(palace_free(ctx, d_b)); CK(palace_free(ctx, d_o)); CK(palace_free(ctx, d_k));
+    }
     }
     for (int side = 0; side < 2; side++) plan[side].parts.clear();
 

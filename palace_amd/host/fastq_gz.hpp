@@ -1,0 +1,385 @@
+// eref's compressed inputs: a FASTQ file given as gzip (BGZF or any other) becomes part of ONE ASCII read set in HBM -- side 2's
+// reads behind side 1's, as the plain path has them -- and is counted from there.
+//   BGZF: the compressed bytes go up a window of members at a time, palace_bgzf_inflate inflates them (a member the device
+//         refuses: inflate_member on the host, uploaded), palace_crc32_members checks every member against its trailer, and
+//         palace_fastq_parse appends the window's sequence lines to the read set.  The text never leaves the device.
+//   other gzip: zlib on a host thread of its own (headers, CRC-32 and ISIZE of every member checked by zlib), the text in chunks
+//         through page-locked staging buffers to the device, parsed there by the same kernels.
+//   plain (the other side of a mixed pair): the mapped text goes up a window at a time.
+// Device memory for text in flight is one window (plus its compressed bytes); host memory for inflated text is the staging ring.
+#pragma once
+#include <zlib.h>
+
+#include <algorithm>
+#include <chrono>
+#include <condition_variable>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <stdexcept>
+#include <string>
+#include <thread>
+#include <vector>
+
+#include "../../include/palace_hip.h"
+#include "bam.hpp"
+#include "fastx.hpp"
+
+namespace palace_host {
+
+enum class FqKind { Plain, Bgzf, Gzip };
+
+// By content, not by name: no gzip magic = plain text; gzip whose members the BGZF walker accepts from the first byte to the last
+// = BGZF; any other gzip = zlib's (which then also decides what is truncated or trailing).
+inline FqKind classify_fastq(const MappedText &t, std::vector<BgzfMember> *members)
+{
+    const uint8_t *d = reinterpret_cast<const uint8_t *>(t.data);
+    if (t.size < 2 || d[0] != 0x1f || d[1] != 0x8b) return FqKind::Plain;
+    try {
+        size_t total = 0;
+        std::vector<BgzfMember> m = bgzf_members(d, t.size, &total);
+        if (!m.empty() && m.back().in_off + m.back().in_len + 8 == t.size) { *members = std::move(m); return FqKind::Bgzf; }
+    } catch (const std::exception &) {
+    }
+    return FqKind::Gzip;
+}
+
+struct FqIngestTimes { double inflate = 0, crc = 0, parse = 0, h2d = 0; };
+
+// The read set in HBM and the parser's state; grows (device copy) when a window could overrun it.
+class DeviceReadSet {
+public:
+    DeviceReadSet(palace_ctx *ctx, int64_t window, bool timed) : ctx_(ctx), window_(window), timed_(timed) {}
+    ~DeviceReadSet() { release_window(); release_set(); }
+    DeviceReadSet(const DeviceReadSet &) = delete;
+    DeviceReadSet &operator=(const DeviceReadSet &) = delete;
+
+    int64_t window() const { return window_; }
+    uint8_t *text() const { return d_text_; }
+    const palace_fastq_cursor &cursor() const { return cur_; }
+    uint8_t *bases() const { return d_bases_; }
+    int64_t *offsets() const { return d_offsets_; }
+    FqIngestTimes times;
+
+    void init(int64_t bases_guess)
+    {
+        ck(palace_malloc(ctx_, static_cast<size_t>(window_) + 64, reinterpret_cast<void **>(&d_text_)), "text window");
+        scratch_bytes_ = palace_fastq_scratch_bytes(window_);
+        ck(palace_malloc(ctx_, scratch_bytes_, &d_scratch_), "parser scratch");
+        ck(palace_malloc(ctx_, sizeof(palace_fastq_cursor), reinterpret_cast<void **>(&d_cur_)), "parser cursor");
+        grow(std::max<int64_t>(bases_guess, 1 << 20), std::max<int64_t>(bases_guess / 64, 1 << 16));
+        const int64_t zero = 0;
+        ck(palace_h2d(ctx_, d_offsets_, &zero, 8), "read set");
+    }
+    // a new file: its first line is line 0, its reads go behind the ones there
+    void start_file()
+    {
+        cur_.line = 0; cur_.open = 0;
+        ck(palace_h2d(ctx_, d_cur_, &cur_, sizeof cur_), "parser cursor");
+    }
+    // d_text_[0 .. n) holds the file's next n bytes (n <= window)
+    void parse(int64_t n, bool final_window) { parse_at(d_text_, n, final_window); }
+    // ... or another 16-byte aligned device buffer does
+    void parse_at(const uint8_t *d_txt, int64_t n, bool final_window)
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (cur_.bases + n > bases_cap_ || cur_.reads + n / 4 + 3 > offsets_cap_)
+            grow(std::max(cur_.bases + n, bases_cap_ + bases_cap_ / 2), std::max(cur_.reads + n / 4 + 3, offsets_cap_ + offsets_cap_ / 2));
+        ck(palace_fastq_parse(ctx_, d_txt, n, final_window ? 1 : 0, d_cur_, d_bases_, bases_cap_, d_offsets_, offsets_cap_, d_scratch_,
+                              scratch_bytes_), "palace_fastq_parse");
+        ck(palace_d2h(ctx_, &cur_, d_cur_, sizeof cur_), "parser cursor");
+        if (cur_.error) throw std::runtime_error("the FASTQ parser ran out of room");
+        if (timed_) times.parse += ms_since(t0);
+    }
+    void release_window()
+    {
+        if (d_text_) palace_free(ctx_, d_text_);
+        if (d_scratch_) palace_free(ctx_, d_scratch_);
+        if (d_cur_) palace_free(ctx_, d_cur_);
+        d_text_ = nullptr; d_scratch_ = nullptr; d_cur_ = nullptr;
+    }
+    void release_set()
+    {
+        if (d_bases_) palace_free(ctx_, d_bases_);
+        if (d_offsets_) palace_free(ctx_, d_offsets_);
+        d_bases_ = nullptr; d_offsets_ = nullptr;
+    }
+    static double ms_since(std::chrono::steady_clock::time_point t)
+    {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    }
+    void ck(int rc, const char *what)
+    {
+        if (rc) throw std::runtime_error(std::string("device error (") + what + "): " + palace_last_error());
+    }
+
+private:
+    void grow(int64_t bases_cap, int64_t offsets_cap)
+    {
+        void *b = nullptr, *o = nullptr;
+        ck(palace_malloc(ctx_, static_cast<size_t>(bases_cap) + 64, &b), "read set");
+        ck(palace_malloc(ctx_, static_cast<size_t>(offsets_cap) * 8, &o), "read set");
+        if (d_bases_) {
+            if (cur_.bases) ck(palace_d2d(ctx_, b, d_bases_, static_cast<size_t>(cur_.bases)), "read set");
+            ck(palace_d2d(ctx_, o, d_offsets_, static_cast<size_t>(cur_.reads + 1) * 8), "read set");
+            ck(palace_sync(ctx_), "read set");
+            release_set();
+        }
+        d_bases_ = static_cast<uint8_t *>(b); d_offsets_ = static_cast<int64_t *>(o);
+        bases_cap_ = bases_cap; offsets_cap_ = offsets_cap;
+    }
+
+    palace_ctx *ctx_;
+    int64_t window_;
+    bool timed_;
+    uint8_t *d_text_ = nullptr, *d_bases_ = nullptr;
+    int64_t *d_offsets_ = nullptr;
+    void *d_scratch_ = nullptr;
+    size_t scratch_bytes_ = 0;
+    palace_fastq_cursor *d_cur_ = nullptr;
+    palace_fastq_cursor cur_{0, 0, 0, 0, 0};
+    int64_t bases_cap_ = 0, offsets_cap_ = 0;
+};
+
+// ---- plain text (one side of a mixed pair) ---------------------------------------------------------------------------------
+inline void ingest_plain(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t)
+{
+    rs.start_file();
+    const int64_t W = rs.window(), N = static_cast<int64_t>(t.size);
+    int64_t p = 0;
+    do {
+        const int64_t n = std::min(W, N - p);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (n) rs.ck(palace_h2d(ctx, rs.text(), t.data + p, static_cast<size_t>(n)), "text upload");
+        rs.times.h2d += DeviceReadSet::ms_since(t0);
+        p += n;
+        rs.parse(n, p == N);
+    } while (p < N);
+}
+
+// ---- BGZF: inflated, checked and parsed on the device ------------------------------------------------------------------------
+inline void ingest_bgzf(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t, const std::vector<BgzfMember> &mem, const std::string &path)
+{
+    rs.start_file();
+    const uint8_t *file = reinterpret_cast<const uint8_t *>(t.data);
+    const int64_t W = rs.window();
+    // Members are inflated kBgzfBatch at a time (a launch takes as long as its slowest member, and the device holds ~7 000 of the
+    // decoder's wavefronts: batches of one 32 MiB window, ~500 members, left it mostly idle -- 260 ms against the 1M-contig sample's
+    // 2.1 GB of text, against 44 ms in batches of 8 192); the parser takes a batch's text a window at a time.  Device memory: <= kBgzfBatch x 64 KiB of text.
+    constexpr size_t kBgzfBatch = 8192;
+    std::vector<size_t> cut{0};                                              // batches [cut[k], cut[k + 1])
+    uint64_t max_in = 0, batch_out = 0;
+    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
+    for (size_t i = 0, out = 0; i < mem.size(); i++) {
+        if (i - cut.back() == kBgzfBatch) { cut.push_back(i); out = 0; }
+        out += mem[i].out_len;
+        batch_out = std::max<uint64_t>(batch_out, out);
+        max_in = std::max<uint64_t>(max_in, mem[i].in_off + mem[i].in_len + 8 - member_start(cut.back()));
+    }
+    cut.push_back(mem.size());
+    const size_t max_n = [&] { size_t m = 0; for (size_t k = 0; k + 1 < cut.size(); k++) m = std::max(m, cut[k + 1] - cut[k]); return m; }();
+    void *d_in = nullptr, *d_batch = nullptr, *d_meta = nullptr;
+    rs.ck(palace_malloc(ctx, static_cast<size_t>(max_in) + 64, &d_in), "compressed window");
+    rs.ck(palace_malloc(ctx, static_cast<size_t>(batch_out) + 64, &d_batch), "inflated window");
+    rs.ck(palace_malloc(ctx, max_n * 32 + 64, &d_meta), "member table");
+    struct Free { palace_ctx *c; void *a, *b, *m; ~Free() { palace_free(c, a); palace_free(c, b); palace_free(c, m); } } free_{ctx, d_in, d_batch, d_meta};
+    // per member: in_off, out_off (int64), in_len, out_len, status, crc (int32) -- one array each, one upload
+    std::vector<uint8_t> meta(max_n * 32);
+    std::vector<uint8_t> host_out(65536);
+    uint64_t file_pos = 0;
+    for (size_t k = 0; k + 1 < cut.size(); k++) {
+        const size_t i0 = cut[k], n = cut[k + 1] - i0;
+        if (n == 0) continue;
+        const uint64_t in0 = member_start(i0), in1 = mem[i0 + n - 1].in_off + mem[i0 + n - 1].in_len + 8;
+        int64_t *in_off = reinterpret_cast<int64_t *>(meta.data()), *out_off = in_off + n;
+        int32_t *in_len = reinterpret_cast<int32_t *>(out_off + n), *out_len = in_len + n, *status = out_len + n;
+        uint32_t *crc = reinterpret_cast<uint32_t *>(status + n);
+        uint8_t *dm = static_cast<uint8_t *>(d_meta);
+        int64_t out = 0;
+        for (size_t j = 0; j < n; j++) {
+            const BgzfMember &m = mem[i0 + j];
+            in_off[j] = static_cast<int64_t>(m.in_off - in0); in_len[j] = static_cast<int32_t>(m.in_len);
+            out_off[j] = out; out_len[j] = static_cast<int32_t>(m.out_len);
+            out += static_cast<int64_t>(m.out_len);
+        }
+        auto t0 = std::chrono::steady_clock::now();
+        rs.ck(palace_h2d(ctx, d_in, file + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
+        rs.ck(palace_h2d(ctx, d_meta, meta.data(), n * 24), "member table");
+        rs.times.h2d += DeviceReadSet::ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        rs.ck(palace_bgzf_inflate(ctx, static_cast<const uint8_t *>(d_in), static_cast<int64_t>(n), reinterpret_cast<const int64_t *>(dm),
+                                  reinterpret_cast<const int32_t *>(dm + 16 * n), reinterpret_cast<const int64_t *>(dm + 8 * n),
+                                  reinterpret_cast<const int32_t *>(dm + 20 * n), static_cast<uint8_t *>(d_batch),
+                                  reinterpret_cast<int32_t *>(dm + 24 * n)), "palace_bgzf_inflate");
+        rs.ck(palace_d2h(ctx, status, dm + 24 * n, 4 * n), "member status");
+        for (size_t j = 0; j < n; j++) {                                     // what the device refused: the host's decoder, zlib behind it
+            if (status[j] == 0) continue;
+            const BgzfMember &m = mem[i0 + j];
+            if (!inflate_member(file, t.size, m, host_out.data()))
+                throw std::runtime_error(path + ": the BGZF member at offset " + std::to_string(member_start(i0 + j)) + " cannot be inflated");
+            if (m.out_len) rs.ck(palace_h2d(ctx, static_cast<uint8_t *>(d_batch) + out_off[j], host_out.data(), m.out_len), "inflated upload");
+        }
+        rs.times.inflate += DeviceReadSet::ms_since(t0);
+        t0 = std::chrono::steady_clock::now();
+        rs.ck(palace_crc32_members(ctx, static_cast<const uint8_t *>(d_batch), static_cast<int64_t>(n), reinterpret_cast<const int64_t *>(dm + 8 * n),
+                                   reinterpret_cast<const int32_t *>(dm + 20 * n), reinterpret_cast<uint32_t *>(dm + 28 * n)), "palace_crc32_members");
+        rs.ck(palace_d2h(ctx, crc, dm + 28 * n, 4 * n), "member CRC");
+        for (size_t j = 0; j < n; j++) {
+            const BgzfMember &m = mem[i0 + j];
+            uint32_t want;
+            std::memcpy(&want, file + m.in_off + m.in_len, 4);
+            if (crc[j] != want)
+                throw std::runtime_error(path + ": CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i0 + j)));
+        }
+        rs.times.crc += DeviceReadSet::ms_since(t0);
+        // the batch's text through the parser, a window at a time (windows start 16-byte aligned: W is a multiple of 16)
+        file_pos = in1;
+        const bool last_batch = file_pos == t.size;
+        int64_t p = 0;
+        do {
+            const int64_t w = std::min(W, out - p);
+            rs.parse_at(static_cast<uint8_t *>(d_batch) + p, w, last_batch && p + w == out);
+            p += w;
+        } while (p < out);
+    }
+}
+
+// ---- other gzip: zlib on a thread of its own, text through a ring of page-locked buffers -------------------------------------
+class GzipProducer {
+public:
+    GzipProducer(palace_ctx *ctx, const MappedText &t, const std::string &path, int64_t chunk) : t_(t), path_(path), chunk_(chunk)
+    {
+        for (int k = 0; k < kRing; k++) {
+            void *p = nullptr;
+            if (palace_host_alloc(ctx, static_cast<size_t>(chunk_), &p)) throw std::runtime_error(std::string("cannot page-lock staging: ") + palace_last_error());
+            buf_[k] = static_cast<uint8_t *>(p);
+        }
+        ctx_ = ctx;
+        th_ = std::thread([this] { run(); });
+    }
+    ~GzipProducer()
+    {
+        {
+            std::lock_guard<std::mutex> g(mu_);
+            stop_ = true;
+        }
+        cv_.notify_all();
+        if (th_.joinable()) th_.join();
+        for (int k = 0; k < kRing; k++) palace_host_free(ctx_, buf_[k]);
+    }
+    // the next chunk: bytes in *n (0 and true = the end); throws what the inflater found
+    const uint8_t *next(int64_t *n, bool *last)
+    {
+        std::unique_lock<std::mutex> g(mu_);
+        if (taken_) { taken_ = false; head_++; cv_.notify_all(); }          // the previous chunk is free again
+        cv_.wait(g, [&] { return tail_ > head_ || done_; });
+        if (tail_ > head_) {
+            *n = len_[head_ % kRing];
+            *last = done_ && tail_ == head_ + 1 && err_.empty();
+            taken_ = true;
+            return buf_[head_ % kRing];
+        }
+        if (!err_.empty()) throw std::runtime_error(err_);
+        *n = 0; *last = true;
+        return nullptr;
+    }
+    double inflate_ms() const { return inflate_ms_; }
+
+private:
+    static constexpr int kRing = 3;
+    void fail(const std::string &m)
+    {
+        std::lock_guard<std::mutex> g(mu_);
+        err_ = path_ + ": " + m;
+        done_ = true;
+        cv_.notify_all();
+    }
+    void run()
+    {
+        const auto t0 = std::chrono::steady_clock::now();
+        z_stream zs{};
+        if (inflateInit2(&zs, 15 + 16) != Z_OK) { fail("zlib cannot start"); return; }
+        const uint8_t *in = reinterpret_cast<const uint8_t *>(t_.data);
+        size_t pos = 0;
+        bool in_member = false;
+        std::string err;
+        for (;;) {
+            uint8_t *dst;
+            {
+                std::unique_lock<std::mutex> g(mu_);
+                cv_.wait(g, [&] { return tail_ - head_ < kRing || stop_; });
+                if (stop_) break;
+                dst = buf_[tail_ % kRing];
+            }
+            int64_t filled = 0;
+            bool end = false;
+            while (filled < chunk_ && err.empty()) {
+                if (!in_member) {
+                    if (pos == t_.size) { end = true; break; }
+                    if (t_.size - pos < 2 || in[pos] != 0x1f || in[pos + 1] != 0x8b) {
+                        err = pos ? "bytes that are not gzip after the last member (offset " + std::to_string(pos) + ")" : "not a gzip file";
+                        break;
+                    }
+                    if (inflateReset(&zs) != Z_OK) { err = "zlib cannot restart"; break; }
+                    in_member = true;
+                }
+                const size_t avail = std::min<size_t>(t_.size - pos, 1u << 30);
+                zs.next_in = const_cast<Bytef *>(in + pos); zs.avail_in = static_cast<uInt>(avail);
+                zs.next_out = dst + filled; zs.avail_out = static_cast<uInt>(chunk_ - filled);
+                const int rc = inflate(&zs, Z_NO_FLUSH);
+                pos += avail - zs.avail_in;
+                filled = chunk_ - zs.avail_out;
+                if (rc == Z_STREAM_END) { in_member = false; continue; }     // CRC-32 and ISIZE checked by zlib
+                if (rc == Z_OK) continue;
+                if (rc == Z_BUF_ERROR && zs.avail_out == 0) continue;
+                if (rc == Z_BUF_ERROR) { err = "truncated gzip stream"; break; }
+                err = std::string("corrupt gzip stream (") + (zs.msg ? zs.msg : "zlib error") + ") near offset " + std::to_string(pos);
+                break;
+            }
+            {
+                std::lock_guard<std::mutex> g(mu_);
+                if (filled) { len_[tail_ % kRing] = filled; tail_++; }
+                if (!err.empty()) { err_ = path_ + ": " + err; done_ = true; }
+                else if (end) done_ = true;
+                inflate_ms_ = DeviceReadSet::ms_since(t0);
+            }
+            cv_.notify_all();
+            if (!err.empty() || end) break;
+        }
+        inflateEnd(&zs);
+    }
+
+    const MappedText &t_;
+    std::string path_;
+    int64_t chunk_;
+    palace_ctx *ctx_ = nullptr;
+    uint8_t *buf_[kRing] = {nullptr, nullptr, nullptr};
+    int64_t len_[kRing] = {0, 0, 0};
+    uint64_t head_ = 0, tail_ = 0;
+    bool taken_ = false, done_ = false, stop_ = false;
+    double inflate_ms_ = 0;
+    std::string err_;
+    std::mutex mu_;
+    std::condition_variable cv_;
+    std::thread th_;
+};
+
+inline void ingest_gzip(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t, const std::string &path)
+{
+    rs.start_file();
+    GzipProducer prod(ctx, t, path, rs.window());
+    for (;;) {
+        int64_t n = 0;
+        bool last = false;
+        const uint8_t *src = prod.next(&n, &last);
+        const auto t0 = std::chrono::steady_clock::now();
+        if (n) rs.ck(palace_h2d(ctx, rs.text(), src, static_cast<size_t>(n)), "text upload");
+        rs.times.h2d += DeviceReadSet::ms_since(t0);
+        rs.parse(n, last);
+        if (last) break;
+    }
+    rs.times.inflate += prod.inflate_ms();
+}
+
+}  // namespace palace_host
