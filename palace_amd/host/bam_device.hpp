@@ -17,9 +17,48 @@
 
 namespace palace_host {
 
-// members per batch: the device holds ~7 000 of the decoder's wavefronts at a time (28 per CU), and a batch takes the time of its
-// slowest member (~20 ms for 64 KiB) however small it is
-constexpr size_t kDeviceInflateBatch = 8192;
+// Members per launch of palace_bgzf_inflate: a launch takes as long as its slowest member (~20 ms for 64 KiB) however few members it
+// has, and the device holds ~7 000 of the decoder's wavefronts at a time (28 per CU).  (eref's FASTQ in batches of one 32 MiB window,
+// ~500 members, left it mostly idle: 260 ms against the 1M-contig sample's 2.1 GB of text, 44 ms in batches of 8 192.)
+constexpr size_t kMemberBatch = 8192;
+
+// The member table of one batch as palace_bgzf_inflate and palace_crc32_members read it: per member in_off, out_off (int64), in_len,
+// out_len, status, crc (int32), one array of n each.  fill() builds it on the host; the caller sends up the first up_bytes() (the
+// columns in front of status) in one copy and reads status / crc back.  Offsets are relative to the batch's first input byte (in0)
+// and to its first member's output.  inflate() and crc32() return what the palace_* call returns (0: enqueued).
+struct MemberTable {
+    static constexpr size_t kBytes = 32 * kMemberBatch;                    // a batch's table, host and device
+    palace_ctx *ctx;
+    uint8_t *dev;                                                          // kBytes of device memory (the caller's)
+    std::vector<uint8_t> host = std::vector<uint8_t>(kBytes);
+    size_t n = 0;
+    void fill(const BgzfMember *m, size_t count, uint64_t in0)
+    {
+        n = count;
+        int64_t *io = in_off(host.data()), *oo = out_off(host.data());
+        int32_t *il = in_len(host.data()), *ol = out_len(host.data());
+        for (size_t k = 0; k < n; k++) {
+            io[k] = static_cast<int64_t>(m[k].in_off - in0); il[k] = static_cast<int32_t>(m[k].in_len);
+            oo[k] = static_cast<int64_t>(m[k].out_off - m[0].out_off); ol[k] = static_cast<int32_t>(m[k].out_len);
+        }
+    }
+    size_t up_bytes() const { return 24 * n; }
+    // the columns in `base` (host.data() or dev)
+    int64_t *in_off(uint8_t *base) const { return reinterpret_cast<int64_t *>(base); }
+    int64_t *out_off(uint8_t *base) const { return reinterpret_cast<int64_t *>(base + 8 * n); }
+    int32_t *in_len(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + 16 * n); }
+    int32_t *out_len(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + 20 * n); }
+    int32_t *status(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + 24 * n); }
+    uint32_t *crc(uint8_t *base) const { return reinterpret_cast<uint32_t *>(base + 28 * n); }
+    // the batch's compressed bytes (d_in = input byte in0) inflated into d_out; status 0: the member's bytes are there
+    int inflate(const uint8_t *d_in, uint8_t *d_out) const
+    {
+        return palace_bgzf_inflate(ctx, d_in, static_cast<int64_t>(n), in_off(dev), in_len(dev), out_off(dev), out_len(dev), d_out, status(dev));
+    }
+    // crc: the CRC-32 of every member's bytes in d_out
+    int crc32(const uint8_t *d_out) const { return palace_crc32_members(ctx, d_out, static_cast<int64_t>(n), out_off(dev), out_len(dev), crc(dev)); }
+};
+
 constexpr double kDeviceBatchDeadlineS = 20.0;          // a batch takes ~0.1 s; behind this the device is taken to be hung
 
 inline MemberHelper device_inflate_helper(int device)
@@ -29,13 +68,10 @@ inline MemberHelper device_inflate_helper(int device)
         const auto t_start = Clock::now();
         palace_ctx *ctx = nullptr;
         if (palace_ctx_create(device, &ctx)) return;                           // no device: everything stays with the loader's threads
-        size_t B = kDeviceInflateBatch;
-        if (const char *e = std::getenv("PALACE_BAM_DEVICE_BATCH")) B = static_cast<size_t>(std::max(64, std::min(16384, std::atoi(e))));   // (tuning runs)
         void *d_in = nullptr, *d_out = nullptr, *d_meta = nullptr;
         size_t in_cap = 0, out_cap = 0;                                        // sized by the batches claimed, not by the largest batch there could be
-        // per member: in_off, out_off (int64), in_len, out_len, status (int32) -- one array each, one upload
-        const size_t meta_bytes = B * (8 + 8 + 4 + 4 + 4);
-        bool up = !palace_malloc(ctx, meta_bytes, &d_meta);
+        bool up = !palace_malloc(ctx, MemberTable::kBytes, &d_meta);
+        MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
         auto room = [&](void *&p, size_t &cap, size_t need) {
             if (need + 64 <= cap) return true;
             if (p) palace_free(ctx, p);
@@ -44,34 +80,24 @@ inline MemberHelper device_inflate_helper(int device)
             cap = need + need / 8 + 64;
             return true;
         };
-        std::vector<uint8_t> meta(meta_bytes);
-        int64_t *in_off = reinterpret_cast<int64_t *>(meta.data()), *out_off = in_off + B;
-        int32_t *in_len = reinterpret_cast<int32_t *>(out_off + B), *out_len = in_len + B, *status = out_len + B;
-        uint8_t *dm = static_cast<uint8_t *>(d_meta);
         size_t first = 0, n = 0;
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;          // (laps need a sync per phase: traced runs only)
         auto ms_since = [](Clock::time_point a) { return std::chrono::duration<double, std::milli>(Clock::now() - a).count(); };
         double t_up = 0, t_kernel = 0, t_down = 0, t_ready = ms_since(t_start);
         size_t batches = 0, members = 0;
         (void)t_ready;
-        while (up && bm.claim(B, &first, &n)) {
-            const BgzfMember &a = bm.member(first), &z = bm.member(first + n - 1);
+        while (up && bm.claim(kMemberBatch, &first, &n)) {
+            const BgzfMember &a = bm.members[first], &z = bm.members[first + n - 1];
             const uint64_t in0 = a.in_off, in1 = z.in_off + z.in_len, out0 = a.out_off, out1 = z.out_off + z.out_len;
             bool ok = room(d_in, in_cap, static_cast<size_t>(in1 - in0)) && room(d_out, out_cap, static_cast<size_t>(out1 - out0));
-            for (size_t k = 0; k < n; k++) {
-                const BgzfMember &m = bm.member(first + k);
-                in_off[k] = static_cast<int64_t>(m.in_off - in0); in_len[k] = static_cast<int32_t>(m.in_len);
-                out_off[k] = static_cast<int64_t>(m.out_off - out0); out_len[k] = static_cast<int32_t>(m.out_len);
-                status[k] = -1;
-            }
+            tab.fill(&a, n, in0);
+            int32_t *status = tab.status(tab.host.data());
             auto t0 = Clock::now();
-            ok = ok && !palace_h2d_async(ctx, d_in, bm.file_data + in0, static_cast<size_t>(in1 - in0)) && !palace_h2d_async(ctx, d_meta, meta.data(), meta_bytes);
+            ok = ok && !palace_h2d_async(ctx, d_in, bm.file_data + in0, static_cast<size_t>(in1 - in0)) && !palace_h2d_async(ctx, d_meta, tab.host.data(), tab.up_bytes());
             if (trace) { palace_sync(ctx); t_up += ms_since(t0); t0 = Clock::now(); }
-            ok = ok && !palace_bgzf_inflate(ctx, static_cast<const uint8_t *>(d_in), static_cast<int64_t>(n), reinterpret_cast<const int64_t *>(dm),
-                                      reinterpret_cast<const int32_t *>(dm + 16 * B), reinterpret_cast<const int64_t *>(dm + 8 * B),
-                                      reinterpret_cast<const int32_t *>(dm + 20 * B), static_cast<uint8_t *>(d_out), reinterpret_cast<int32_t *>(dm + 24 * B));
+            ok = ok && !tab.inflate(static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_out));
             if (trace) { palace_sync(ctx); t_kernel += ms_since(t0); t0 = Clock::now(); }
-            ok = ok && !palace_d2h_async(ctx, status, dm + 24 * B, 4 * n) && !palace_d2h_async(ctx, bm.out + out0, d_out, static_cast<size_t>(out1 - out0)) &&
+            ok = ok && !palace_d2h_async(ctx, status, tab.status(tab.dev), 4 * n) && !palace_d2h_async(ctx, bm.out + out0, d_out, static_cast<size_t>(out1 - out0)) &&
                  !palace_mark(ctx, 0);
             if (ok && palace_mark_wait_for(ctx, 0, kDeviceBatchDeadlineS)) {
                 // the batch never came back (a kernel or a copy that does not return): its members' bytes may still be written behind

@@ -19,8 +19,6 @@
 //   pseudo-bin 37450    = {[first, behind last) of the contig's lines, (number of lines, 0)}, as htslib writes it
 //   virtual offset      = (file offset of the BGZF member << 16) | offset of the byte inside the member's text
 #pragma once
-#include <zlib.h>
-
 #include <algorithm>
 #include <cstdint>
 #include <cstdio>
@@ -31,43 +29,11 @@
 #include <vector>
 
 #include "bam.hpp"
+#include "bgzf.hpp"
 
 namespace palace_host {
 
-constexpr size_t kBgzfText = 0xff00;                   // bytes of text per member (bgzf.h BGZF_BLOCK_SIZE)
-
 inline void put_le(std::vector<uint8_t> &b, uint64_t v, int bytes) { for (int k = 0; k < bytes; k++) b.push_back(static_cast<uint8_t>(v >> (8 * k))); }
-
-// one BGZF member for `n` (<= 0xff00) bytes of text; throws when zlib fails or the member would not fit 64 KiB
-inline void bgzf_member(const uint8_t *text, size_t n, int level, std::vector<uint8_t> &out)
-{
-    static const uint8_t head[16] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0};
-    const size_t at = out.size();
-    out.insert(out.end(), head, head + 16);
-    out.push_back(0); out.push_back(0);                                      // BSIZE, patched below
-    z_stream zs{};
-    if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw std::runtime_error("deflateInit2 failed");
-    const size_t bound = deflateBound(&zs, static_cast<uLong>(n));
-    out.resize(at + 18 + bound);
-    zs.next_in = const_cast<Bytef *>(text); zs.avail_in = static_cast<uInt>(n);
-    zs.next_out = out.data() + at + 18; zs.avail_out = static_cast<uInt>(bound);
-    const int rc = deflate(&zs, Z_FINISH);
-    const size_t clen = bound - zs.avail_out;
-    deflateEnd(&zs);
-    if (rc != Z_STREAM_END) throw std::runtime_error("deflate failed");
-    out.resize(at + 18 + clen);
-    put_le(out, crc32(crc32(0L, Z_NULL, 0), text, static_cast<uInt>(n)), 4);
-    put_le(out, n, 4);
-    const size_t total = out.size() - at;
-    if (total > 0x10000) throw std::runtime_error("BGZF member larger than 64 KiB");
-    out[at + 16] = static_cast<uint8_t>(total - 1); out[at + 17] = static_cast<uint8_t>((total - 1) >> 8);
-}
-
-inline const uint8_t *bgzf_eof_member()
-{
-    static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 'B', 'C', 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    return eof;
-}
 
 // A BGZF file written from a stream of text: members of exactly kBgzfText bytes (the last one shorter), compressed on `threads`
 // threads a batch at a time, the EOF member at close.  member_off[k] = file offset of member k (member n_members = the EOF member).

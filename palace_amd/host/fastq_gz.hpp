@@ -23,7 +23,7 @@
 #include <vector>
 
 #include "../../include/palace_hip.h"
-#include "bam.hpp"
+#include "bam_device.hpp"
 #include "fastx.hpp"
 
 namespace palace_host {
@@ -164,55 +164,42 @@ inline void ingest_bgzf(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t,
     rs.start_file();
     const uint8_t *file = reinterpret_cast<const uint8_t *>(t.data);
     const int64_t W = rs.window();
-    // Members are inflated kBgzfBatch at a time (a launch takes as long as its slowest member, and the device holds ~7 000 of the
-    // decoder's wavefronts: batches of one 32 MiB window, ~500 members, left it mostly idle -- 260 ms against the 1M-contig sample's
-    // 2.1 GB of text, against 44 ms in batches of 8 192); the parser takes a batch's text a window at a time.  Device memory: <= kBgzfBatch x 64 KiB of text.
-    constexpr size_t kBgzfBatch = 8192;
+    // Members are inflated kMemberBatch at a time (bam_device.hpp); the parser takes a batch's text a window at a time.  Device memory:
+    // <= kMemberBatch x 64 KiB of text.
     std::vector<size_t> cut{0};                                              // batches [cut[k], cut[k + 1])
     uint64_t max_in = 0, batch_out = 0;
     auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
     for (size_t i = 0, out = 0; i < mem.size(); i++) {
-        if (i - cut.back() == kBgzfBatch) { cut.push_back(i); out = 0; }
+        if (i - cut.back() == kMemberBatch) { cut.push_back(i); out = 0; }
         out += mem[i].out_len;
         batch_out = std::max<uint64_t>(batch_out, out);
         max_in = std::max<uint64_t>(max_in, mem[i].in_off + mem[i].in_len + 8 - member_start(cut.back()));
     }
     cut.push_back(mem.size());
-    const size_t max_n = [&] { size_t m = 0; for (size_t k = 0; k + 1 < cut.size(); k++) m = std::max(m, cut[k + 1] - cut[k]); return m; }();
     void *d_in = nullptr, *d_batch = nullptr, *d_meta = nullptr;
     rs.ck(palace_malloc(ctx, static_cast<size_t>(max_in) + 64, &d_in), "compressed window");
     rs.ck(palace_malloc(ctx, static_cast<size_t>(batch_out) + 64, &d_batch), "inflated window");
-    rs.ck(palace_malloc(ctx, max_n * 32 + 64, &d_meta), "member table");
+    rs.ck(palace_malloc(ctx, MemberTable::kBytes, &d_meta), "member table");
     struct Free { palace_ctx *c; void *a, *b, *m; ~Free() { palace_free(c, a); palace_free(c, b); palace_free(c, m); } } free_{ctx, d_in, d_batch, d_meta};
-    // per member: in_off, out_off (int64), in_len, out_len, status, crc (int32) -- one array each, one upload
-    std::vector<uint8_t> meta(max_n * 32);
+    MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
     std::vector<uint8_t> host_out(65536);
     uint64_t file_pos = 0;
     for (size_t k = 0; k + 1 < cut.size(); k++) {
         const size_t i0 = cut[k], n = cut[k + 1] - i0;
         if (n == 0) continue;
         const uint64_t in0 = member_start(i0), in1 = mem[i0 + n - 1].in_off + mem[i0 + n - 1].in_len + 8;
-        int64_t *in_off = reinterpret_cast<int64_t *>(meta.data()), *out_off = in_off + n;
-        int32_t *in_len = reinterpret_cast<int32_t *>(out_off + n), *out_len = in_len + n, *status = out_len + n;
-        uint32_t *crc = reinterpret_cast<uint32_t *>(status + n);
-        uint8_t *dm = static_cast<uint8_t *>(d_meta);
-        int64_t out = 0;
-        for (size_t j = 0; j < n; j++) {
-            const BgzfMember &m = mem[i0 + j];
-            in_off[j] = static_cast<int64_t>(m.in_off - in0); in_len[j] = static_cast<int32_t>(m.in_len);
-            out_off[j] = out; out_len[j] = static_cast<int32_t>(m.out_len);
-            out += static_cast<int64_t>(m.out_len);
-        }
+        tab.fill(&mem[i0], n, in0);
+        const int64_t *out_off = tab.out_off(tab.host.data());
+        int32_t *status = tab.status(tab.host.data());
+        uint32_t *crc = tab.crc(tab.host.data());
+        const int64_t out = out_off[n - 1] + static_cast<int64_t>(mem[i0 + n - 1].out_len);
         auto t0 = std::chrono::steady_clock::now();
         rs.ck(palace_h2d(ctx, d_in, file + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
-        rs.ck(palace_h2d(ctx, d_meta, meta.data(), n * 24), "member table");
+        rs.ck(palace_h2d(ctx, d_meta, tab.host.data(), tab.up_bytes()), "member table");
         rs.times.h2d += DeviceReadSet::ms_since(t0);
         t0 = std::chrono::steady_clock::now();
-        rs.ck(palace_bgzf_inflate(ctx, static_cast<const uint8_t *>(d_in), static_cast<int64_t>(n), reinterpret_cast<const int64_t *>(dm),
-                                  reinterpret_cast<const int32_t *>(dm + 16 * n), reinterpret_cast<const int64_t *>(dm + 8 * n),
-                                  reinterpret_cast<const int32_t *>(dm + 20 * n), static_cast<uint8_t *>(d_batch),
-                                  reinterpret_cast<int32_t *>(dm + 24 * n)), "palace_bgzf_inflate");
-        rs.ck(palace_d2h(ctx, status, dm + 24 * n, 4 * n), "member status");
+        rs.ck(tab.inflate(static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_batch)), "palace_bgzf_inflate");
+        rs.ck(palace_d2h(ctx, status, tab.status(tab.dev), 4 * n), "member status");
         for (size_t j = 0; j < n; j++) {                                     // what the device refused: the host's decoder, zlib behind it
             if (status[j] == 0) continue;
             const BgzfMember &m = mem[i0 + j];
@@ -222,9 +209,8 @@ inline void ingest_bgzf(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t,
         }
         rs.times.inflate += DeviceReadSet::ms_since(t0);
         t0 = std::chrono::steady_clock::now();
-        rs.ck(palace_crc32_members(ctx, static_cast<const uint8_t *>(d_batch), static_cast<int64_t>(n), reinterpret_cast<const int64_t *>(dm + 8 * n),
-                                   reinterpret_cast<const int32_t *>(dm + 20 * n), reinterpret_cast<uint32_t *>(dm + 28 * n)), "palace_crc32_members");
-        rs.ck(palace_d2h(ctx, crc, dm + 28 * n, 4 * n), "member CRC");
+        rs.ck(tab.crc32(static_cast<const uint8_t *>(d_batch)), "palace_crc32_members");
+        rs.ck(palace_d2h(ctx, crc, tab.crc(tab.dev), 4 * n), "member CRC");
         for (size_t j = 0; j < n; j++) {
             const BgzfMember &m = mem[i0 + j];
             uint32_t want;

@@ -9,11 +9,13 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <stdexcept>
 #include <string>
 #include <vector>
 
-#include "inflate_fast.hpp"
+#include "bgzf.hpp"
 #include "fastx.hpp"
+#include "inflate_fast.hpp"
 
 using palace_host::inflate_fast;
 
@@ -150,24 +152,16 @@ static int time_file(const char *path)
 {
     const std::vector<char> f = palace_host::read_file(path);
     const uint8_t *d = reinterpret_cast<const uint8_t *>(f.data());
-    struct Member { size_t in, in_len, out_len; };
-    std::vector<Member> ms;
     size_t total = 0;
-    for (size_t p = 0; p + 18 <= f.size();) {
-        const size_t xlen = d[p + 10] | (d[p + 11] << 8), bsize = (d[p + 16] | (d[p + 17] << 8)) + 1u;     // (BC is the first subfield in what htslib and synthbam write)
-        const size_t isize = d[p + bsize - 4] | (d[p + bsize - 3] << 8) | (d[p + bsize - 2] << 16) | (static_cast<size_t>(d[p + bsize - 1]) << 24);
-        ms.push_back({p + 12 + xlen, bsize - xlen - 20, isize});
-        total += isize;
-        p += bsize;
-    }
+    const std::vector<palace_host::BgzfMember> ms = palace_host::bgzf_members(d, f.size(), &total);
     std::vector<uint8_t> a(65536 + 8), b;
     for (int which = 0; which < 2; which++) {
         const auto t0 = std::chrono::steady_clock::now();
         size_t refused = 0;
-        for (const Member &m : ms) {
+        for (const palace_host::BgzfMember &m : ms) {
             if (!m.out_len) continue;
-            if (which == 0) { if (!inflate_fast(d + m.in, m.in_len, f.size() - m.in - m.in_len, a.data(), m.out_len)) refused++; }
-            else if (!zlib_inflate(d + m.in, m.in_len, b, m.out_len)) refused++;
+            if (which == 0) { if (!inflate_fast(d + m.in_off, m.in_len, f.size() - m.in_off - m.in_len, a.data(), m.out_len)) refused++; }
+            else if (!zlib_inflate(d + m.in_off, m.in_len, b, m.out_len)) refused++;
         }
         const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         std::printf("%-12s %8.1f MB/s  (%zu members, %.1f MB, %zu refused)\n", which ? "zlib" : "inflate_fast", total / s / 1e6, ms.size(), total / 1e6, refused);
@@ -177,6 +171,8 @@ static int time_file(const char *path)
 
 int main(int argc, char **argv)
 {
-    if (argc >= 3 && !std::strcmp(argv[1], "time")) return time_file(argv[2]);
+    if (argc >= 3 && !std::strcmp(argv[1], "time")) {
+        try { return time_file(argv[2]); } catch (const std::exception &e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
+    }
     return self_test();
 }

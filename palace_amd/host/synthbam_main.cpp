@@ -9,8 +9,6 @@
 //   sa.i32 (rows of 8: tid2 pos2 mapq2 nm2 clip_s2 clip_e2 len2 rev2)   targets.tsv (name \t length per line)
 // Record i: qname "q<qkey & 2^48-1 in hex>", CIGAR <ref_len>M[<clip_e>S], 150 pseudo-random bases + binned qualities,
 // NM:C, SA:Z when it has items.
-#include <zlib.h>
-
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
@@ -22,6 +20,10 @@
 #include <string>
 #include <thread>
 #include <vector>
+
+#include "bgzf.hpp"
+
+using namespace palace_host;
 
 namespace {
 
@@ -135,48 +137,32 @@ int main(int argc, char **argv)
             std::memcpy(&o[at], &bs, 4);
         }
     });
-    // BGZF blocks over the concatenation of the parts
+    // BGZF members of kBgzfText bytes over the concatenation of the parts
     std::vector<size_t> start(part.size() + 1, 0);
     for (size_t k = 0; k < part.size(); k++) start[k + 1] = start[k] + part[k].size();
-    const size_t total = start.back(), kBlock = 0xff00, n_blocks = (total + kBlock - 1) / kBlock;
+    const size_t total = start.back(), n_blocks = (total + kBgzfText - 1) / kBgzfText;
     std::vector<std::vector<uint8_t>> z(n_blocks);
     std::atomic<bool> bad{false};
     parallel_for(n_blocks, threads, [&](size_t a, size_t b, int) {
-        std::vector<uint8_t> raw(kBlock);
-        z_stream zs{};
-        if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) { bad = true; return; }
-        for (size_t blk = a; blk < b; blk++) {
-            const size_t lo = blk * kBlock, hi = std::min(total, lo + kBlock);
-            size_t k = std::upper_bound(start.begin(), start.end(), lo) - start.begin() - 1, w = 0;
-            for (size_t p = lo; p < hi;) {
-                const size_t take = std::min(hi, start[k + 1]) - p;
-                std::memcpy(raw.data() + w, part[k].data() + (p - start[k]), take);
-                w += take; p += take; k++;
+        std::vector<uint8_t> raw(kBgzfText);
+        try {
+            for (size_t blk = a; blk < b; blk++) {
+                const size_t lo = blk * kBgzfText, hi = std::min(total, lo + kBgzfText);
+                size_t k = std::upper_bound(start.begin(), start.end(), lo) - start.begin() - 1, w = 0;
+                for (size_t p = lo; p < hi;) {
+                    const size_t take = std::min(hi, start[k + 1]) - p;
+                    std::memcpy(raw.data() + w, part[k].data() + (p - start[k]), take);
+                    w += take; p += take; k++;
+                }
+                bgzf_member(raw.data(), w, level, z[blk]);
             }
-            auto &out = z[blk];
-            out.resize(18 + compressBound(static_cast<uLong>(w)) + 8);
-            deflateReset(&zs);
-            zs.next_in = raw.data(); zs.avail_in = static_cast<uInt>(w);
-            zs.next_out = out.data() + 18; zs.avail_out = static_cast<uInt>(out.size() - 26);
-            if (deflate(&zs, Z_FINISH) != Z_STREAM_END) { bad = true; break; }
-            const size_t clen = out.size() - 26 - zs.avail_out, bsize = 18 + clen + 8;
-            const uint8_t head[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0,
-                                      static_cast<uint8_t>((bsize - 1) & 255), static_cast<uint8_t>((bsize - 1) >> 8)};
-            std::memcpy(out.data(), head, 18);
-            const uint32_t crc = static_cast<uint32_t>(crc32(crc32(0, nullptr, 0), raw.data(), static_cast<uInt>(w))), isz = static_cast<uint32_t>(w);
-            std::memcpy(out.data() + 18 + clen, &crc, 4);
-            std::memcpy(out.data() + 22 + clen, &isz, 4);
-            out.resize(bsize);
-            if (bsize > 65536) { bad = true; break; }
-        }
-        deflateEnd(&zs);
+        } catch (const std::exception &) { bad = true; }
     });
     if (bad) { std::cerr << "synthbam: deflate failed\n"; return 1; }
     FILE *f = std::fopen(argv[2], "wb");
     if (!f) { std::cerr << "synthbam: cannot write " << argv[2] << "\n"; return 1; }
     for (auto &b : z) std::fwrite(b.data(), 1, b.size(), f);
-    static const uint8_t eof[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    std::fwrite(eof, 1, 28, f);
+    std::fwrite(bgzf_eof_member(), 1, 28, f);
     std::fclose(f);
     return 0;
 }
