@@ -434,6 +434,54 @@ int palace_fastq_parse(palace_ctx *ctx, const uint8_t *d_text, int64_t n, int fi
                        uint8_t *d_bases, int64_t bases_cap, int64_t *d_offsets, int64_t offsets_cap, void *d_scratch,
                        size_t scratch_bytes);
 
+/* ---- gzip that is not BGZF: one DEFLATE stream inflated by many wavefronts ------------------------------------------------ */
+
+/* stride: compressed bytes between the places where a block start is searched for (one chunk per place at most); span: compressed
+ * bytes uploaded and worked on at a time; text_cap: the most text resolved at a time (at most 1 GiB).  0 = the default
+ * (16 KiB, 64 MiB, 512 MiB).  Device memory in flight: span + 3 x text_cap + 32 KiB per chunk of a batch (at most 4096 chunks). */
+typedef struct {
+    int64_t stride, span, text_cap;
+    int64_t check_guards;      /* tests: != 0 puts guard bytes around every output buffer and counts the damaged ones */
+} palace_gzip_params;
+
+/* why the device path declined a file (palace_gzip_stats.fallback); the caller then lets zlib decide the file */
+enum {
+    PALACE_GZ_NONE = 0,
+    PALACE_GZ_HEADER = 1,      /* a member header zlib would refuse */
+    PALACE_GZ_DECODE = 2,      /* a chunk on the chain did not decode */
+    PALACE_GZ_CHAIN_OPEN = 3,  /* more certain starts had to be queued in one span than the bound on rounds allows */
+    PALACE_GZ_NO_PROGRESS = 4, /* no block ends inside a whole span */
+    PALACE_GZ_TOO_BIG = 5,     /* one chunk inflates to more than text_cap */
+    PALACE_GZ_TRUNCATED = 6,   /* the file ends inside a stream or a trailer */
+    PALACE_GZ_CRC = 7,
+    PALACE_GZ_ISIZE = 8,
+    PALACE_GZ_TRAILING = 9,    /* bytes that are no gzip member behind the last one */
+    PALACE_GZ_SINK = 10,       /* the sink returned non-zero */
+    PALACE_GZ_MARKER = 11      /* a reference to before the start of a member */
+};
+
+/* chunks_found: block starts the finder reported; chunks_accepted: chunks on the chain (decoded to text); false_hits: reported
+ * starts the chain ran across; rounds: certain starts queued behind the first size pass (a dropped hit, the member behind a
+ * trailer); guards_bad: guard bytes found changed (check_guards; always 0); ms_*: wall time of the stages, each waited for. */
+typedef struct {
+    int64_t chunks_found, chunks_accepted, false_hits, rounds, members, spans, batches, text_bytes;
+    int32_t fallback, guards_bad;
+    double ms_upload, ms_find, ms_size, ms_decode, ms_chain, ms_resolve, ms_crc, ms_sink;
+} palace_gzip_stats;
+
+/* takes the next n bytes of the file's text (device memory, 16-byte aligned, valid until the sink returns); last != 0 with the
+ * file's final bytes (n may be 0).  Non-zero return: stop. */
+typedef int (*palace_gzip_sink)(void *user, const uint8_t *d_text, int64_t n, int last);
+
+/* The text of a gzip file (host memory, every member of it) handed to `sink` in file order, inflated on the device: block starts
+ * found inside the stream at every `stride` (dynamic-Huffman headers that parse completely), the chunks between them sized,
+ * chained on the host, decoded to 16-bit symbols (a literal, or a reference into the 32 KiB before the chunk), the references
+ * resolved through a chain of windows, CRC-32 and ISIZE of every member checked.  Returns 0 also when the device path declines
+ * the file (stats->fallback != 0: damaged input, or a stream it cannot cut): text the sink already took is then void -- a member's
+ * CRC is known only at its end -- and the caller decides the file with zlib.  Negative: a device error.  Synchronises. */
+int palace_gzip_inflate(palace_ctx *ctx, const uint8_t *file, int64_t size, const palace_gzip_params *prm, palace_gzip_sink sink,
+                        void *user, palace_gzip_stats *stats);
+
 /* ---- depth stage: `samtools depth <bam> | awk '{sum+=$3} END {print sum/NR}'` (palace:538-552) ------------------ */
 
 /* The two numbers of that mean.  A match segment is one M / = / X CIGAR operation of a record whose UNMAP, SECONDARY,

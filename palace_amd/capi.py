@@ -46,6 +46,19 @@ class BamCols(C.Structure):
                                       "flag", "mapq", "qkey", "sa_off")]
 
 
+class GzipParams(C.Structure):
+    _fields_ = [("stride", C.c_int64), ("span", C.c_int64), ("text_cap", C.c_int64), ("check_guards", C.c_int64)]
+
+
+class GzipStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("chunks_found", "chunks_accepted", "false_hits", "rounds", "members", "spans", "batches", "text_bytes")] + \
+        [("fallback", C.c_int32), ("guards_bad", C.c_int32)] + \
+        [(k, C.c_double) for k in ("ms_upload", "ms_find", "ms_size", "ms_decode", "ms_chain", "ms_resolve", "ms_crc", "ms_sink")]
+
+
+GZIP_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int)
+
+
 class Stage04Inputs(C.Structure):
     """palace_stage04_inputs"""
     _fields_ = [("n_segs", C.c_int32), ("min_count", C.c_int32), ("seed", C.c_void_p), ("tlen", C.c_void_p), ("rank", C.c_void_p),
@@ -147,6 +160,7 @@ _SIGS = {
     "palace_bgzf_inflate": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_fastq_scratch_bytes": [C.c_int64],          # (returns size_t: restype set below)
     "palace_crc32_members": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_gzip_inflate": [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GzipParams), GZIP_SINK, C.c_void_p, C.POINTER(GzipStats)],
     "palace_fastq_parse": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                            C.c_void_p, C.c_size_t],
     "palace_graph_score_border": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(GraphParams)],
@@ -456,6 +470,31 @@ def crc32_members(ctx: Ctx, data: bytes, lengths) -> np.ndarray:
     finally:
         for b in (d_data, d_off, d_len, d_crc):
             b.free()
+
+
+def gzip_inflate(ctx: Ctx, blob: bytes, stride: int = 0, span: int = 0, text_cap: int = 0, check_guards: bool = False):
+    """The text of the gzip file `blob` as palace_gzip_inflate hands it over, and the call's counters as a dict.  The text is None
+    when the device path declined the file (counters["fallback"] != 0) or the sink did not see the file's last bytes."""
+    blob = bytes(blob)
+    parts, seen_last = [], []
+
+    def take(_user, d_text, n, last):
+        if n:
+            part = np.empty(n, np.uint8)
+            if lib().palace_d2h(ctx.h, part.ctypes.data, d_text, n):
+                return 1
+            parts.append(part.tobytes())
+        if last:
+            seen_last.append(True)
+        return 0
+
+    prm = GzipParams(stride, span, text_cap, int(check_guards))
+    st = GzipStats()
+    buf = np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8)
+    _check(lib().palace_gzip_inflate(ctx.h, buf.ctypes.data, len(blob), C.byref(prm), GZIP_SINK(take), None, C.byref(st)), "palace_gzip_inflate")
+    stats = {k: getattr(st, k) for k, _ in GzipStats._fields_}
+    text = b"".join(parts) if stats["fallback"] == 0 and seen_last else None
+    return text, stats
 
 
 def fastq_read_set(ctx: Ctx, text: bytes, cuts=(), reads0: int = 0, bases0: int = 0):

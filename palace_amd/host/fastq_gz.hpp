@@ -3,8 +3,11 @@
 //   BGZF: the compressed bytes go up a window of members at a time, palace_bgzf_inflate inflates them (a member the device
 //         refuses: inflate_member on the host, uploaded), palace_crc32_members checks every member against its trailer, and
 //         palace_fastq_parse appends the window's sequence lines to the read set.  The text never leaves the device.
-//   other gzip: zlib on a host thread of its own (headers, CRC-32 and ISIZE of every member checked by zlib), the text in chunks
-//         through page-locked staging buffers to the device, parsed there by the same kernels.
+//   other gzip: palace_gzip_inflate cuts the DEFLATE stream at block starts it finds, inflates the chunks on the device, checks
+//         CRC-32 and ISIZE of every member and hands the text to the parser.  What it declines (damaged input, a stream it cannot
+//         cut) goes through zlib on a host thread of its own (headers, CRC-32 and ISIZE of every member checked by zlib), the text
+//         in chunks through page-locked staging buffers to the device, parsed there by the same kernels: zlib's verdict is the
+//         one the user sees.
 //   plain (the other side of a mixed pair): the mapped text goes up a window at a time.
 // Device memory for text in flight is one window (plus its compressed bytes); host memory for inflated text is the staging ring.
 #pragma once
@@ -15,6 +18,8 @@
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
+#include <exception>
 #include <cstring>
 #include <mutex>
 #include <stdexcept>
@@ -56,6 +61,9 @@ public:
     DeviceReadSet &operator=(const DeviceReadSet &) = delete;
 
     int64_t window() const { return window_; }
+    bool timed() const { return timed_; }
+    // forget the reads behind `c` (a cursor() taken earlier): the file they came from is read again
+    void rewind(const palace_fastq_cursor &c) { cur_.reads = c.reads; cur_.bases = c.bases; }
     uint8_t *text() const { return d_text_; }
     const palace_fastq_cursor &cursor() const { return cur_; }
     uint8_t *bases() const { return d_bases_; }
@@ -351,8 +359,62 @@ private:
     std::thread th_;
 };
 
+// The device path: true = the file's reads are in the set; false = declined (the set is as it was).  A device error, or a parser
+// out of room, is thrown.
+inline bool ingest_gzip_device(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t, const std::string &path)
+{
+    const palace_fastq_cursor before = rs.cursor();
+    rs.start_file();
+    palace_gzip_params prm{0, 0, 0, 0};
+#ifdef PALACE_TEST_HOOKS
+    if (const char *v = std::getenv("PALACE_EREF_GZ_STRIDE")) prm.stride = std::atoll(v);    // test builds only
+    if (const char *v = std::getenv("PALACE_EREF_GZ_SPAN")) prm.span = std::atoll(v);
+#endif
+    struct Sink {
+        DeviceReadSet *rs;
+        std::exception_ptr err;
+        static int take(void *user, const uint8_t *d_text, int64_t n, int last)
+        {
+            Sink *self = static_cast<Sink *>(user);
+            try {
+                const int64_t W = self->rs->window();
+                int64_t p = 0;
+                do {                                                         // (windows start 16-byte aligned: W is a multiple of 16)
+                    const int64_t w = std::min(W, n - p);
+                    self->rs->parse_at(d_text + p, w, last && p + w == n);
+                    p += w;
+                } while (p < n);
+            } catch (...) {
+                self->err = std::current_exception();
+                return 1;
+            }
+            return 0;
+        }
+    } sink{&rs, nullptr};
+    palace_gzip_stats st;
+    const double parse0 = rs.times.parse;
+    rs.ck(palace_gzip_inflate(ctx, reinterpret_cast<const uint8_t *>(t.data), static_cast<int64_t>(t.size), &prm, &Sink::take, &sink, &st),
+          "palace_gzip_inflate");
+    if (sink.err) std::rethrow_exception(sink.err);
+    if (rs.timed()) {
+        std::fprintf(stderr, "[eref] gzip on the device: %s: %s; chunks found %lld, accepted %lld, false hits %lld, rounds %lld, members %lld, "
+                     "spans %lld, batches %lld, fallback %d; upload %.1f ms, find %.1f ms, size %.1f ms, decode %.1f ms, chain %.1f ms, "
+                     "resolve %.1f ms, crc %.1f ms, parse %.1f ms\n", path.c_str(), st.fallback ? "declined, zlib on the host decides" : "device path",
+                     static_cast<long long>(st.chunks_found), static_cast<long long>(st.chunks_accepted), static_cast<long long>(st.false_hits),
+                     static_cast<long long>(st.rounds), static_cast<long long>(st.members), static_cast<long long>(st.spans),
+                     static_cast<long long>(st.batches), st.fallback, st.ms_upload, st.ms_find, st.ms_size, st.ms_decode, st.ms_chain, st.ms_resolve,
+                     st.ms_crc, rs.times.parse - parse0);
+        rs.times.h2d += st.ms_upload;
+        rs.times.inflate += st.ms_find + st.ms_size + st.ms_decode + st.ms_chain + st.ms_resolve;
+        rs.times.crc += st.ms_crc;
+    }
+    if (st.fallback) rs.rewind(before);
+    return st.fallback == 0;
+}
+
 inline void ingest_gzip(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t, const std::string &path)
 {
+    if (ingest_gzip_device(rs, ctx, t, path)) return;
     rs.start_file();
     GzipProducer prod(ctx, t, path, rs.window());
     for (;;) {
