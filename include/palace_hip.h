@@ -402,6 +402,25 @@ int palace_graph_copy_numbers(palace_ctx *ctx, const uint64_t *d_consumed, const
 int palace_bgzf_inflate(palace_ctx *ctx, const uint8_t *d_in, int64_t n_members, const int64_t *d_in_off, const int32_t *d_in_len,
                         const int64_t *d_out_off, const int32_t *d_out_len, uint8_t *d_out, int32_t *d_status);
 
+/* ---- BGZF members written on the device: the counterpart of palace_bgzf_inflate ------------------------------------------- */
+
+/* One complete BGZF member per piece of device text, one workgroup each: piece m is the d_len[m] (0 .. 0xff00) bytes at
+ * d_text + d_off[m]; its member -- the 18-byte header with the BC subfield and BSIZE, one DEFLATE block, CRC-32 (d_crc[m], as
+ * palace_crc32_members computes it for the same ranges) and ISIZE -- goes to d_slots + 65536 * m (4-byte aligned; the slot's bytes
+ * behind the member are undefined) and its length to d_member_len[m] (28 .. 65311).  The block is dynamic Huffman (BTYPE 10) over
+ * tokens whose only match candidate is the byte one previous-line-length back (lines end at LF: the text of `samtools depth`
+ * compresses like zlib level 6 this way, other text like its literals alone); a piece that would not become shorter is a stored
+ * block (BTYPE 00), an empty piece the 28-byte EOF member.  The contract is the format, not zlib's bytes: every member inflates to
+ * its piece in zlib and in palace_bgzf_inflate, and the same input always gives the same bytes.  Enqueues only. */
+int palace_bgzf_deflate(palace_ctx *ctx, const uint8_t *d_text, int64_t n_members, const int64_t *d_off, const int32_t *d_len,
+                        const uint32_t *d_crc, uint8_t *d_slots, int32_t *d_member_len);
+
+/* The members of such a batch as consecutive file bytes: d_member_off[m] = sum of the lengths in front of member m
+ * (n_members + 1 entries, the last = all bytes), member m copied to d_file + d_member_off[m] (room for 65311 bytes per member is
+ * always enough).  A batch then leaves the device as one copy of d_member_off[n_members] bytes.  Enqueues only. */
+int palace_bgzf_compact(palace_ctx *ctx, const uint8_t *d_slots, int64_t n_members, const int32_t *d_member_len, uint8_t *d_file,
+                        int64_t *d_member_off);
+
 /* ---- compressed FASTQ for eref: inflated text parsed in HBM -------------------------------------------------------------- */
 
 /* CRC-32 (the gzip polynomial) of n_members byte ranges of device memory, one wavefront each: d_crc[m] = crc32 of the d_len[m]
@@ -500,6 +519,27 @@ int palace_depth_per_contig(palace_ctx *ctx, int64_t n_segs, const int32_t *d_se
                             const int32_t *d_seg_len, int32_t n_targets, const int32_t *d_tlen, const int64_t *d_tbase,
                             int64_t total_len, uint64_t *sum_out, uint64_t *covered_out, uint64_t *d_contig_sum,
                             uint64_t *d_contig_covered);
+
+/* The text of `samtools depth` itself (palace:541), resident on the device: one line `contig <TAB> 1-based position <TAB> depth`
+ * per position with depth > 0, contigs in header order.  create takes the match segments as palace_depth_sum_covered does, d_tbase
+ * with n_targets + 1 entries (the last = total_len), and the contig names as one byte blob: name t = d_names[d_name_off[t] ..
+ * d_name_off[t + 1]).  It keeps the depth of every position (4 B per position + 24 B per tile of 1024 positions, allocated here)
+ * and returns the size of the text, its lines and the sum of its depths: sum / lines is the awk number.  The caller's arrays
+ * other than the segments stay in use until destroy.  Waits for the stream. */
+typedef struct palace_depth_text palace_depth_text;
+int palace_depth_text_create(palace_ctx *ctx, int64_t n_segs, const int32_t *d_seg_tid, const int32_t *d_seg_pos,
+                             const int32_t *d_seg_len, int32_t n_targets, const int32_t *d_tlen, const int64_t *d_tbase,
+                             int64_t total_len, const uint8_t *d_names, const int64_t *d_name_off, palace_depth_text **out,
+                             uint64_t *text_bytes_out, uint64_t *lines_out, uint64_t *sum_out);
+int palace_depth_text_destroy(palace_ctx *ctx, palace_depth_text *dt);
+/* bytes [text_begin, text_end) of the text to d_out[0 ..); a line may straddle either end.  Enqueues only. */
+int palace_depth_text_emit(palace_ctx *ctx, const palace_depth_text *dt, uint64_t text_begin, uint64_t text_end, uint8_t *d_out);
+/* For n_windows ranges [d_win_beg[w], d_win_end[w]) of global positions (contigs end to end: d_tbase[t] + position):
+ * d_text_beg[w] / d_text_end[w] = the text offset of the first line at or behind the range's first / end position, d_lines[w] = the
+ * lines of the range.  With one range per contig and 16 kb window these are the chunks and the linear index of the file's tabix
+ * index.  Enqueues only. */
+int palace_depth_text_windows(palace_ctx *ctx, const palace_depth_text *dt, int64_t n_windows, const int64_t *d_win_beg,
+                              const int64_t *d_win_end, uint64_t *d_text_beg, uint64_t *d_text_end, uint64_t *d_lines);
 
 /* ---- matching: path / cycle decomposition of the conjugate graph ------------------------- */
 

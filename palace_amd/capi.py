@@ -160,6 +160,13 @@ _SIGS = {
     "palace_bgzf_inflate": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_fastq_scratch_bytes": [C.c_int64],          # (returns size_t: restype set below)
     "palace_crc32_members": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_bgzf_deflate": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_bgzf_compact": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_depth_text_create": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                 C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
+    "palace_depth_text_destroy": [C.c_void_p, C.c_void_p],
+    "palace_depth_text_emit": [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p],
+    "palace_depth_text_windows": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_gzip_inflate": [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GzipParams), GZIP_SINK, C.c_void_p, C.POINTER(GzipStats)],
     "palace_fastq_parse": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                            C.c_void_p, C.c_size_t],
@@ -448,6 +455,13 @@ class Ctx:
     def crc32_members(self, d_data_ptr: int, n_members: int, d_off: DevBuf, d_len: DevBuf, d_crc: DevBuf):
         _check(lib().palace_crc32_members(self.h, d_data_ptr, n_members, d_off.ptr, d_len.ptr, d_crc.ptr), "palace_crc32_members")
 
+    def bgzf_deflate(self, d_text_ptr: int, n_members: int, d_off: DevBuf, d_len: DevBuf, d_crc: DevBuf, d_slots: DevBuf, d_member_len: DevBuf):
+        _check(lib().palace_bgzf_deflate(self.h, d_text_ptr, n_members, d_off.ptr, d_len.ptr, d_crc.ptr, d_slots.ptr, d_member_len.ptr),
+               "palace_bgzf_deflate")
+
+    def bgzf_compact(self, d_slots: DevBuf, n_members: int, d_member_len: DevBuf, d_file: DevBuf, d_member_off: DevBuf):
+        _check(lib().palace_bgzf_compact(self.h, d_slots.ptr, n_members, d_member_len.ptr, d_file.ptr, d_member_off.ptr), "palace_bgzf_compact")
+
     def fastq_parse(self, d_text_ptr: int, n: int, final_window: bool, d_cursor: DevBuf, d_bases: DevBuf, bases_cap: int,
                     d_offsets: DevBuf, offsets_cap: int, d_scratch: DevBuf):
         _check(lib().palace_fastq_parse(self.h, d_text_ptr, n, int(final_window), d_cursor.ptr, d_bases.ptr, bases_cap, d_offsets.ptr,
@@ -469,6 +483,28 @@ def crc32_members(ctx: Ctx, data: bytes, lengths) -> np.ndarray:
         return d_crc.to_host()[:len(lens)]
     finally:
         for b in (d_data, d_off, d_len, d_crc):
+            b.free()
+
+
+def bgzf_deflate(ctx: Ctx, pieces, lead: int = 0):
+    """One BGZF member per piece (bytes, at most 0xff00 each), written on the device: CRC-32, DEFLATE and the compaction to file bytes.
+    -> (file bytes, member offsets with the total as last entry).  lead: bytes in front of the first piece (any alignment)."""
+    lens = np.array([len(p) for p in pieces], dtype=np.int32)
+    n = len(lens)
+    offs = (lead + np.concatenate([[0], np.cumsum(lens, dtype=np.int64)[:-1]])).astype(np.int64) if n else np.zeros(0, np.int64)
+    blob = bytes(lead) + b"".join(bytes(p) for p in pieces) + bytes(4)
+    bufs = [ctx.upload(np.frombuffer(blob, dtype=np.uint8)), ctx.upload(offs if n else np.zeros(1, np.int64)),
+            ctx.upload(lens if n else np.zeros(1, np.int32)), ctx.empty(max(1, n), np.uint32), ctx.empty(max(1, n) * 65536, np.uint8),
+            ctx.empty(max(1, n), np.int32), ctx.empty(max(1, n) * 65536, np.uint8), ctx.empty(n + 1, np.int64)]
+    d_text, d_off, d_len, d_crc, d_slots, d_mlen, d_file, d_moff = bufs
+    try:
+        ctx.crc32_members(d_text.ptr, n, d_off, d_len, d_crc)
+        ctx.bgzf_deflate(d_text.ptr, n, d_off, d_len, d_crc, d_slots, d_mlen)
+        ctx.bgzf_compact(d_slots, n, d_mlen, d_file, d_moff)
+        moff = d_moff.to_host()
+        return d_file.to_host()[:int(moff[-1])].tobytes(), moff
+    finally:
+        for b in bufs:
             b.free()
 
 

@@ -8,6 +8,10 @@
 //     first_depth=$(bamdepth --depth-gz <bam>.depth.gz <bam>)
 // writes the per-base depth file itself -- <bam>.depth.gz (the text of `samtools depth`, BGZF) and <bam>.depth.gz.tbi (the index
 // `tabix -s 1 -b 2 -e 2` makes) -- and prints the awk number: the four commands of palace:541-545 as one, host only (depthgz.hpp).
+//     first_depth=$(bamdepth --depth-gz-gpu <bam>.depth.gz <bam>)
+// writes the same two files with the text, its CRC-32, the DEFLATE members and the index's offsets computed on the device
+// (depthgz_device.hpp): same text, same cut into members, same index once virtual offsets are mapped to text offsets; the
+// compressed bytes are the device coder's.  Opt-in; without a device it fails like `bamdepth <bam>`, it does not fall back.
 // (`generateGraph <bam> <fai> <out> auto` uses the same number without a second pass over the BAM.)
 #include <algorithm>
 #include <iostream>
@@ -17,15 +21,18 @@
 #include "device_pick.hpp"
 #include "depth_host.hpp"
 #include "depthgz.hpp"
+#include "depthgz_device.hpp"
 
 using namespace palace_host;
 
 int main(int argc, char **argv)
 {
     const bool per_contig = argc >= 3 && std::string(argv[1]) == "--per-contig";
-    const bool depth_gz = argc >= 4 && std::string(argv[1]) == "--depth-gz";
-    if (argc < 2 || (per_contig && argc < 3) || (std::string(argv[1]) == "--depth-gz" && argc < 4)) {
-        std::cerr << "Usage: " << argv[0] << " [--per-contig | --depth-gz <out.depth.gz>] <bam>\n";
+    const bool gz_mode = argc >= 2 && (std::string(argv[1]) == "--depth-gz" || std::string(argv[1]) == "--depth-gz-gpu");
+    const bool depth_gz_gpu = argc >= 4 && std::string(argv[1]) == "--depth-gz-gpu";
+    const bool depth_gz = argc >= 4 && gz_mode;
+    if (argc < 2 || (per_contig && argc < 3) || (gz_mode && argc < 4)) {
+        std::cerr << "Usage: " << argv[0] << " [--per-contig | --depth-gz <out.depth.gz> | --depth-gz-gpu <out.depth.gz>] <bam>\n";
         return 1;
     }
     const char *bam = depth_gz ? argv[3] : per_contig ? argv[2] : argv[1];
@@ -34,6 +41,24 @@ int main(int argc, char **argv)
     try {
         load_bam(bam, threads, 1, c);
     } catch (const std::exception &e) { std::cerr << e.what() << "\n"; return 1; }
+    if (depth_gz_gpu) {                              // text, CRC-32, DEFLATE and the index's offsets on the device
+        palace_ctx *gctx = nullptr;
+        if (palace_ctx_create(pick_device(), &gctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
+        int code = 0;
+        try {
+            DepthGzDeviceTimes tm;
+            const bool trace = std::getenv("PALACE_TRACE") != nullptr;
+            const DepthGzResult r = write_depth_gz_device(gctx, c, argv[2], trace ? &tm : nullptr);
+            if (trace)
+                std::fprintf(stderr, "[bamdepth] depth-gz-gpu ms: upload %.1f create %.1f emit %.1f crc %.1f deflate+compact %.1f d2h+write %.1f windows %.1f tbi %.1f; "
+                             "text %llu B, file %llu B\n", tm.upload, tm.create, tm.emit, tm.crc, tm.deflate, tm.copy_write, tm.windows, tm.tbi,
+                             static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.file_bytes));
+            if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
+            else std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
+        } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; code = 1; }
+        palace_ctx_destroy(gctx);
+        return code;
+    }
     if (depth_gz) {                                  // no GPU in this mode: text and DEFLATE are host work
         try {
             const DepthGzResult r = write_depth_gz(c, argv[2], threads);
