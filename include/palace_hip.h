@@ -541,6 +541,37 @@ int palace_depth_text_emit(palace_ctx *ctx, const palace_depth_text *dt, uint64_
 int palace_depth_text_windows(palace_ctx *ctx, const palace_depth_text *dt, int64_t n_windows, const int64_t *d_win_beg,
                               const int64_t *d_win_end, uint64_t *d_text_beg, uint64_t *d_text_end, uint64_t *d_lines);
 
+/* ---- the BAM's records found and their match segments made where the inflated stream lies ------------------------------------- */
+
+/* The record walk of the BAM loader (what sam_read1's loop does to the stream, generate_graph.cpp:644) on an inflated stream in
+ * device memory: d_stream[0 .. total), the first alignment record at `first` (behind the header).  The result is DEFINED as the
+ * serial walk from `first`: a record at p needs its 4-byte block_size >= 32, all of its bytes in front of `total`, l_read_name >= 1
+ * and name, CIGAR, bases and qualities that fit block_size; the first offset that fails ends the stream (`stop`; == total for a
+ * well-formed one).  d_starts receives, in file order, the offset of every record's refID (p + 4) when it has room for them all
+ * (cap entries); otherwise -- d_starts may be NULL with cap 0 -- only the count is returned and palace_bam_walk_starts writes them
+ * later from the same scratch.  The walk runs as one guess per chunk of `chunk` bytes (0 = 64 KiB, at least 64) that a chain over
+ * the chunks confirms or repairs: the result never depends on the guesses, the time does (n_ref, the number of targets, only
+ * sharpens them).  stats_out[4] = chunks, guesses that held, chunks the chain walked itself, chunks without a guess.
+ * d_scratch: palace_bam_walk_scratch_bytes(total, first, chunk) bytes, 8-byte aligned.  Waits for the stream. */
+size_t palace_bam_walk_scratch_bytes(int64_t total, int64_t first, int64_t chunk);
+int palace_bam_walk(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, int64_t first, int32_t n_ref, int64_t chunk,
+                    void *d_scratch, size_t scratch_bytes, int64_t *d_starts, int64_t cap, int64_t *n_records_out,
+                    int64_t *stop_out, int64_t stats_out[4]);
+/* the starts of the last palace_bam_walk with these arguments and this scratch (at most cap of them).  Enqueues only. */
+int palace_bam_walk_starts(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, int64_t first, int64_t chunk, const void *d_scratch,
+                           size_t scratch_bytes, int64_t *d_starts, int64_t cap);
+
+/* The match segments of palace_depth_sum_covered from the records themselves (d_starts as palace_bam_walk leaves them): one entry
+ * per M / = / X operation of length > 0 of every record with flags 0x704 clear, 0 <= refID < n_ref and pos >= 0, at pos + the
+ * reference consumed in front of it (M, D, N, =, X), in record order, then operation order.  The CIGAR is the record's own, or
+ * the CG:B,I tag's behind a <l_seq>S<ref>N placeholder (SAM spec 4.2.2: the first CG tag decides; taken when its type is B with
+ * subtype I or i and n_cigar_op <= count < 2^29; the scan of the aux fields stops at one whose size is unknown or past the record).
+ * Without the three arrays, or with cap smaller than the count, nothing is written and *n_segs_out is what a second call needs.
+ * Waits for the stream for the count; the segments are enqueued. */
+int palace_bam_match_segments(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                              int32_t n_ref, int32_t *d_seg_tid, int32_t *d_seg_pos, int32_t *d_seg_len, int64_t cap,
+                              int64_t *n_segs_out);
+
 /* ---- matching: path / cycle decomposition of the conjugate graph ------------------------- */
 
 /* M1. One greedy matching over the arcs of the conjugate graph, computed as rounds of locally

@@ -173,6 +173,12 @@ _SIGS = {
     "palace_graph_score_border": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(GraphParams)],
     "palace_graph_resolve_ex": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(GraphParams), C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_bam_walk_scratch_bytes": [C.c_int64, C.c_int64, C.c_int64],          # (returns size_t: restype set below)
+    "palace_bam_walk": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64,
+                        C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "palace_bam_walk_starts": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64],
+    "palace_bam_match_segments": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_int64, C.POINTER(C.c_int64)],
     "palace_stage04_create": [C.c_void_p, C.POINTER(Stage04Inputs), C.POINTER(C.c_void_p)],
     "palace_stage04_destroy": [C.c_void_p, C.c_void_p],
     "palace_stage04_reserve": [C.c_void_p, C.c_void_p, C.c_int64],
@@ -217,6 +223,7 @@ def lib() -> C.CDLL:
             fn.argtypes = sig
             fn.restype = C.c_int
         _LIB.palace_fastq_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_bam_walk_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -568,6 +575,52 @@ def fastq_read_set(ctx: Ctx, text: bytes, cuts=(), reads0: int = 0, bases0: int 
     finally:
         for buf in (d_win, d_bases, d_offsets, d_scratch, d_cur):
             buf.free()
+
+
+def bam_walk(ctx: Ctx, stream: bytes, first: int, n_ref: int, chunk: int = 0):
+    """palace_bam_walk on the inflated stream `stream` -> (record starts int64, stop offset, stats dict); the count first, then the
+    starts into a buffer of exactly that size, as the loader of `bamdepth --bam-gpu` does."""
+    stream = bytes(stream)
+    total = len(stream)
+    nscr = int(lib().palace_bam_walk_scratch_bytes(total, first, chunk))
+    d_stream = ctx.upload(np.frombuffer(stream, dtype=np.uint8) if total else np.zeros(1, np.uint8))
+    d_scr = DevBuf(ctx, max(nscr, 8))
+    n, stop, stats = C.c_int64(), C.c_int64(), (C.c_int64 * 4)()
+    d_starts = None
+    try:
+        _check(lib().palace_bam_walk(ctx.h, d_stream.ptr, total, first, n_ref, chunk, d_scr.ptr, nscr, None, 0, C.byref(n), C.byref(stop), stats),
+               "palace_bam_walk")
+        d_starts = ctx.empty(max(1, n.value), np.int64)
+        _check(lib().palace_bam_walk_starts(ctx.h, d_stream.ptr, total, first, chunk, d_scr.ptr, nscr, d_starts.ptr, n.value), "palace_bam_walk_starts")
+        starts = d_starts.to_host()[:n.value].copy()
+        return starts, int(stop.value), dict(zip(("chunks", "held", "repaired", "no_start"), (int(v) for v in stats)))
+    finally:
+        for b in (d_stream, d_scr, d_starts):
+            if b is not None:
+                b.free()
+
+
+def bam_match_segments(ctx: Ctx, stream: bytes, starts, n_ref: int):
+    """palace_bam_match_segments -> (tid, pos, len) int32 arrays: the count first, then the segments."""
+    stream = bytes(stream)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    d_stream = ctx.upload(np.frombuffer(stream, dtype=np.uint8) if stream else np.zeros(1, np.uint8))
+    d_st = ctx.upload(st if len(st) else np.zeros(1, np.int64))
+    n = C.c_int64()
+    bufs = [d_stream, d_st]
+    try:
+        _check(lib().palace_bam_match_segments(ctx.h, d_stream.ptr, len(stream), d_st.ptr, len(st), n_ref, None, None, None, 0, C.byref(n)),
+               "palace_bam_match_segments")
+        want = n.value
+        out = [ctx.empty(max(1, want), np.int32) for _ in range(3)]
+        bufs += out
+        _check(lib().palace_bam_match_segments(ctx.h, d_stream.ptr, len(stream), d_st.ptr, len(st), n_ref, out[0].ptr, out[1].ptr, out[2].ptr,
+                                               want, C.byref(n)), "palace_bam_match_segments")
+        assert n.value == want
+        return tuple(b.to_host()[:want].copy() for b in out)
+    finally:
+        for b in bufs:
+            b.free()
 
 
 _ARC_BUFFERS = {}

@@ -12,12 +12,20 @@
 // writes the same two files with the text, its CRC-32, the DEFLATE members and the index's offsets computed on the device
 // (depthgz_device.hpp): same text, same cut into members, same index once virtual offsets are mapped to text offsets; the
 // compressed bytes are the device coder's.  Opt-in; without a device it fails like `bamdepth <bam>`, it does not fall back.
+//     first_depth=$(bamdepth --bam-gpu [--per-contig | --depth-gz-gpu <bam>.depth.gz] <bam>)
+// prints (and writes) the same with the BAM itself read on the device (bam_stream_device.hpp): its BGZF members are inflated and
+// CRC-checked there, the record starts found (palace_bam_walk) and the match segments made (palace_bam_match_segments) where the
+// inflated stream lies, and handed to the depth kernels as device pointers; the host parses the header only.  With --depth-gz-gpu
+// the stage is file -> device -> file.  `--bam-gpu` comes first; `--bam-gpu --depth-gz` is a usage error (that mode is host only).
+// Opt-in; the whole inflated BAM must fit the device; without a device it fails like `bamdepth <bam>`, it never falls back to
+// the host loader.  PALACE_TRACE prints the loader's laps and the walk's statistics.
 // (`generateGraph <bam> <fai> <out> auto` uses the same number without a second pass over the BAM.)
 #include <algorithm>
 #include <iostream>
 #include <thread>
 
 #include "bam.hpp"
+#include "bam_stream_device.hpp"
 #include "device_pick.hpp"
 #include "depth_host.hpp"
 #include "depthgz.hpp"
@@ -25,18 +33,71 @@
 
 using namespace palace_host;
 
+// `bamdepth --bam-gpu ...`: argv[1 ..] are the arguments behind --bam-gpu, parsed as main() parses them
+static int main_bam_gpu(bool per_contig, bool depth_gz_gpu, const char *gz_path, const char *bam, int threads)
+{
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
+    int code = 0;
+    try {
+        DeviceBam b;
+        BamDeviceTimes bt;
+        const bool trace = std::getenv("PALACE_TRACE") != nullptr;
+        try {
+            load_bam_device(ctx, bam, threads, b, trace ? &bt : nullptr);
+        } catch (const std::exception &e) { throw std::runtime_error(std::string(bam) + ": " + e.what()); }
+        if (trace)
+            std::fprintf(stderr, "[bamdepth] bam-gpu ms: member index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f segments %.1f; "
+                         "walk: chunks %lld, guesses held %lld, repaired %lld, without a start %lld; stream %lld B, records %lld, segments %lld, "
+                         "members inflated on the host %lld\n", bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, bt.segments,
+                         static_cast<long long>(b.walk_stats[0]), static_cast<long long>(b.walk_stats[1]), static_cast<long long>(b.walk_stats[2]),
+                         static_cast<long long>(b.walk_stats[3]), static_cast<long long>(b.total), static_cast<long long>(b.n_records),
+                         static_cast<long long>(b.n_segs), static_cast<long long>(b.host_inflated));
+        if (depth_gz_gpu) {
+            DepthGzDeviceTimes tm;
+            const DepthGzResult r = write_depth_gz_device(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_name, b.target_len, gz_path, trace ? &tm : nullptr);
+            if (trace)
+                std::fprintf(stderr, "[bamdepth] depth-gz-gpu ms: upload %.1f create %.1f emit %.1f crc %.1f deflate+compact %.1f d2h+write %.1f windows %.1f tbi %.1f; "
+                             "text %llu B, file %llu B\n", tm.upload, tm.create, tm.emit, tm.crc, tm.deflate, tm.copy_write, tm.windows, tm.tbi,
+                             static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.file_bytes));
+            if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
+            else std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
+        } else {
+            std::string text;
+            std::vector<uint64_t> cs, cc;
+            const int rc = per_contig ? first_depth(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_len, text, nullptr, nullptr, &cs, &cc)
+                                      : first_depth(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_len, text);
+            if (rc < 0) throw std::runtime_error(palace_last_error());
+            if (per_contig) {
+                std::string out;
+                for (size_t t = 0; t < cs.size(); t++)
+                    if (cc[t]) out += b.target_name[t] + "\t" + std::to_string(cs[t]) + "\t" + std::to_string(cc[t]) + "\n";
+                std::cout << out;
+            } else if (rc > 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
+            else std::cout << text << "\n";
+        }
+    } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; code = 1; }
+    palace_ctx_destroy(ctx);
+    return code;
+}
+
 int main(int argc, char **argv)
 {
+    const char *prog = argv[0];
+    const bool bam_gpu = argc >= 2 && std::string(argv[1]) == "--bam-gpu";
+    if (bam_gpu) { argc--; argv++; }                 // the rest is parsed as without it
     const bool per_contig = argc >= 3 && std::string(argv[1]) == "--per-contig";
     const bool gz_mode = argc >= 2 && (std::string(argv[1]) == "--depth-gz" || std::string(argv[1]) == "--depth-gz-gpu");
     const bool depth_gz_gpu = argc >= 4 && std::string(argv[1]) == "--depth-gz-gpu";
     const bool depth_gz = argc >= 4 && gz_mode;
-    if (argc < 2 || (per_contig && argc < 3) || (gz_mode && argc < 4)) {
-        std::cerr << "Usage: " << argv[0] << " [--per-contig | --depth-gz <out.depth.gz> | --depth-gz-gpu <out.depth.gz>] <bam>\n";
+    if (argc < 2 || (per_contig && argc < 3) || (gz_mode && argc < 4) || (bam_gpu && depth_gz && !depth_gz_gpu)) {
+        std::cerr << "Usage: " << prog << " [--bam-gpu] [--per-contig | --depth-gz <out.depth.gz> | --depth-gz-gpu <out.depth.gz>] <bam>"
+                  << "   (--bam-gpu: the BAM is read on the device; not with --depth-gz, the host-only mode)\n";
         return 1;
     }
     const char *bam = depth_gz ? argv[3] : per_contig ? argv[2] : argv[1];
     const int threads = static_cast<int>(std::max(1u, std::min(16u, std::thread::hardware_concurrency())));
+    if (bam_gpu) return main_bam_gpu(per_contig, depth_gz_gpu, depth_gz_gpu ? argv[2] : nullptr, bam, threads);
     BamColumns c;
     try {
         load_bam(bam, threads, 1, c);

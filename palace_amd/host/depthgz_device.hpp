@@ -27,7 +27,10 @@ inline size_t depthgz_batch_members()
 }
 
 // Throws std::runtime_error (with palace_last_error() for a device error).  times: each stage waited for (PALACE_DEPTHGZ_TIMES=1).
-inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, const BamColumns &c, const std::string &gz_path, DepthGzDeviceTimes *times = nullptr)
+// The match segments (ns of them) are in device memory already.
+inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, int64_t n_segs, const int32_t *d_tid, const int32_t *d_pos, const int32_t *d_len,
+                                           const std::vector<std::string> &target_name, const std::vector<int32_t> &target_len, const std::string &gz_path,
+                                           DepthGzDeviceTimes *times = nullptr)
 {
     using clk = std::chrono::steady_clock;
     auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
@@ -47,17 +50,16 @@ inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, const BamColumns &c,
     auto dev = [&](size_t bytes) { void *p = nullptr; ck(palace_malloc(ctx, bytes ? bytes : 1, &p), "palace_malloc"); owned.push_back(p); return p; };
     auto up = [&](const void *h, size_t bytes) { void *p = dev(bytes); ck(palace_h2d(ctx, p, h, bytes), "palace_h2d"); return p; };
 
-    const size_t nt = c.target_len.size(), ns = c.mseg_tid.size();
+    const size_t nt = target_len.size(), ns = static_cast<size_t>(n_segs);
     std::vector<int64_t> base(nt + 1, 0), name_off(nt + 1, 0);
     std::string names;
     for (size_t t = 0; t < nt; t++) {
-        base[t + 1] = base[t] + std::max(0, c.target_len[t]);
-        names += c.target_name[t];
+        base[t + 1] = base[t] + std::max(0, target_len[t]);
+        names += target_name[t];
         name_off[t + 1] = static_cast<int64_t>(names.size());
     }
     auto t0 = clk::now();
-    const int32_t *d_tid = static_cast<const int32_t *>(up(c.mseg_tid.data(), ns * 4)), *d_pos = static_cast<const int32_t *>(up(c.mseg_pos.data(), ns * 4)),
-                  *d_len = static_cast<const int32_t *>(up(c.mseg_len.data(), ns * 4)), *d_tlen = static_cast<const int32_t *>(up(c.target_len.data(), nt * 4));
+    const int32_t *d_tlen = static_cast<const int32_t *>(up(target_len.data(), nt * 4));
     const int64_t *d_base = static_cast<const int64_t *>(up(base.data(), (nt + 1) * 8)), *d_name_off = static_cast<const int64_t *>(up(name_off.data(), (nt + 1) * 8));
     const uint8_t *d_names = static_cast<const uint8_t *>(up(names.data(), names.size()));
     lap(t0, times ? &times->upload : nullptr);
@@ -115,7 +117,7 @@ inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, const BamColumns &c,
     std::vector<int64_t> wb, we;
     std::vector<size_t> first_win(nt + 1, 0);
     for (size_t t = 0; t < nt; t++) {
-        const int64_t L = std::max(0, c.target_len[t]);
+        const int64_t L = std::max(0, target_len[t]);
         for (int64_t p = 0; p < L; p += 16384) { wb.push_back(base[t] + p); we.push_back(base[t] + std::min(L, p + 16384)); }
         first_win[t + 1] = wb.size();
     }
@@ -144,12 +146,33 @@ inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, const BamColumns &c,
             while (r.ioff.size() <= win) r.ioff.push_back(tb[first_win[t] + r.ioff.size()]);
         }
         if (r.bins.empty()) continue;
-        r.name = c.target_name[t];
+        r.name = target_name[t];
         refs.push_back(std::move(r));
     }
     write_tbi(gz_path + ".tbi", refs, w);
     lap(t0, times ? &times->tbi : nullptr);
     return res;
+}
+
+// the same from the match segments the host loader collected: uploaded, then as above
+inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, const BamColumns &c, const std::string &gz_path, DepthGzDeviceTimes *times = nullptr)
+{
+    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
+    const size_t ns = c.mseg_tid.size();
+    void *seg[3] = {nullptr, nullptr, nullptr};
+    struct Cleanup { palace_ctx *ctx; void **seg; ~Cleanup() { for (int k = 0; k < 3; k++) palace_free(ctx, seg[k]); } } cleanup{ctx, seg};
+    const auto t0 = std::chrono::steady_clock::now();
+    const int32_t *host[3] = {c.mseg_tid.data(), c.mseg_pos.data(), c.mseg_len.data()};
+    for (int k = 0; k < 3; k++) {
+        ck(palace_malloc(ctx, ns ? ns * 4 : 1, &seg[k]), "palace_malloc");
+        ck(palace_h2d(ctx, seg[k], host[k], ns * 4), "palace_h2d");
+    }
+    if (times) {
+        ck(palace_sync(ctx), "palace_sync");
+        times->upload += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    return write_depth_gz_device(ctx, static_cast<int64_t>(ns), static_cast<const int32_t *>(seg[0]), static_cast<const int32_t *>(seg[1]),
+                                 static_cast<const int32_t *>(seg[2]), c.target_name, c.target_len, gz_path, times);
 }
 
 }  // namespace palace_host
