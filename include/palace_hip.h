@@ -572,6 +572,50 @@ int palace_bam_match_segments(palace_ctx *ctx, const uint8_t *d_stream, int64_t 
                               int32_t n_ref, int32_t *d_seg_tid, int32_t *d_seg_pos, int32_t *d_seg_len, int64_t cap,
                               int64_t *n_segs_out);
 
+/* ---- the BAM's records decoded where the inflated stream lies: generateGraph's columns and SA items ------------------------------ */
+
+/* Every array of palace_bam_cols except sa_off, for records [0, n_records) of the stream (d_starts as palace_bam_walk leaves them);
+ * the arrays `cols` names are WRITTEN (n_records entries each; cols->n and cols->sa_off are not looked at).  The result is DEFINED as
+ * what the host loader writes for the same record (BamLoad::decode_range, palace_amd/host/bam.cpp):
+ *   tid, pos, mapq, flag, mtid, mpos: the fixed fields.  The CIGAR is the record's own, or the first CG tag's under the conditions of
+ *   palace_bam_match_segments and refID >= 0, pos >= 0.  ref_len counts M, D, N, =, X; read_len counts M, I, S, =, X.  clip_s / clip_e:
+ *   zero-length ops are dropped, the leading S, the trailing S only when more than one op remains; clip_s = -1 for a record without ops.
+ *   nm: the FIRST NM field decides -- types c, C, s, S, i, I are read with their signedness, any other type gives 0 -- default 0.
+ *   The aux scan stops at a field of unknown size or one that runs past the record, and once both NM and SA:Z are found.
+ *   qkey = the seeded 64-bit key of the read name's C-string view (up to the first NUL inside l_read_name, else l_read_name - 1 bytes):
+ *   FNV-1a from 0xcbf29ce484222325 ^ (seed * 0x9e3779b97f4a7c15), then h ^= h >> 32; h *= 0xd6e8feb86659fd93; h ^= h >> 32.
+ * Enqueues only. */
+int palace_bam_columns(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                       uint64_t key_seed, const palace_bam_cols *cols);
+/* qkey alone, with another seed: the way out of a read-name key collision.  Enqueues only. */
+int palace_bam_name_keys(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                         uint64_t key_seed, uint64_t *d_qkey);
+/* How many of the n_pairs pairs of record ordinals (d_pairs[2k], d_pairs[2k + 1]) have different C-string read names: the exactness
+ * guard behind equal keys, without the names leaving the device.  An ordinal outside [0, n_records) counts as different.  Waits. */
+int palace_bam_names_differ(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                            const int64_t *d_pairs, int64_t n_pairs, int64_t *n_differ_out);
+
+/* The header's contig names as a hash table in device memory: name t = d_names[d_name_off[t] .. d_name_off[t + 1]) (n_ref + 1
+ * offsets; blob and offsets stay the caller's and in use until destroy).  A look-up compares the exact name on a hit; of equal names
+ * the LAST one's tid is found.  create allocates the table and enqueues its build; destroy waits for the stream. */
+typedef struct palace_bam_names palace_bam_names;
+int palace_bam_names_create(palace_ctx *ctx, const uint8_t *d_names, const int64_t *d_name_off, int32_t n_ref, palace_bam_names **out);
+int palace_bam_names_destroy(palace_ctx *ctx, palace_bam_names *names);
+
+/* sa_off (n_records + 1 entries) and the parsed SA items, in record order, then list order, as the host loader makes them (bam.cpp:
+ * decode_range, parse_sa, clip_from_text).  The first SA field of type Z is taken (an SA of another type does not end the search);
+ * items are parsed only when 0 <= tid < n_ref; the text is split at ';', empty items are skipped; six comma fields are needed in
+ * getline's sense (a field exists iff at least one byte is left); C-locale white space is trimmed from both ends of every field; an
+ * empty name or position fails the item, and failed items are not listed.  rev2 = the strand field is exactly "-".  The CIGAR text:
+ * any non-digit byte ends an op, zero-length ops are dropped, empty text gives clip_s2 = -1.  pos2, mapq2 and nm2 are glibc's atoi:
+ * optional sign, digits up to the first non-digit, 0 when there are none; beyond the range of long the value saturates (LONG_MAX /
+ * LONG_MIN) and the conversion to int keeps the low 32 bits (-1 / 0).  tid2 = -1 when the name is the record's own contig's, else the
+ * contig's tid (the last duplicate of a name), -1 for an unknown name.
+ * Counted first, written second: without d_sa_off, or with cap smaller than the count, nothing is written and *n_items_out is what a
+ * second call needs.  More items than int32 holds is an error.  Waits for the stream for the count; the items are enqueued. */
+int palace_bam_sa_items(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                        const palace_bam_names *names, int32_t *d_sa_off, palace_sa_item *d_items, int64_t cap, int64_t *n_items_out);
+
 /* ---- matching: path / cycle decomposition of the conjugate graph ------------------------- */
 
 /* M1. One greedy matching over the arcs of the conjugate graph, computed as rounds of locally

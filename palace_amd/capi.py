@@ -179,6 +179,13 @@ _SIGS = {
     "palace_bam_walk_starts": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64],
     "palace_bam_match_segments": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_int64, C.POINTER(C.c_int64)],
+    "palace_bam_columns": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint64, C.POINTER(BamCols)],
+    "palace_bam_name_keys": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_uint64, C.c_void_p],
+    "palace_bam_names_differ": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)],
+    "palace_bam_names_create": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)],
+    "palace_bam_names_destroy": [C.c_void_p, C.c_void_p],
+    "palace_bam_sa_items": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
+                            C.POINTER(C.c_int64)],
     "palace_stage04_create": [C.c_void_p, C.POINTER(Stage04Inputs), C.POINTER(C.c_void_p)],
     "palace_stage04_destroy": [C.c_void_p, C.c_void_p],
     "palace_stage04_reserve": [C.c_void_p, C.c_void_p, C.c_int64],
@@ -618,6 +625,76 @@ def bam_match_segments(ctx: Ctx, stream: bytes, starts, n_ref: int):
                                                want, C.byref(n)), "palace_bam_match_segments")
         assert n.value == want
         return tuple(b.to_host()[:want].copy() for b in out)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+BAM_COLUMNS = (("tid", np.int32), ("pos", np.int32), ("mtid", np.int32), ("mpos", np.int32), ("nm", np.int32), ("ref_len", np.int32),
+               ("read_len", np.int32), ("clip_s", np.int32), ("clip_e", np.int32), ("flag", np.uint16), ("mapq", np.uint8), ("qkey", np.uint64))
+
+
+def bam_decode(ctx: Ctx, stream: bytes, starts, names, key_seed: int = 1):
+    """palace_bam_columns and palace_bam_sa_items on the inflated stream -> (dict of column arrays incl. sa_off, SA items as
+    SA_ITEM_DTYPE); `names` = the header's contig names (bytes), in tid order.  The items are counted first, then written."""
+    stream = bytes(stream)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    n = len(st)
+    blob = b"".join(names)
+    off = np.zeros(len(names) + 1, np.int64)
+    off[1:] = np.cumsum([len(x) for x in names])
+    bufs = [ctx.upload(np.frombuffer(stream, dtype=np.uint8) if stream else np.zeros(1, np.uint8)), ctx.upload(st if n else np.zeros(1, np.int64)),
+            ctx.upload(np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8)), ctx.upload(off)]
+    d_stream, d_st, d_blob, d_off = bufs
+    table = C.c_void_p()
+    try:
+        col = {k: ctx.empty(max(1, n), dt) for k, dt in BAM_COLUMNS}
+        col["sa_off"] = ctx.empty(n + 1, np.int32)
+        bufs += list(col.values())
+        cols = BamCols(n, **{k: b.ptr for k, b in col.items()})
+        _check(lib().palace_bam_columns(ctx.h, d_stream.ptr, len(stream), d_st.ptr, n, key_seed, C.byref(cols)), "palace_bam_columns")
+        _check(lib().palace_bam_names_create(ctx.h, d_blob.ptr, d_off.ptr, len(names), C.byref(table)), "palace_bam_names_create")
+        cnt = C.c_int64()
+        _check(lib().palace_bam_sa_items(ctx.h, d_stream.ptr, len(stream), d_st.ptr, n, table, None, None, 0, C.byref(cnt)), "palace_bam_sa_items")
+        want = cnt.value
+        d_items = ctx.empty(max(1, want), SA_ITEM_DTYPE)
+        bufs.append(d_items)
+        _check(lib().palace_bam_sa_items(ctx.h, d_stream.ptr, len(stream), d_st.ptr, n, table, col["sa_off"].ptr, d_items.ptr, want, C.byref(cnt)),
+               "palace_bam_sa_items")
+        assert cnt.value == want
+        out = {k: b.to_host()[:n + 1 if k == "sa_off" else n].copy() for k, b in col.items()}
+        return out, d_items.to_host()[:want].copy()
+    finally:
+        if table:
+            lib().palace_bam_names_destroy(ctx.h, table)
+        for b in bufs:
+            b.free()
+
+
+def bam_name_keys(ctx: Ctx, stream: bytes, starts, key_seed: int):
+    """palace_bam_name_keys -> uint64 key per record"""
+    stream = bytes(stream)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    bufs = [ctx.upload(np.frombuffer(stream, dtype=np.uint8)), ctx.upload(st), ctx.empty(max(1, len(st)), np.uint64)]
+    try:
+        _check(lib().palace_bam_name_keys(ctx.h, bufs[0].ptr, len(stream), bufs[1].ptr, len(st), key_seed, bufs[2].ptr), "palace_bam_name_keys")
+        return bufs[2].to_host()[:len(st)].copy()
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bam_names_differ(ctx: Ctx, stream: bytes, starts, pairs) -> int:
+    """palace_bam_names_differ: how many of the (ordinal, ordinal) pairs have different read names"""
+    stream = bytes(stream)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    pr = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+    bufs = [ctx.upload(np.frombuffer(stream, dtype=np.uint8)), ctx.upload(st), ctx.upload(pr if len(pr) else np.zeros((1, 2), np.int64))]
+    n = C.c_int64()
+    try:
+        _check(lib().palace_bam_names_differ(ctx.h, bufs[0].ptr, len(stream), bufs[1].ptr, len(st), bufs[2].ptr, len(pr), C.byref(n)),
+               "palace_bam_names_differ")
+        return int(n.value)
     finally:
         for b in bufs:
             b.free()

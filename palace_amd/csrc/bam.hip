@@ -18,6 +18,12 @@
 // Whatever the bytes are, the result is the serial walk's; only the time depends on them (a stream built to defeat every guess
 // is walked by the chain alone: one wave, one dependent load per record).  Every read lies inside [0, total): a step reads the
 // four bytes of its size word only when they are there and a record's fields only when the whole record is.
+//
+// For `generateGraph --bam-gpu` the same record starts feed the decode itself (decode_range of host/bam.cpp, one thread per record: a
+// record's aux fields are a serial scan): palace_bam_columns writes the classify kernel's columns, palace_bam_sa_items parses the SA
+// tags' text into palace_sa_item -- counted, scanned, emitted, as the segments are -- with the contig names looked up in a hash table
+// built on the device from the header's names (palace_bam_names_create), palace_bam_name_keys re-keys the read names and
+// palace_bam_names_differ compares them where they lie.  Every read lies inside the record the walk accepted.
 #include "common.hpp"
 
 namespace palace {
@@ -180,6 +186,35 @@ __device__ __forceinline__ uint64_t aux_size(const uint8_t *d, uint32_t type, in
     }
 }
 
+// The record's CIGAR as the loader sees it (decode_range, host/bam.cpp): its own ops, or the first CG:B,I tag's behind the
+// <l_seq>S<ref>N placeholder of a mapped record (SAM spec 4.2.2; htslib puts it back in place inside bam_read1).  ops = offset of
+// the first op word, aux = offset of the first aux field.  The only place these conditions live on the device.
+struct RecCigar { int64_t ops, n_ops, aux; };
+__device__ __forceinline__ RecCigar record_cigar(const uint8_t *d, int64_t s, int64_t end)
+{
+    const int32_t tid = static_cast<int32_t>(ld32(d, s)), pos = static_cast<int32_t>(ld32(d, s + 4));
+    const int64_t l_name = d[s + 8], n_cig = ld16(d, s + 12), l_seq = ld32(d, s + 16);
+    const int64_t cg = s + 32 + l_name;
+    RecCigar c{cg, n_cig, cg + 4 * n_cig + (l_seq + 1) / 2 + l_seq};
+    if (n_cig > 0 && tid >= 0 && pos >= 0 && (ld32(d, cg) & 15u) == 4 && static_cast<int64_t>(ld32(d, cg) >> 4) == l_seq) {
+        for (int64_t x = c.aux; x + 3 <= end;) {
+            const int64_t v = x + 3;
+            const uint32_t type = d[x + 2];
+            const uint64_t sz = aux_size(d, type, v, end);
+            if (!sz || sz > static_cast<uint64_t>(end - v)) break;
+            if (d[x] == 'C' && d[x + 1] == 'G') {                            // the first CG tag decides
+                if (type == 'B' && (d[v] == 'I' || d[v] == 'i') && ld32(d, v + 1) >= static_cast<uint32_t>(n_cig) && ld32(d, v + 1) < (1u << 29)) {
+                    c.ops = v + 5;
+                    c.n_ops = ld32(d, v + 1);
+                }
+                break;
+            }
+            x = v + static_cast<int64_t>(sz);
+        }
+    }
+    return c;
+}
+
 // f(tid, pos, len) for every match segment of the record whose refID lies at s, in operation order
 template <class F>
 __device__ __forceinline__ void record_segments(const uint8_t *d, int64_t s, int32_t n_ref, F f)
@@ -188,29 +223,10 @@ __device__ __forceinline__ void record_segments(const uint8_t *d, int64_t s, int
     const int32_t tid = static_cast<int32_t>(ld32(d, s)), pos = static_cast<int32_t>(ld32(d, s + 4));
     const uint32_t flag = ld16(d, s + 14);
     if ((flag & 0x704u) || tid < 0 || tid >= n_ref || pos < 0) return;       // what `samtools depth` does not count
-    const int64_t l_name = d[s + 8], n_cig = ld16(d, s + 12), l_seq = ld32(d, s + 16);
-    const int64_t cg = s + 32 + l_name;
-    int64_t ops = cg, n_ops = n_cig;
-    // a CIGAR of more than 65535 ops: the CG:B,I tag behind the <l_seq>S<ref>N placeholder (SAM spec 4.2.2)
-    if (n_cig > 0 && (ld32(d, cg) & 15u) == 4 && static_cast<int64_t>(ld32(d, cg) >> 4) == l_seq) {
-        for (int64_t x = cg + 4 * n_cig + (l_seq + 1) / 2 + l_seq; x + 3 <= end;) {
-            const int64_t v = x + 3;
-            const uint32_t type = d[x + 2];
-            const uint64_t sz = aux_size(d, type, v, end);
-            if (!sz || sz > static_cast<uint64_t>(end - v)) break;
-            if (d[x] == 'C' && d[x + 1] == 'G') {                            // the first CG tag decides
-                if (type == 'B' && (d[v] == 'I' || d[v] == 'i') && ld32(d, v + 1) >= static_cast<uint32_t>(n_cig) && ld32(d, v + 1) < (1u << 29)) {
-                    ops = v + 5;
-                    n_ops = ld32(d, v + 1);
-                }
-                break;
-            }
-            x = v + static_cast<int64_t>(sz);
-        }
-    }
+    const RecCigar c = record_cigar(d, s, end);
     uint32_t rl = 0;
-    for (int64_t k = 0; k < n_ops; k++) {
-        const uint32_t w = ld32(d, ops + 4 * k), op = w & 15u, len = w >> 4;
+    for (int64_t k = 0; k < c.n_ops; k++) {
+        const uint32_t w = ld32(d, c.ops + 4 * k), op = w & 15u, len = w >> 4;
         if (len > 0 && (op == 0 || op == 7 || op == 8)) f(tid, static_cast<int32_t>(static_cast<uint32_t>(pos) + rl), static_cast<int32_t>(len));
         if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;
     }
@@ -285,6 +301,317 @@ __global__ __launch_bounds__(kSegThreads) void bam_seg_emit_kernel(const uint8_t
         if (at < cap) { seg_tid[at] = tid; seg_pos[at] = pos; seg_len[at] = len; }
         at++;
     });
+}
+
+// ---- columns and SA items: decode_range's per-record columns (host/bam.cpp) ------------------------------------------------------
+
+// OpScan of the host: zero-length ops are dropped; the leading S, the trailing S when more than one op remains, the query span
+struct OpScan {
+    int32_t n_ops = 0, first_len = 0, last_len = 0;
+    bool first_s = false, last_s = false;
+    uint32_t len = 0;
+    __device__ __forceinline__ void add(int32_t n, bool is_s, bool in_read)
+    {
+        if (n <= 0) return;
+        if (!n_ops) { first_s = is_s; first_len = n; }
+        last_s = is_s; last_len = n; n_ops++;
+        if (in_read) len += static_cast<uint32_t>(n);
+    }
+    __device__ __forceinline__ int32_t clip_s() const { return n_ops && first_s ? first_len : 0; }
+    __device__ __forceinline__ int32_t clip_e() const { return n_ops > 1 && last_s ? last_len : 0; }
+};
+
+// the C-string view of the read name: up to the first NUL inside l_read_name, else l_read_name - 1 bytes (l_read_name >= 1: the walk)
+__device__ __forceinline__ int64_t name_len(const uint8_t *d, int64_t s)
+{
+    const int64_t l_name = d[s + 8];
+    for (int64_t k = 0; k < l_name; k++)
+        if (d[s + 32 + k] == 0) return k;
+    return l_name - 1;
+}
+
+// name_key of the host
+__device__ __forceinline__ uint64_t name_key(const uint8_t *d, int64_t at, int64_t n, uint64_t seed)
+{
+    uint64_t h = 0xcbf29ce484222325ull ^ (seed * 0x9e3779b97f4a7c15ull);
+    for (int64_t i = 0; i < n; i++) { h ^= d[at + i]; h *= 0x100000001b3ull; }
+    h ^= h >> 32; h *= 0xd6e8feb86659fd93ull; h ^= h >> 32;
+    return h;
+}
+
+// the aux scan of decode_range: the first NM field decides nm (integer types with their signedness, any other type 0), the first SA
+// field of type Z is the SA text [sa, sa + sa_len); the scan stops at a field of unknown size or past the record, and once both are found
+struct RecAux { int32_t nm; int64_t sa, sa_len; };
+__device__ __forceinline__ RecAux record_aux(const uint8_t *d, int64_t x0, int64_t end)
+{
+    RecAux a{0, -1, 0};
+    bool have_nm = false, have_sa = false;
+    for (int64_t x = x0; x + 3 <= end && !(have_nm && have_sa);) {
+        const int64_t v = x + 3;
+        const uint32_t type = d[x + 2];
+        const uint64_t sz = aux_size(d, type, v, end);
+        if (!sz || sz > static_cast<uint64_t>(end - v)) break;
+        if (!have_nm && d[x] == 'N' && d[x + 1] == 'M') {
+            have_nm = true;
+            switch (type) {
+            case 'c': a.nm = static_cast<int8_t>(d[v]); break;
+            case 'C': a.nm = d[v]; break;
+            case 's': a.nm = static_cast<int16_t>(ld16(d, v)); break;
+            case 'S': a.nm = static_cast<int32_t>(ld16(d, v)); break;
+            case 'i': case 'I': a.nm = static_cast<int32_t>(ld32(d, v)); break;
+            default: a.nm = 0;
+            }
+        } else if (!have_sa && d[x] == 'S' && d[x + 1] == 'A' && type == 'Z') {
+            have_sa = true;
+            a.sa = v;
+            a.sa_len = static_cast<int64_t>(sz) - 1;
+        }
+        x = v + static_cast<int64_t>(sz);
+    }
+    return a;
+}
+
+struct ColsOut {
+    int32_t *tid, *pos, *mtid, *mpos, *nm, *ref_len, *read_len, *clip_s, *clip_e;
+    uint16_t *flag;
+    uint8_t *mapq;
+    uint64_t *qkey;
+};
+
+constexpr int kColThreads = 256;
+
+__global__ __launch_bounds__(kColThreads) void bam_columns_kernel(const uint8_t *d, const int64_t *starts, int64_t n, uint64_t seed, ColsOut o)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kColThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t s = starts[i], end = s + static_cast<int64_t>(ld32(d, s - 4));
+    o.tid[i] = static_cast<int32_t>(ld32(d, s));
+    o.pos[i] = static_cast<int32_t>(ld32(d, s + 4));
+    o.mapq[i] = d[s + 9];
+    o.flag[i] = static_cast<uint16_t>(ld16(d, s + 14));
+    o.mtid[i] = static_cast<int32_t>(ld32(d, s + 20));
+    o.mpos[i] = static_cast<int32_t>(ld32(d, s + 24));
+    o.qkey[i] = name_key(d, s + 32, name_len(d, s), seed);
+    const RecCigar c = record_cigar(d, s, end);
+    uint32_t rl = 0, ql = 0;
+    OpScan sc;
+    for (int64_t k = 0; k < c.n_ops; k++) {
+        const uint32_t w = ld32(d, c.ops + 4 * k), op = w & 15u, len = w >> 4;
+        const bool in_read = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;
+        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;
+        if (in_read) ql += len;
+        sc.add(static_cast<int32_t>(len), op == 4, in_read);
+    }
+    o.ref_len[i] = static_cast<int32_t>(rl);
+    o.read_len[i] = static_cast<int32_t>(ql);
+    o.clip_s[i] = c.n_ops ? sc.clip_s() : -1;
+    o.clip_e[i] = sc.clip_e();
+    o.nm[i] = record_aux(d, c.aux, end).nm;
+}
+
+__global__ __launch_bounds__(kColThreads) void bam_name_keys_kernel(const uint8_t *d, const int64_t *starts, int64_t n, uint64_t seed, uint64_t *qkey)
+{
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kColThreads + threadIdx.x;
+    if (i >= n) return;
+    const int64_t s = starts[i];
+    qkey[i] = name_key(d, s + 32, name_len(d, s), seed);
+}
+
+// pairs of record ordinals whose C-string names differ (an ordinal outside [0, n) differs from everything: nothing is read for it)
+__global__ __launch_bounds__(kColThreads) void bam_names_differ_kernel(const uint8_t *d, const int64_t *starts, int64_t n, const int64_t *pairs,
+                                                                       int64_t n_pairs, unsigned long long *differ)
+{
+    const int64_t k = static_cast<int64_t>(blockIdx.x) * kColThreads + threadIdx.x;
+    bool diff = false;
+    if (k < n_pairs) {
+        const int64_t a = pairs[2 * k], b = pairs[2 * k + 1];
+        if (a < 0 || a >= n || b < 0 || b >= n) diff = true;
+        else if (a != b) {
+            const int64_t sa = starts[a], sb = starts[b], la = name_len(d, sa);
+            diff = la != name_len(d, sb);
+            for (int64_t j = 0; !diff && j < la; j++) diff = d[sa + 32 + j] != d[sb + 32 + j];
+        }
+    }
+    const unsigned long long m = __ballot(diff);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(differ, static_cast<unsigned long long>(__popcll(m)));
+}
+
+}  // namespace
+}  // namespace palace
+
+// the header's contig names on the device: the blob and offsets are the caller's, the table is this object's.  slots[k] = a tid or -1;
+// equal names share one slot that holds the largest tid (the last duplicate wins, as BamColumns::tid_of)
+struct palace_bam_names {
+    const uint8_t *names;
+    const int64_t *off;
+    int32_t n_ref;
+    uint32_t mask;
+    int32_t *slots;
+};
+
+namespace palace {
+namespace {
+
+__device__ __forceinline__ uint32_t hash_name(const uint8_t *p, int64_t n)
+{
+    uint64_t h = 0xcbf29ce484222325ull;
+    for (int64_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001b3ull; }
+    h ^= h >> 29; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 32;
+    return static_cast<uint32_t>(h);
+}
+__device__ __forceinline__ bool same_bytes(const uint8_t *a, int64_t na, const uint8_t *b, int64_t nb)
+{
+    if (na != nb) return false;
+    for (int64_t i = 0; i < na; i++)
+        if (a[i] != b[i]) return false;
+    return true;
+}
+__device__ __forceinline__ bool is_name(const palace_bam_names &t, int32_t tid, const uint8_t *p, int64_t n)
+{
+    return same_bytes(t.names + t.off[tid], t.off[tid + 1] - t.off[tid], p, n);
+}
+
+// linear probing without removals: a name sits between its hash's slot and the first empty one (the table is at most half full)
+__global__ __launch_bounds__(kColThreads) void bam_names_build_kernel(palace_bam_names t)
+{
+    const int32_t tid = static_cast<int32_t>(blockIdx.x * kColThreads + threadIdx.x);
+    if (tid >= t.n_ref) return;
+    const uint8_t *p = t.names + t.off[tid];
+    const int64_t n = t.off[tid + 1] - t.off[tid];
+    for (uint32_t at = hash_name(p, n) & t.mask;; at = (at + 1) & t.mask) {
+        const int32_t old = atomicCAS(&t.slots[at], -1, tid);
+        if (old < 0) return;
+        if (is_name(t, old, p, n)) { atomicMax(&t.slots[at], tid); return; }
+    }
+}
+
+__device__ __forceinline__ int32_t tid_of(const palace_bam_names &t, const uint8_t *p, int64_t n)
+{
+    for (uint32_t at = hash_name(p, n) & t.mask;; at = (at + 1) & t.mask) {
+        const int32_t tid = t.slots[at];
+        if (tid < 0) return -1;
+        if (is_name(t, tid, p, n)) return tid;
+    }
+}
+
+__device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); }      // isspace of the C locale
+__device__ __forceinline__ bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
+
+// parseSAItem's cut of one item [b, e) (parse_sa of the host): six comma fields in getline's sense -- a field exists iff at least
+// one byte, possibly just its delimiter, is left -- trimmed at both ends; an empty name or position fails the item
+struct SaFields { int64_t b[6], e[6]; };
+__device__ __forceinline__ bool sa_fields(const uint8_t *d, int64_t b, int64_t e, SaFields *f)
+{
+    int64_t p = b;
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        if (p >= e) return false;
+        int64_t q = p;
+        while (q < e && d[q] != ',') q++;
+        f->b[k] = p;
+        f->e[k] = q;
+        p = q < e ? q + 1 : e;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; k++) {
+        while (f->b[k] < f->e[k] && is_space(d[f->b[k]])) f->b[k]++;
+        while (f->e[k] > f->b[k] && is_space(d[f->e[k] - 1])) f->e[k]--;
+    }
+    return f->b[0] != f->e[0] && f->b[1] != f->e[1];
+}
+
+// glibc's atoi on [b, e): (int) strtol -- optional sign, digits up to the first non-digit, 0 without digits; beyond the range of
+// long the value saturates, and the conversion to int keeps its low 32 bits.  (The fields are trimmed: no leading blanks are left.)
+__device__ __forceinline__ int32_t atoi_field(const uint8_t *d, int64_t b, int64_t e)
+{
+    bool neg = false, over = false;
+    if (b < e && (d[b] == '-' || d[b] == '+')) { neg = d[b] == '-'; b++; }
+    const uint64_t limit = neg ? 0x8000000000000000ull : 0x7fffffffffffffffull;
+    uint64_t v = 0;
+    for (; b < e && is_digit(d[b]); b++) {
+        const uint64_t digit = d[b] - '0';
+        if (v > (limit - digit) / 10) over = true;
+        else v = v * 10 + digit;
+    }
+    if (over) v = limit;
+    return static_cast<int32_t>(static_cast<uint32_t>(neg ? 0 - v : v));
+}
+
+// clip_from_text of the host on [b, e): any non-digit byte ends an op; empty text gives clip_s = -1
+__device__ __forceinline__ void clip_from_text(const uint8_t *d, int64_t b, int64_t e, palace_sa_item *out)
+{
+    if (b == e) { out->clip_s2 = -1; out->clip_e2 = 0; out->len2 = 0; return; }
+    OpScan sc;
+    uint32_t acc = 0;
+    for (; b < e; b++) {
+        const uint8_t ch = d[b];
+        if (is_digit(ch)) acc = acc * 10 + (ch - '0');
+        else { sc.add(static_cast<int32_t>(acc), ch == 'S', ch == 'M' || ch == 'I' || ch == 'S' || ch == '=' || ch == 'X'); acc = 0; }
+    }
+    out->clip_s2 = sc.clip_s(); out->clip_e2 = sc.clip_e(); out->len2 = static_cast<int32_t>(sc.len);
+}
+
+// f(fields) for every item of record i's SA list that parses, in list order: the first SA:Z field of a record with 0 <= tid < n_ref,
+// split at ';', empty items skipped
+template <class F>
+__device__ __forceinline__ void record_sa_items(const uint8_t *d, int64_t s, int32_t n_ref, F f)
+{
+    const int32_t tid = static_cast<int32_t>(ld32(d, s));
+    if (tid < 0 || tid >= n_ref) return;
+    const int64_t end = s + static_cast<int64_t>(ld32(d, s - 4));
+    const int64_t l_name = d[s + 8], n_cig = ld16(d, s + 12), l_seq = ld32(d, s + 16);
+    const RecAux a = record_aux(d, s + 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq, end);
+    if (a.sa < 0) return;
+    for (int64_t p = a.sa, se = a.sa + a.sa_len; p < se;) {
+        int64_t ie = p;
+        while (ie < se && d[ie] != ';') ie++;
+        SaFields fl;
+        if (ie > p && sa_fields(d, p, ie, &fl)) f(fl);
+        p = ie < se ? ie + 1 : se;
+    }
+}
+
+__device__ __forceinline__ long long sa_items_of(const uint8_t *d, const int64_t *starts, int64_t i, int64_t n, int32_t n_ref)
+{
+    long long cnt = 0;
+    if (i < n) record_sa_items(d, starts[i], n_ref, [&](const SaFields &) { cnt++; });
+    return cnt;
+}
+
+__global__ __launch_bounds__(kSegThreads) void bam_sa_count_kernel(const uint8_t *d, const int64_t *starts, int64_t n, int32_t n_ref, long long *block_sum)
+{
+    __shared__ long long lds[kSegThreads / 64 + 1];
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kSegThreads + threadIdx.x;
+    long long total;
+    block_exclusive<long long, kSegThreads>(sa_items_of(d, starts, i, n, n_ref), lds, &total);
+    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(kSegThreads) void bam_sa_emit_kernel(const uint8_t *d, const int64_t *starts, int64_t n, palace_bam_names t,
+                                                                  const long long *block_base, int32_t *sa_off, palace_sa_item *items, int64_t cap)
+{
+    __shared__ long long lds[kSegThreads / 64 + 1];
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * kSegThreads + threadIdx.x;
+    long long total;
+    long long at = block_base[blockIdx.x] + block_exclusive<long long, kSegThreads>(sa_items_of(d, starts, i, n, t.n_ref), lds, &total);
+    if (i >= n) return;
+    sa_off[i] = static_cast<int32_t>(at);
+    const int64_t s = starts[i];
+    const int32_t own = static_cast<int32_t>(ld32(d, s));
+    record_sa_items(d, s, t.n_ref, [&](const SaFields &f) {
+        palace_sa_item it;
+        const uint8_t *name = d + f.b[0];
+        const int64_t name_n = f.e[0] - f.b[0];
+        it.tid2 = is_name(t, own, name, name_n) ? -1 : tid_of(t, name, name_n);
+        it.pos2 = atoi_field(d, f.b[1], f.e[1]);
+        it.rev2 = (f.e[2] - f.b[2] == 1 && d[f.b[2]] == '-') ? 1 : 0;
+        clip_from_text(d, f.b[3], f.e[3], &it);
+        it.mapq2 = atoi_field(d, f.b[4], f.e[4]);
+        it.nm2 = atoi_field(d, f.b[5], f.e[5]);
+        if (at < cap) items[at] = it;
+        at++;
+    });
+    if (i == n - 1) sa_off[n] = static_cast<int32_t>(at);
 }
 
 inline int64_t chunk_bytes(int64_t chunk) { return chunk <= 0 ? kDefaultChunk : chunk < kMinChunk ? kMinChunk : chunk; }
@@ -371,6 +698,129 @@ extern "C" int palace_bam_match_segments(palace_ctx *ctx, const uint8_t *d_strea
     if (!emit || n_segs > cap) return PALACE_OK;                              // the count: the caller comes back with room
     hipLaunchKernelGGL(bam_seg_emit_kernel, dim3(static_cast<unsigned>(nb)), dim3(kSegThreads), 0, ctx->stream, d_stream, d_starts, n_records, n_ref,
                        sums, d_seg_tid, d_seg_pos, d_seg_len, cap);
+    PALACE_HIP_TRY(hipGetLastError());
+    return PALACE_OK;
+}
+
+extern "C" int palace_bam_columns(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                                  uint64_t key_seed, const palace_bam_cols *cols)
+{
+    PALACE_REQUIRE(ctx && total >= 0 && n_records >= 0 && cols, "bad argument");
+    if (n_records == 0) return PALACE_OK;
+    PALACE_REQUIRE(d_stream && d_starts, "null device pointer");
+    PALACE_REQUIRE(cols->tid && cols->pos && cols->mtid && cols->mpos && cols->nm && cols->ref_len && cols->read_len && cols->clip_s && cols->clip_e &&
+                   cols->flag && cols->mapq && cols->qkey, "a column is missing");
+    const int64_t nb = (n_records + kColThreads - 1) / kColThreads;
+    PALACE_REQUIRE(nb < (1ll << 31), "too many records");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    auto w = [](const int32_t *p) { return const_cast<int32_t *>(p); };
+    const ColsOut o{w(cols->tid), w(cols->pos), w(cols->mtid), w(cols->mpos), w(cols->nm), w(cols->ref_len), w(cols->read_len), w(cols->clip_s),
+                    w(cols->clip_e), const_cast<uint16_t *>(cols->flag), const_cast<uint8_t *>(cols->mapq), const_cast<uint64_t *>(cols->qkey)};
+    hipLaunchKernelGGL(bam_columns_kernel, dim3(static_cast<unsigned>(nb)), dim3(kColThreads), 0, ctx->stream, d_stream, d_starts, n_records, key_seed, o);
+    PALACE_HIP_TRY(hipGetLastError());
+    return PALACE_OK;
+}
+
+extern "C" int palace_bam_name_keys(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                                    uint64_t key_seed, uint64_t *d_qkey)
+{
+    PALACE_REQUIRE(ctx && total >= 0 && n_records >= 0, "bad argument");
+    if (n_records == 0) return PALACE_OK;
+    PALACE_REQUIRE(d_stream && d_starts && d_qkey, "null device pointer");
+    const int64_t nb = (n_records + kColThreads - 1) / kColThreads;
+    PALACE_REQUIRE(nb < (1ll << 31), "too many records");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(bam_name_keys_kernel, dim3(static_cast<unsigned>(nb)), dim3(kColThreads), 0, ctx->stream, d_stream, d_starts, n_records, key_seed, d_qkey);
+    PALACE_HIP_TRY(hipGetLastError());
+    return PALACE_OK;
+}
+
+extern "C" int palace_bam_names_differ(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                                       const int64_t *d_pairs, int64_t n_pairs, int64_t *n_differ_out)
+{
+    PALACE_REQUIRE(ctx && total >= 0 && n_records >= 0 && n_pairs >= 0 && n_differ_out, "bad argument");
+    *n_differ_out = 0;
+    if (n_pairs == 0) return PALACE_OK;
+    PALACE_REQUIRE(d_pairs && (n_records == 0 || (d_stream && d_starts)), "null device pointer");
+    const int64_t nb = (n_pairs + kColThreads - 1) / kColThreads;
+    PALACE_REQUIRE(nb < (1ll << 31), "too many pairs");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    int rc = ensure_workspace(ctx, sizeof(unsigned long long));
+    if (rc) return rc;
+    unsigned long long *d_n = static_cast<unsigned long long *>(ctx->ws.ptr), n = 0;
+    PALACE_HIP_TRY(hipMemsetAsync(d_n, 0, sizeof n, ctx->stream));
+    hipLaunchKernelGGL(bam_names_differ_kernel, dim3(static_cast<unsigned>(nb)), dim3(kColThreads), 0, ctx->stream, d_stream, d_starts, n_records, d_pairs,
+                       n_pairs, d_n);
+    PALACE_HIP_TRY(hipGetLastError());
+    PALACE_HIP_TRY(hipMemcpyAsync(&n, d_n, sizeof n, hipMemcpyDeviceToHost, ctx->stream));
+    PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    *n_differ_out = static_cast<int64_t>(n);
+    return PALACE_OK;
+}
+
+extern "C" int palace_bam_names_create(palace_ctx *ctx, const uint8_t *d_names, const int64_t *d_name_off, int32_t n_ref, palace_bam_names **out)
+{
+    PALACE_REQUIRE(ctx && out && n_ref >= 0 && n_ref < (1 << 30), "bad argument");
+    PALACE_REQUIRE(n_ref == 0 || (d_names && d_name_off), "null device pointer");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    uint32_t cap = 64;
+    while (cap < 2u * static_cast<uint32_t>(n_ref)) cap <<= 1;
+    palace_bam_names *t = new palace_bam_names{d_names, d_name_off, n_ref, cap - 1, nullptr};
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&t->slots), static_cast<size_t>(cap) * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemsetAsync(t->slots, 0xff, static_cast<size_t>(cap) * sizeof(int32_t), ctx->stream);      // every slot -1
+    if (e == hipSuccess && n_ref) {
+        hipLaunchKernelGGL(bam_names_build_kernel, dim3((static_cast<unsigned>(n_ref) + kColThreads - 1) / kColThreads), dim3(kColThreads), 0, ctx->stream, *t);
+        e = hipGetLastError();
+    }
+    if (e != hipSuccess) {
+        set_error("palace_bam_names_create: %s", hipGetErrorString(e));
+        if (t->slots) (void)hipFree(t->slots);
+        delete t;
+        return PALACE_EHIP;
+    }
+    *out = t;
+    return PALACE_OK;
+}
+
+extern "C" int palace_bam_names_destroy(palace_ctx *ctx, palace_bam_names *names)
+{
+    if (!names) return PALACE_OK;
+    PALACE_REQUIRE(ctx, "bad argument");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));                       // (a look-up may still be running)
+    PALACE_HIP_TRY(hipFree(names->slots));
+    delete names;
+    return PALACE_OK;
+}
+
+extern "C" int palace_bam_sa_items(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                                   const palace_bam_names *names, int32_t *d_sa_off, palace_sa_item *d_items, int64_t cap, int64_t *n_items_out)
+{
+    PALACE_REQUIRE(ctx && total >= 0 && n_records >= 0 && cap >= 0 && names && n_items_out, "bad argument");
+    PALACE_REQUIRE(d_items || cap == 0, "items without room");
+    *n_items_out = 0;
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    if (n_records == 0) {
+        if (d_sa_off) PALACE_HIP_TRY(hipMemsetAsync(d_sa_off, 0, sizeof(int32_t), ctx->stream));
+        return PALACE_OK;
+    }
+    PALACE_REQUIRE(d_stream && d_starts, "null device pointer");
+    const int64_t nb = (n_records + kSegThreads - 1) / kSegThreads;
+    PALACE_REQUIRE(nb < (1ll << 31), "too many records");
+    int rc = ensure_workspace(ctx, static_cast<size_t>(nb + 1) * sizeof(long long));
+    if (rc) return rc;
+    long long *sums = static_cast<long long *>(ctx->ws.ptr);
+    hipLaunchKernelGGL(bam_sa_count_kernel, dim3(static_cast<unsigned>(nb)), dim3(kSegThreads), 0, ctx->stream, d_stream, d_starts, n_records, names->n_ref, sums);
+    hipLaunchKernelGGL(bam_seg_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
+    PALACE_HIP_TRY(hipGetLastError());
+    long long n_items = 0;
+    PALACE_HIP_TRY(hipMemcpyAsync(&n_items, sums + nb, sizeof n_items, hipMemcpyDeviceToHost, ctx->stream));
+    PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    PALACE_REQUIRE(n_items <= 0x7fffffffll, "more SA items than sa_off's int32 can address");
+    *n_items_out = n_items;
+    if (!d_sa_off || n_items > cap) return PALACE_OK;                         // the count: the caller comes back with room
+    hipLaunchKernelGGL(bam_sa_emit_kernel, dim3(static_cast<unsigned>(nb)), dim3(kSegThreads), 0, ctx->stream, d_stream, d_starts, n_records, *names, sums,
+                       d_sa_off, d_items, cap);
     PALACE_HIP_TRY(hipGetLastError());
     return PALACE_OK;
 }

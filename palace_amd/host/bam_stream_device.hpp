@@ -8,6 +8,8 @@
 // What load_bam (bam.cpp) rejects is rejected here, with its message; its behaviour is not touched.  Device memory held at once: the
 // inflated stream, one batch of compressed bytes, 8 B per record, 12 B per segment (the stream and the starts are given back once the
 // segments are there).  No fall-back: a device error is the caller's error.
+// `generateGraph --bam-gpu` uses the same stream part (load_bam_stream_device: everything up to the record starts) and keeps the stream
+// and the starts alive for palace_bam_columns / palace_bam_sa_items and its read-name guard (generate_graph_main.cpp).
 #pragma once
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -19,6 +21,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <stdexcept>
 #include <string>
 #include <thread>
@@ -30,7 +33,7 @@
 
 namespace palace_host {
 
-struct BamDeviceTimes { double index = 0, header = 0, upload = 0, inflate = 0, crc = 0, walk = 0, segments = 0; };
+struct BamDeviceTimes { double index = 0, header = 0, upload = 0, inflate = 0, crc = 0, walk = 0, segments = 0, columns = 0, sa = 0; };
 
 // members per batch: kMemberBatch; PALACE_OPT_BAM_BATCH=<members> for tests
 inline size_t bam_batch_members()
@@ -50,6 +53,50 @@ inline int64_t bam_walk_chunk()
 // thrown when the device cannot hold what the mode keeps there: the message names the way out
 struct BamDeviceNoRoom : std::runtime_error { using std::runtime_error::runtime_error; };
 
+// device allocations of a loader: freed when it leaves, unless handed on (keep) or given back early
+struct DeviceOwner {
+    palace_ctx *ctx;
+    std::vector<void *> owned;
+    explicit DeviceOwner(palace_ctx *c) : ctx(c) {}
+    DeviceOwner(const DeviceOwner &) = delete;
+    DeviceOwner &operator=(const DeviceOwner &) = delete;
+    ~DeviceOwner() { for (void *p : owned) palace_free(ctx, p); }
+    void *alloc(size_t bytes, const char *what)
+    {
+        void *p = nullptr;
+        if (palace_malloc(ctx, bytes ? bytes : 1, &p))
+            throw BamDeviceNoRoom("--bam-gpu keeps the whole inflated BAM on the device and cannot allocate " + std::to_string(bytes) + " bytes for " + what + " (" +
+                                  palace_last_error() + "); run without --bam-gpu to load the BAM on the host");
+        owned.push_back(p);
+        return p;
+    }
+    void give_back(void *p) { palace_free(ctx, p); owned.erase(std::find(owned.begin(), owned.end(), p)); }
+    void keep(void *p) { owned.erase(std::find(owned.begin(), owned.end(), p)); }        // (the result's from here on)
+    void keep_all() { owned.clear(); }
+};
+
+// The part every --bam-gpu mode shares: the header's targets on the host; the inflated, CRC-checked stream and the record starts
+// on the device, alive as long as this object is.
+struct DeviceBamStream {
+    palace_ctx *ctx = nullptr;
+    std::vector<std::string> target_name;
+    std::vector<int32_t> target_len;
+    int32_t n_ref = 0;
+    int64_t n_records = 0, stop = 0, total = 0, first = 0, host_inflated = 0;
+    int64_t walk_stats[4] = {0, 0, 0, 0};              // chunks, guesses that held, chunks repaired, chunks without a start
+    uint8_t *d_stream = nullptr;
+    int64_t *d_starts = nullptr;
+    DeviceBamStream() = default;
+    DeviceBamStream(const DeviceBamStream &) = delete;
+    DeviceBamStream &operator=(const DeviceBamStream &) = delete;
+    void release()
+    {
+        for (void *p : {static_cast<void *>(d_stream), static_cast<void *>(d_starts)}) if (p) palace_free(ctx, p);
+        d_stream = nullptr; d_starts = nullptr;
+    }
+    ~DeviceBamStream() { release(); }
+};
+
 // What the depth stage needs of a BAM: the header's targets on the host, the match segments on the device.
 struct DeviceBam {
     palace_ctx *ctx = nullptr;
@@ -64,35 +111,41 @@ struct DeviceBam {
     ~DeviceBam() { for (void *p : {static_cast<void *>(d_tid), static_cast<void *>(d_pos), static_cast<void *>(d_len)}) if (p) palace_free(ctx, p); }
 };
 
-// Throws std::runtime_error: load_bam's messages for what load_bam rejects, BamDeviceNoRoom, or a device error with
-// palace_last_error().  times: every stage waited for (traced runs).
-inline void load_bam_device(palace_ctx *ctx, const std::string &path, int threads, DeviceBam &out, BamDeviceTimes *times = nullptr)
-{
+// a stage clock for traced runs: lap() adds the time since the last lap to *acc (waiting for the device first when asked to)
+struct BamDeviceClock {
     using clk = std::chrono::steady_clock;
-    auto le32 = [](const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; };
-    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
-    auto t0 = clk::now();
-    BamDeviceTimes unused;
-    BamDeviceTimes &tm = times ? *times : unused;
-    auto lap = [&](double *acc, bool device) {
-        if (!times) return;
-        if (device) ck(palace_sync(ctx), "palace_sync");
+    palace_ctx *ctx;
+    bool on;
+    clk::time_point t0 = clk::now();
+    void restart() { t0 = clk::now(); }
+    void lap(double *acc, bool device)
+    {
+        if (!on) return;
+        if (device && palace_sync(ctx)) throw std::runtime_error(std::string("palace_sync: ") + palace_last_error());
         const auto t1 = clk::now();
         *acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
         t0 = t1;
-    };
+    }
+};
+
+// The file map, the member index, the header, the batches with inflate and CRC, and the walk.
+// Throws std::runtime_error: load_bam's messages for what load_bam rejects, BamDeviceNoRoom, or a device error with
+// palace_last_error().  times: every stage waited for (traced runs).
+// on_header: called once out.target_name / target_len are there, before the first batch goes up (what depends on the names only can
+// start beside the rest; it may take the two vectors out of `out`).
+inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int threads, DeviceBamStream &out, BamDeviceTimes *times = nullptr,
+                                   const std::function<void()> &on_header = {})
+{
+    auto le32 = [](const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; };
+    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
+    BamDeviceTimes unused;
+    BamDeviceTimes &tm = times ? *times : unused;
+    BamDeviceClock clock{ctx, times != nullptr};
+    auto lap = [&](double *acc, bool device) { clock.lap(acc, device); };
     out.ctx = ctx;
-    std::vector<void *> owned;
-    struct Cleanup { palace_ctx *ctx; std::vector<void *> &owned; ~Cleanup() { for (void *p : owned) palace_free(ctx, p); } } cleanup{ctx, owned};
-    auto give_back = [&](void *p) { palace_free(ctx, p); owned.erase(std::find(owned.begin(), owned.end(), p)); };
-    auto dev = [&](size_t bytes, const char *what) {
-        void *p = nullptr;
-        if (palace_malloc(ctx, bytes ? bytes : 1, &p))
-            throw BamDeviceNoRoom("--bam-gpu keeps the whole inflated BAM on the device and cannot allocate " + std::to_string(bytes) + " bytes for " + what + " (" +
-                                  palace_last_error() + "); run without --bam-gpu to load the BAM on the host");
-        owned.push_back(p);
-        return p;
-    };
+    DeviceOwner own(ctx);
+    auto give_back = [&](void *p) { own.give_back(p); };
+    auto dev = [&](size_t bytes, const char *what) { return own.alloc(bytes, what); };
 
     // ---- the file and its checked member index ----
     struct Mapped {
@@ -116,11 +169,22 @@ inline void load_bam_device(palace_ctx *ctx, const std::string &path, int thread
     size_t total = 0;
     const std::vector<BgzfMember> mem = bgzf_members(file.data, file.size, &total);
     const size_t nb = mem.size();
+    out.total = static_cast<int64_t>(total);
     lap(&tm.index, false);
 
     // ---- the header (BAM spec 4.2), from the front members inflated here: rounds of twice as many members, on the threads ----
     std::vector<uint8_t> hdr;
     size_t hdr_members = 0;
+    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
+    // a header that cannot be read: a front member whose bytes are not the ones its trailer's CRC-32 was made of says so (checked
+    // here only: a header that reads well is checked with every other member, on the device)
+    auto unreadable_header = [&]() -> std::runtime_error {
+        for (size_t i = 0; i < hdr_members; i++)
+            if (static_cast<uint32_t>(::crc32(::crc32(0L, Z_NULL, 0), hdr.data() + mem[i].out_off, static_cast<uInt>(mem[i].out_len))) !=
+                le32(file.data + mem[i].in_off + mem[i].in_len))
+                return std::runtime_error("CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i)));
+        return std::runtime_error("Failed to read BAM header");
+    };
     auto need = [&](size_t upto) {
         while (hdr.size() < upto && hdr_members < nb) {
             const size_t a = hdr_members, b = std::min(nb, a + std::max<size_t>(1, a));
@@ -138,10 +202,10 @@ inline void load_bam_device(palace_ctx *ctx, const std::string &path, int thread
             if (bad) throw std::runtime_error("BGZF inflate failed");
             hdr_members = b;
         }
-        if (hdr.size() < upto) throw std::runtime_error("Failed to read BAM header");
+        if (hdr.size() < upto) throw unreadable_header();
     };
     need(12);
-    if (std::memcmp(hdr.data(), "BAM\1", 4) != 0) throw std::runtime_error("Failed to read BAM header");
+    if (std::memcmp(hdr.data(), "BAM\1", 4) != 0) throw unreadable_header();
     size_t p = 8 + static_cast<size_t>(le32(hdr.data() + 4));
     need(p + 4);
     const int32_t n_ref = static_cast<int32_t>(le32(hdr.data() + p));
@@ -157,10 +221,10 @@ inline void load_bam_device(palace_ctx *ctx, const std::string &path, int thread
     const size_t first = p;
     std::vector<uint8_t>().swap(hdr);
     lap(&tm.header, false);
+    if (on_header) on_header();
 
     // ---- every member inflated into one device buffer, a batch of compressed bytes at a time ----
     const size_t batch = bam_batch_members();
-    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
     uint64_t max_in = 0;
     for (size_t i0 = 0; i0 < nb; i0 += batch) {
         const size_t i1 = std::min(nb, i0 + batch);
@@ -180,7 +244,7 @@ inline void load_bam_device(palace_ctx *ctx, const std::string &path, int thread
             const int64_t *out_off = tab.out_off(tab.host.data());
             int32_t *status = tab.status(tab.host.data());
             uint32_t *crc = tab.crc(tab.host.data());
-            t0 = clk::now();
+            clock.restart();
             ck(palace_h2d(ctx, d_in, file.data + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
             ck(palace_h2d(ctx, d_meta, tab.host.data(), tab.up_bytes()), "member table");
             lap(&tm.upload, true);
@@ -207,8 +271,8 @@ inline void load_bam_device(palace_ctx *ctx, const std::string &path, int thread
         give_back(d_meta);
     }
 
-    // ---- the records' starts, then their match segments: each counted first, then written into exactly that much memory ----
-    t0 = clk::now();
+    // ---- the records' starts: counted first, then written into exactly that much memory ----
+    clock.restart();
     const int64_t chunk = bam_walk_chunk();
     const size_t scratch_bytes = palace_bam_walk_scratch_bytes(static_cast<int64_t>(total), static_cast<int64_t>(first), chunk);
     void *d_scratch = dev(scratch_bytes, "the record walk");
@@ -220,21 +284,44 @@ inline void load_bam_device(palace_ctx *ctx, const std::string &path, int thread
     ck(palace_sync(ctx), "palace_sync");                                    // (the starts are written: the walk's table can go)
     lap(&tm.walk, true);
     give_back(d_scratch);
-    ck(palace_bam_match_segments(ctx, d_stream, static_cast<int64_t>(total), d_starts, out.n_records, n_ref, nullptr, nullptr, nullptr, 0, &out.n_segs),
+    own.keep(d_stream);
+    own.keep(d_starts);
+    out.d_stream = d_stream;
+    out.d_starts = d_starts;
+    out.n_ref = n_ref;
+    out.total = static_cast<int64_t>(total);
+    out.first = static_cast<int64_t>(first);
+}
+
+// `bamdepth --bam-gpu`: the stream part, then the match segments -- counted first, then written into exactly that much memory; the
+// stream and the starts are given back once the segments are there.
+inline void load_bam_device(palace_ctx *ctx, const std::string &path, int threads, DeviceBam &out, BamDeviceTimes *times = nullptr)
+{
+    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
+    BamDeviceTimes unused;
+    BamDeviceTimes &tm = times ? *times : unused;
+    DeviceBamStream st;
+    load_bam_stream_device(ctx, path, threads, st, times);
+    BamDeviceClock clock{ctx, times != nullptr};
+    out.ctx = ctx;
+    out.target_name.swap(st.target_name);
+    out.target_len.swap(st.target_len);
+    out.n_records = st.n_records; out.stop = st.stop; out.total = st.total; out.first = st.first; out.host_inflated = st.host_inflated;
+    std::copy(st.walk_stats, st.walk_stats + 4, out.walk_stats);
+    DeviceOwner own(ctx);
+    ck(palace_bam_match_segments(ctx, st.d_stream, st.total, st.d_starts, st.n_records, st.n_ref, nullptr, nullptr, nullptr, 0, &out.n_segs),
        "palace_bam_match_segments");
     int32_t **seg[3] = {&out.d_tid, &out.d_pos, &out.d_len};
     for (int32_t **s : seg) {
-        *s = static_cast<int32_t *>(dev(static_cast<size_t>(out.n_segs) * 4, "the match segments"));
-        owned.pop_back();                                                    // (the result's from here on)
+        *s = static_cast<int32_t *>(own.alloc(static_cast<size_t>(out.n_segs) * 4, "the match segments"));
+        own.keep(*s);                                                        // (the result's from here on)
     }
     int64_t again = 0;
-    ck(palace_bam_match_segments(ctx, d_stream, static_cast<int64_t>(total), d_starts, out.n_records, n_ref, out.d_tid, out.d_pos, out.d_len, out.n_segs,
-                                 &again), "palace_bam_match_segments");
+    ck(palace_bam_match_segments(ctx, st.d_stream, st.total, st.d_starts, st.n_records, st.n_ref, out.d_tid, out.d_pos, out.d_len, out.n_segs, &again),
+       "palace_bam_match_segments");
     if (again != out.n_segs) throw std::runtime_error("palace_bam_match_segments: two counts of one stream differ");
     ck(palace_sync(ctx), "palace_sync");
-    lap(&tm.segments, true);
-    out.total = static_cast<int64_t>(total);
-    out.first = static_cast<int64_t>(first);
+    clock.lap(&tm.segments, true);
 }
 
 }  // namespace palace_host

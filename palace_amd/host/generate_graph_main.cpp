@@ -27,6 +27,7 @@
 
 #include "bam.hpp"
 #include "bam_device.hpp"
+#include "bam_stream_device.hpp"
 #include "depth_host.hpp"
 #include "fastx.hpp"
 #include "stage04_fused.hpp"
@@ -55,6 +56,8 @@ void usage(const char *prog)            // same option surface as generate_graph
               << "  --min-score <double>      (accepted, unused as in the reference)\n"
               << "  --debug                   JUNC lines carry their supporting reads (' READS: name(flag) ...') and the per-read\n"
               << "                            text of the reference's debug mode goes to stderr\n"
+              << "  --bam-gpu                 the BAM is inflated, CRC-checked, walked and decoded into the kernels' columns and SA items\n"
+              << "                            on the device (opt-in; the whole inflated BAM must fit it; not with --debug)\n"
               << "Stage 04 in this process (optional; every file of palace:566-600, none read back):\n"
               << "  --hit-seqs F --node-scores F --blast F --fasta-fai F --paths F   inputs of filter_graph.py (+ --blast-ratio, --score-threshold: 0.7)\n"
               << "  --filtered-pre F --filtered F --all-hit-segs F                  its outputs (F after uniq)\n"
@@ -236,6 +239,59 @@ void name_ranks(const std::vector<std::string> &names, std::vector<int32_t> &by_
     }
 }
 
+// `--bam-gpu`: the per-record columns and the SA items made where the inflated stream lies (palace_bam_columns, palace_bam_sa_items):
+// 51 B per record, 32 B per SA item; the contig names go up once as a blob for the SA items' name look-up.  Throws like the loader.
+struct DeviceColumns {
+    palace_bam_cols cols{};
+    uint64_t *d_qkey = nullptr;
+    palace_sa_item *d_sa = nullptr;
+    int64_t n_sa = 0;
+};
+void decode_on_device(palace_ctx *ctx, const DeviceBamStream &st, const std::vector<std::string> &names, uint64_t seed, DeviceColumns &out,
+                      BamDeviceTimes *times)
+{
+    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
+    BamDeviceTimes unused;
+    BamDeviceTimes &tm = times ? *times : unused;
+    BamDeviceClock clock{ctx, times != nullptr};
+    DeviceOwner own(ctx);
+    const size_t n = static_cast<size_t>(st.n_records);
+    auto col32 = [&] { return static_cast<int32_t *>(own.alloc(n * 4, "the record columns")); };
+    palace_bam_cols &c = out.cols;
+    c.n = st.n_records;
+    c.tid = col32(); c.pos = col32(); c.mtid = col32(); c.mpos = col32(); c.nm = col32(); c.ref_len = col32(); c.read_len = col32();
+    c.clip_s = col32(); c.clip_e = col32();
+    c.flag = static_cast<uint16_t *>(own.alloc(n * 2, "the record columns"));
+    c.mapq = static_cast<uint8_t *>(own.alloc(n, "the record columns"));
+    c.qkey = out.d_qkey = static_cast<uint64_t *>(own.alloc(n * 8, "the record columns"));
+    int32_t *d_sa_off = static_cast<int32_t *>(own.alloc((n + 1) * 4, "the record columns"));
+    c.sa_off = d_sa_off;
+    ck(palace_bam_columns(ctx, st.d_stream, st.total, st.d_starts, st.n_records, seed, &c), "palace_bam_columns");
+    clock.lap(&tm.columns, true);
+    // the header's names for the SA items' look-up: one blob, offsets, the table built from them on the device
+    std::vector<int64_t> off(names.size() + 1, 0);
+    for (size_t t = 0; t < names.size(); t++) off[t + 1] = off[t] + static_cast<int64_t>(names[t].size());
+    std::string blob;
+    blob.reserve(static_cast<size_t>(off.back()));
+    for (const std::string &nm : names) blob += nm;
+    uint8_t *d_blob = static_cast<uint8_t *>(own.alloc(blob.size(), "the contig names"));
+    int64_t *d_off = static_cast<int64_t *>(own.alloc(off.size() * 8, "the contig names"));
+    ck(palace_h2d(ctx, d_blob, blob.data(), blob.size()), "contig names");
+    ck(palace_h2d(ctx, d_off, off.data(), off.size() * 8), "contig names");
+    palace_bam_names *table = nullptr;
+    ck(palace_bam_names_create(ctx, d_blob, d_off, static_cast<int32_t>(names.size()), &table), "palace_bam_names_create");
+    struct Table { palace_ctx *ctx; palace_bam_names *t; ~Table() { palace_bam_names_destroy(ctx, t); } } table_guard{ctx, table};
+    ck(palace_bam_sa_items(ctx, st.d_stream, st.total, st.d_starts, st.n_records, table, nullptr, nullptr, 0, &out.n_sa), "palace_bam_sa_items");
+    out.d_sa = static_cast<palace_sa_item *>(own.alloc(static_cast<size_t>(out.n_sa) * sizeof(palace_sa_item), "the SA items"));
+    int64_t again = 0;
+    ck(palace_bam_sa_items(ctx, st.d_stream, st.total, st.d_starts, st.n_records, table, d_sa_off, out.d_sa, out.n_sa, &again), "palace_bam_sa_items");
+    if (again != out.n_sa) throw std::runtime_error("palace_bam_sa_items: two counts of one stream differ");
+    ck(palace_sync(ctx), "palace_sync");
+    clock.lap(&tm.sa, true);
+    own.give_back(d_blob);                                                   // (the table goes with table_guard, behind the sync)
+    own.give_back(d_off);
+    own.keep_all();
+}
 
 }  // namespace
 
@@ -243,13 +299,14 @@ int main(int argc, char **argv)
 {
     palace_graph_params prm{300, 0, 5, 1, 0, 0, 0.80};
     int min_count = 5;
-    bool debug = false;
+    bool debug = false, bam_gpu = false;
     static struct option long_opts[] = {{"max-span-frac", required_argument, 0, 1000},
                                         {"both-order", required_argument, 0, 1001},
                                         {"lib", required_argument, 0, 1002},
                                         {"min-count", required_argument, 0, 1003},
                                         {"min-score", required_argument, 0, 1004},
                                         {"debug", no_argument, 0, 1005},
+                                        {"bam-gpu", no_argument, 0, 1006},
                                         {"hit-seqs", required_argument, 0, 1100}, {"node-scores", required_argument, 0, 1101},
                                         {"blast", required_argument, 0, 1102}, {"fasta-fai", required_argument, 0, 1103},
                                         {"paths", required_argument, 0, 1104}, {"blast-ratio", required_argument, 0, 1105},
@@ -278,6 +335,7 @@ int main(int argc, char **argv)
         case 1003: min_count = std::max(1, std::atoi(optarg)); break;
         case 1004: break;
         case 1005: debug = true; break;
+        case 1006: bam_gpu = true; break;
         case 1100: s4o.gene_file = optarg; break;
         case 1101: s4o.score_file = optarg; break;
         case 1102: s4o.blast_file = optarg; break;
@@ -308,6 +366,10 @@ int main(int argc, char **argv)
         std::cerr << "generateGraph: --debug goes with the plain four-argument call, not with the stage-04 outputs\n";
         return 1;
     }
+    if (bam_gpu && debug) {                       // (the per-read text is written from host columns and names, which this mode never makes)
+        std::cerr << "generateGraph: --debug needs the host loader: run it without --bam-gpu\n";
+        return 1;
+    }
     const std::string bam_path = argv[optind], fai_path = argv[optind + 1], out_path = argv[optind + 2];
     // <avgDepth> = "auto": the depth stage (palace:538-552) is done here, on the records this run decodes anyway; the value
     // goes through the same text the driver would have passed ("%.6g" of awk, then atof)
@@ -321,16 +383,6 @@ int main(int argc, char **argv)
     c.want_match_segments = auto_depth;                         // (only the depth stage reads them: 6.7 M triples at 1M contigs)
     const int threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
     uint64_t seed = 1;
-    BamLoad *load = nullptr;
-    try {
-        // header parsed, the rest of the file is being inflated -- by the threads, and by the device once its runtime is up (bam_device.hpp)
-        load = load_bam_begin(bam_path, threads, c, device_inflate_helpers(device));
-    } catch (const std::exception &e) {
-        std::cerr << e.what() << "\n";
-        return 1;
-    }
-    tr.lap("bam header");
-    const int32_t nt = static_cast<int32_t>(c.target_name.size());
     // what depends on the target names only runs beside the inflate / decode of the records: the name ranks, the FASTG
     // keys, and the HIP runtime coming up
     std::vector<int32_t> by_name, rank;
@@ -339,33 +391,88 @@ int main(int argc, char **argv)
     int ctx_rc = 0;
     std::string ctx_err;
     Stage04Side s4side;
-    std::thread side04;
+    std::thread side04, side, side2, hip_up;
     auto join04 = [&] { if (side04.joinable()) side04.join(); };
-    std::thread side([&] { Trace t("generateGraph/names"); name_ranks(c.target_name, by_name, rank); t.lap("name ranks"); });
-    std::thread side2([&] { Trace t("generateGraph/fastg"); fkeys = fastg_keys(fai_path, c, 8); t.lap("fastg keys"); });
-    std::thread hip_up([&] {
-        ctx_rc = palace_ctx_create(device, &ctx);
-        if (ctx_rc) ctx_err = palace_last_error();
-    });
     palace_stage04 *s4obj = nullptr;
     std::string s4err;
-    if (s4o.enabled())                                            // beside the inflate, like the rest: the side files, then (once the
-        side04 = std::thread([&] {                               // name ranks are there) the resident object and its scratch on the device
-            stage04_read_side_files(s4o, c, s4side);
-            side.join();
-            bool unique_names = true;
-            for (int32_t k = 1; k < nt && unique_names; k++) unique_names = rank[by_name[k]] != rank[by_name[k - 1]];
-            if (!unique_names) { s4err = "stage 04 in this process needs distinct target names; run the stages separately"; return; }
-            s4obj = stage04_prepare(s4o, c, s4side, rank, min_count, std::max<int64_t>(1 << 20, static_cast<int64_t>(load_bam_size_hint(load)) / 2400), s4err);
+    int32_t nt = 0;
+    // started once the header is in `c` (target names, lengths, the name index); stream_bytes: the inflated stream's size
+    auto start_side_work = [&](size_t stream_bytes) {
+        nt = static_cast<int32_t>(c.target_name.size());
+        side = std::thread([&] { Trace t("generateGraph/names"); name_ranks(c.target_name, by_name, rank); t.lap("name ranks"); });
+        side2 = std::thread([&] { Trace t("generateGraph/fastg"); fkeys = fastg_keys(fai_path, c, 8); t.lap("fastg keys"); });
+        if (s4o.enabled())                                        // beside the inflate, like the rest: the side files, then (once the
+            side04 = std::thread([&, stream_bytes] {             // name ranks are there) the resident object and its scratch on the device
+                stage04_read_side_files(s4o, c, s4side);
+                side.join();
+                bool unique_names = true;
+                for (int32_t k = 1; k < nt && unique_names; k++) unique_names = rank[by_name[k]] != rank[by_name[k - 1]];
+                if (!unique_names) { s4err = "stage 04 in this process needs distinct target names; run the stages separately"; return; }
+                s4obj = stage04_prepare(s4o, c, s4side, rank, min_count, std::max<int64_t>(1 << 20, static_cast<int64_t>(stream_bytes) / 2400), s4err);
+            });
+    };
+    auto join_side_work = [&] { join04(); if (side.joinable()) side.join(); if (side2.joinable()) side2.join(); if (hip_up.joinable()) hip_up.join(); };
+    DeviceBamStream dstream;                                    // --bam-gpu: the inflated stream and the record starts, until the name guard is through
+    DeviceColumns dcols;
+    if (bam_gpu) {
+        // file -> device -> columns: the context first (nothing else can start without it), then the stream part of bam_stream_device.hpp
+        // with the name-only work started at its header, then the decode kernels
+        if (palace_ctx_create(device, &ctx)) { std::cerr << "generateGraph: cannot set up the GPU: " << palace_last_error() << "\n"; return 1; }
+        BamDeviceTimes bt;
+        const bool trace = std::getenv("PALACE_TRACE") != nullptr;
+        try {
+            load_bam_stream_device(ctx, bam_path, threads, dstream, trace ? &bt : nullptr, [&] {
+                c.target_name.swap(dstream.target_name);
+                c.target_len.swap(dstream.target_len);
+                // the name index over the names just taken (its keys are views of those strings: they stay where they are from here on)
+                const size_t nr = c.target_name.size();
+                c.tid_names.reserve(nr + 16);
+                c.tid_of_name.reserve(nr + 16);
+                for (size_t i = 0; i < nr; i++) {
+                    const int k = c.tid_names.intern(c.target_name[i]);
+                    if (static_cast<size_t>(k) >= c.tid_of_name.size()) c.tid_of_name.resize(static_cast<size_t>(k) + 1);
+                    c.tid_of_name[static_cast<size_t>(k)] = static_cast<int32_t>(i);
+                }
+                tr.lap("bam header");
+                start_side_work(static_cast<size_t>(dstream.total));
+            });
+            tr.lap("bam stream on the device (inflate, crc, walk)");
+            decode_on_device(ctx, dstream, c.target_name, seed, dcols, trace ? &bt : nullptr);
+        } catch (const std::exception &e) {
+            std::cerr << e.what() << "\n";
+            join_side_work();
+            return 1;
+        }
+        if (trace)
+            std::fprintf(stderr, "[generateGraph] bam-gpu ms: index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f columns %.1f sa %.1f; "
+                         "stream %lld B, records %lld, SA items %lld, members inflated on the host %lld\n", bt.index, bt.header, bt.upload, bt.inflate, bt.crc,
+                         bt.walk, bt.columns, bt.sa, static_cast<long long>(dstream.total), static_cast<long long>(dstream.n_records),
+                         static_cast<long long>(dcols.n_sa), static_cast<long long>(dstream.host_inflated));
+        tr.lap("bam records (device columns + SA items)");
+    } else {
+        BamLoad *load = nullptr;
+        try {
+            // header parsed, the rest of the file is being inflated -- by the threads, and by the device once its runtime is up (bam_device.hpp)
+            load = load_bam_begin(bam_path, threads, c, device_inflate_helpers(device));
+        } catch (const std::exception &e) {
+            std::cerr << e.what() << "\n";
+            return 1;
+        }
+        tr.lap("bam header");
+        start_side_work(load_bam_size_hint(load));
+        hip_up = std::thread([&] {
+            ctx_rc = palace_ctx_create(device, &ctx);
+            if (ctx_rc) ctx_err = palace_last_error();
         });
-    try {
-        load_bam_finish(load, seed);
-    } catch (const std::exception &e) {
-        std::cerr << e.what() << "\n";
-        join04(); if (side.joinable()) side.join(); side2.join(); hip_up.join();
-        return 1;
+        try {
+            load_bam_finish(load, seed);
+        } catch (const std::exception &e) {
+            std::cerr << e.what() << "\n";
+            join_side_work();
+            return 1;
+        }
+        tr.lap("bam records");
     }
-    tr.lap("bam records");
     if (debug) {
         // the per-read text of the reference's --debug (:454-458, :607-609, :711-853): a diagnostic the host writes from the decoded
         // records (debug_trace.hpp); the graph below is the device's as without the option
@@ -376,14 +483,28 @@ int main(int argc, char **argv)
     join04();                                                     // (it joined `side`)
     if (side.joinable()) side.join();
     side2.join();
-    if (s4o.enabled() && !s4obj) { std::cerr << "generateGraph: stage 04: " << s4err << "\n"; hip_up.join(); return 1; }
+    if (s4o.enabled() && !s4obj) { std::cerr << "generateGraph: stage 04: " << s4err << "\n"; if (hip_up.joinable()) hip_up.join(); return 1; }
     tr.lap("name ranks + fastg keys (joined)");
-    hip_up.join();
+    if (hip_up.joinable()) hip_up.join();
     if (ctx_rc) { std::cerr << "generateGraph: cannot set up the GPU: " << ctx_err << "\n"; join04(); return 1; }
     tr.lap("hip runtime up (joined)");
     if (auto_depth) {
         std::string text;
-        const int drc = first_depth(ctx, c, text);
+        int drc;
+        if (bam_gpu) {
+            // the match segments from the records where they lie, counted first; handed to the depth call as device pointers
+            int64_t n_segs = 0, again = 0;
+            void *seg[3] = {nullptr, nullptr, nullptr};
+            CK(palace_bam_match_segments(ctx, dstream.d_stream, dstream.total, dstream.d_starts, dstream.n_records, dstream.n_ref, nullptr, nullptr, nullptr,
+                                         0, &n_segs));
+            for (void *&sp : seg) CK(palace_malloc(ctx, std::max<size_t>(1, static_cast<size_t>(n_segs) * 4), &sp));
+            CK(palace_bam_match_segments(ctx, dstream.d_stream, dstream.total, dstream.d_starts, dstream.n_records, dstream.n_ref,
+                                         static_cast<int32_t *>(seg[0]), static_cast<int32_t *>(seg[1]), static_cast<int32_t *>(seg[2]), n_segs, &again));
+            drc = first_depth(ctx, n_segs, static_cast<int32_t *>(seg[0]), static_cast<int32_t *>(seg[1]), static_cast<int32_t *>(seg[2]), c.target_len, text);
+            for (void *sp : seg) palace_free(ctx, sp);
+        } else {
+            drc = first_depth(ctx, c, text);
+        }
         if (drc < 0) { std::cerr << "generateGraph: " << palace_last_error() << "\n"; return 1; }
         if (drc > 0) { std::cerr << "generateGraph: no position is covered, cannot derive avgDepth\n"; return 1; }
         avg_depth = std::atof(text.c_str());
@@ -391,22 +512,29 @@ int main(int argc, char **argv)
         tr.lap("depth stage");
     }
     palace_bam_cols cols{};
-    cols.n = c.n();
+    const int64_t n_records = bam_gpu ? dstream.n_records : c.n(), n_sa = bam_gpu ? dcols.n_sa : static_cast<int64_t>(c.sa.size());
+    cols.n = n_records;
     int32_t *d_tid, *d_pos, *d_mtid, *d_mpos, *d_nm, *d_rl, *d_ql, *d_cs, *d_ce, *d_sao, *d_tlen, *d_rank;
     uint16_t *d_flag; uint8_t *d_mapq; uint64_t *d_qkey, *d_fk, *d_consumed; palace_sa_item *d_sa;
-    CK(upload(ctx, c.tid, &d_tid)); CK(upload(ctx, c.pos, &d_pos)); CK(upload(ctx, c.mtid, &d_mtid));
-    CK(upload(ctx, c.mpos, &d_mpos)); CK(upload(ctx, c.nm, &d_nm)); CK(upload(ctx, c.ref_len, &d_rl));
-    CK(upload(ctx, c.read_len, &d_ql)); CK(upload(ctx, c.clip_s, &d_cs)); CK(upload(ctx, c.clip_e, &d_ce));
-    CK(upload(ctx, c.sa_off, &d_sao)); CK(upload(ctx, c.flag, &d_flag)); CK(upload(ctx, c.mapq, &d_mapq));
-    CK(upload(ctx, c.qkey, &d_qkey)); CK(upload(ctx, c.sa, &d_sa)); CK(upload(ctx, c.target_len, &d_tlen));
-    CK(upload(ctx, rank, &d_rank)); CK(upload(ctx, fkeys, &d_fk));
-    cols.tid = d_tid; cols.pos = d_pos; cols.mtid = d_mtid; cols.mpos = d_mpos; cols.nm = d_nm;
-    cols.ref_len = d_rl; cols.read_len = d_ql; cols.clip_s = d_cs; cols.clip_e = d_ce; cols.sa_off = d_sao;
-    cols.flag = d_flag; cols.mapq = d_mapq; cols.qkey = d_qkey;
+    if (bam_gpu) {                                                // the kernels wrote them: nothing to upload but the header's and the candidates' side
+        cols = dcols.cols;
+        d_qkey = dcols.d_qkey;
+        d_sa = dcols.d_sa;
+    } else {
+        CK(upload(ctx, c.tid, &d_tid)); CK(upload(ctx, c.pos, &d_pos)); CK(upload(ctx, c.mtid, &d_mtid));
+        CK(upload(ctx, c.mpos, &d_mpos)); CK(upload(ctx, c.nm, &d_nm)); CK(upload(ctx, c.ref_len, &d_rl));
+        CK(upload(ctx, c.read_len, &d_ql)); CK(upload(ctx, c.clip_s, &d_cs)); CK(upload(ctx, c.clip_e, &d_ce));
+        CK(upload(ctx, c.sa_off, &d_sao)); CK(upload(ctx, c.flag, &d_flag)); CK(upload(ctx, c.mapq, &d_mapq));
+        CK(upload(ctx, c.qkey, &d_qkey)); CK(upload(ctx, c.sa, &d_sa));
+        cols.tid = d_tid; cols.pos = d_pos; cols.mtid = d_mtid; cols.mpos = d_mpos; cols.nm = d_nm;
+        cols.ref_len = d_rl; cols.read_len = d_ql; cols.clip_s = d_cs; cols.clip_e = d_ce; cols.sa_off = d_sao;
+        cols.flag = d_flag; cols.mapq = d_mapq; cols.qkey = d_qkey;
+    }
+    CK(upload(ctx, c.target_len, &d_tlen)); CK(upload(ctx, rank, &d_rank)); CK(upload(ctx, fkeys, &d_fk));
     void *p = nullptr;
     CK(palace_malloc(ctx, std::max<size_t>(1, nt) * 8, &p));
     d_consumed = static_cast<uint64_t *>(p);
-    const int64_t cand_cap = c.n() + static_cast<int64_t>(c.sa.size()) + 1;      // worst case: every record, every item
+    const int64_t cand_cap = n_records + n_sa + 1;      // worst case: every record, every item
     CK(palace_malloc(ctx, static_cast<size_t>(cand_cap) * sizeof(palace_graph_cand), &p));
     palace_graph_cand *d_cands = static_cast<palace_graph_cand *>(p);
 
@@ -432,20 +560,36 @@ int main(int argc, char **argv)
         std::vector<uint64_t> g_key(cap_t);
         std::vector<int64_t> g_ord(cap_t, -1);                             // -1: empty slot
         bool collision = false;
+        std::vector<int64_t> pairs;                                        // --bam-gpu: (first ordinal, this ordinal) of equal keys; the names are compared where they lie
         for (const auto &k : cands) {
             if (k.kind != 1) continue;
             size_t at = static_cast<size_t>((k.qkey * 0x9E3779B97F4A7C15ull) >> 20) & (cap_t - 1);
             while (g_ord[at] >= 0 && g_key[at] != k.qkey) at = (at + 1) & (cap_t - 1);
             if (g_ord[at] < 0) { g_key[at] = k.qkey; g_ord[at] = k.ord; }
-            else if (g_ord[at] != k.ord && c.qname(g_ord[at]) != c.qname(k.ord)) { collision = true; break; }
+            else if (g_ord[at] == k.ord) continue;
+            else if (bam_gpu) { pairs.push_back(g_ord[at]); pairs.push_back(k.ord); }
+            else if (c.qname(g_ord[at]) != c.qname(k.ord)) { collision = true; break; }
+        }
+        if (bam_gpu && !pairs.empty()) {
+            int64_t *d_pairs = nullptr, n_differ = 0;
+            CK(upload(ctx, pairs, &d_pairs));
+            CK(palace_bam_names_differ(ctx, dstream.d_stream, dstream.total, dstream.d_starts, dstream.n_records, d_pairs,
+                                       static_cast<int64_t>(pairs.size() / 2), &n_differ));
+            palace_free(ctx, d_pairs);
+            collision = n_differ != 0;
         }
         if (!collision) break;
         if (attempt == 8) { std::cerr << "generateGraph: read-name key collisions persist\n"; return 1; }
-        rekey(c, ++seed);
-        CK(palace_h2d(ctx, d_qkey, c.qkey.data(), c.qkey.size() * 8));
+        ++seed;
+        if (bam_gpu) {
+            CK(palace_bam_name_keys(ctx, dstream.d_stream, dstream.total, dstream.d_starts, dstream.n_records, seed, d_qkey));
+        } else {
+            rekey(c, seed);
+            CK(palace_h2d(ctx, d_qkey, c.qkey.data(), c.qkey.size() * 8));
+        }
     }
+    dstream.release();                                             // (--bam-gpu: the stream and the starts have served)
     tr.lap("classify + name guard");
-    const int64_t n_records = c.n();
     CK(palace_malloc(ctx, static_cast<size_t>(std::max<int64_t>(1, n_cands)) * sizeof(palace_graph_edge), &p));
     palace_graph_edge *d_edges = static_cast<palace_graph_edge *>(p);
     int64_t n_edges = 0;
