@@ -1,6 +1,7 @@
 // The inflated BAM stream in HBM -> where its alignment records start (palace_bam_walk) and the match segments of the depth stage
 // (palace_bam_match_segments): what `bamdepth --bam-gpu` needs to take a BAM without its records crossing PCIe again
-// (include/palace_hip.h; the host's statement of both is host/bam.cpp: BamLoad::walk_step and decode_range).
+// (include/palace_hip.h).  What a record IS -- the step of the walk, its CIGAR, spans, segments, aux fields, SA items -- is
+// bam_record.hpp, the one text that the host loader (host/bam.cpp: BamLoad::walk, decode_range) compiles as well.
 //
 // The record walk is serial by format -- a record's size is its first word -- and its result is DEFINED as that serial walk from
 // the first record.  What runs in parallel is a guess that is checked, never trusted:
@@ -19,12 +20,13 @@
 // is walked by the chain alone: one wave, one dependent load per record).  Every read lies inside [0, total): a step reads the
 // four bytes of its size word only when they are there and a record's fields only when the whole record is.
 //
-// For `generateGraph --bam-gpu` the same record starts feed the decode itself (decode_range of host/bam.cpp, one thread per record: a
-// record's aux fields are a serial scan): palace_bam_columns writes the classify kernel's columns, palace_bam_sa_items parses the SA
-// tags' text into palace_sa_item -- counted, scanned, emitted, as the segments are -- with the contig names looked up in a hash table
+// For `generateGraph --bam-gpu` the same record starts feed the decode itself (what decode_range of host/bam.cpp does with the
+// same functions, here one thread per record: a record's aux fields are a serial scan): palace_bam_columns writes the classify
+// kernel's columns, palace_bam_sa_items parses the SA tags' text into palace_sa_item -- counted, scanned, emitted, as the segments are -- with the contig names looked up in a hash table
 // built on the device from the header's names (palace_bam_names_create), palace_bam_name_keys re-keys the read names and
 // palace_bam_names_differ compares them where they lie.  Every read lies inside the record the walk accepted.
 #include "common.hpp"
+#include "bam_record.hpp"
 
 namespace palace {
 namespace {
@@ -39,31 +41,10 @@ constexpr int32_t kEnded = 1, kUsed = 2;
 // [0] records, [1] stop offset, [2..5] chunks, guesses that held, chunks repaired, chunks without a start
 struct WalkHead { int64_t v[8]; };
 
-// unaligned-safe loads: the stream has no alignment anywhere
-__device__ __forceinline__ uint32_t ld16(const uint8_t *d, int64_t p) { return d[p] | (static_cast<uint32_t>(d[p + 1]) << 8); }
-__device__ __forceinline__ uint32_t ld32(const uint8_t *d, int64_t p)
-{
-    return d[p] | (static_cast<uint32_t>(d[p + 1]) << 8) | (static_cast<uint32_t>(d[p + 2]) << 16) | (static_cast<uint32_t>(d[p + 3]) << 24);
-}
-
-// BamLoad::walk_step (host/bam.cpp) on a stream that is there in full: true = a record at p, *next = the offset behind it
-__device__ __forceinline__ bool walk_step(const uint8_t *d, int64_t p, int64_t total, int64_t *next)
-{
-    if (p + 4 > total) return false;
-    const int64_t bs = ld32(d, p);
-    if (bs < 32) return false;
-    if (p + 4 + bs > total) return false;
-    const int64_t r = p + 4;
-    const int64_t l_name = d[r + 8], n_cig = ld16(d, r + 12), l_seq = ld32(d, r + 16);
-    if (l_name < 1 || l_seq > 0x7fffffffll || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs) return false;
-    *next = p + 4 + bs;
-    return true;
-}
-
 // the guess's test: a step of the walk, and the fields a real record keeps in range
 __device__ __forceinline__ bool looks_like_record(const uint8_t *d, int64_t p, int64_t total, int32_t n_ref, int64_t *next)
 {
-    if (!walk_step(d, p, total, next)) return false;
+    if (walk_step(d, p, total, total, next) != 1) return false;
     const int64_t r = p + 4;
     const int32_t tid = static_cast<int32_t>(ld32(d, r)), pos = static_cast<int32_t>(ld32(d, r + 4));
     const int32_t mtid = static_cast<int32_t>(ld32(d, r + 20)), mpos = static_cast<int32_t>(ld32(d, r + 24));
@@ -88,7 +69,7 @@ __device__ __forceinline__ void walk_chunk(const uint8_t *d, int64_t total, int6
     int32_t n = 0, flags = 0;
     while (p < chunk_end) {
         int64_t next;
-        if (!walk_step(d, p, total, &next)) { flags = kEnded; break; }
+        if (walk_step(d, p, total, total, &next) != 1) { flags = kEnded; break; }
         n++;
         p = next;
     }
@@ -159,78 +140,6 @@ __global__ __launch_bounds__(256) void bam_starts_kernel(const uint8_t *d, int64
 }
 
 // ---- match segments: decode_range's mseg_* (host/bam.cpp) --------------------------------------------------------------------
-
-// size of one aux value at v (type byte consumed); 0 = unknown type or malformed (aux_size of the host)
-__device__ __forceinline__ uint64_t aux_size(const uint8_t *d, uint32_t type, int64_t v, int64_t end)
-{
-    switch (type) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'Z': case 'H':
-        for (int64_t q = v; q < end; q++)
-            if (d[q] == 0) return static_cast<uint64_t>(q - v + 1);
-        return 0;
-    case 'B': {
-        if (end - v < 5) return 0;
-        uint64_t es;
-        switch (d[v]) {
-        case 'c': case 'C': es = 1; break;
-        case 's': case 'S': es = 2; break;
-        case 'i': case 'I': case 'f': es = 4; break;
-        default: return 0;
-        }
-        return 5 + es * static_cast<uint64_t>(ld32(d, v + 1));
-    }
-    default: return 0;
-    }
-}
-
-// The record's CIGAR as the loader sees it (decode_range, host/bam.cpp): its own ops, or the first CG:B,I tag's behind the
-// <l_seq>S<ref>N placeholder of a mapped record (SAM spec 4.2.2; htslib puts it back in place inside bam_read1).  ops = offset of
-// the first op word, aux = offset of the first aux field.  The only place these conditions live on the device.
-struct RecCigar { int64_t ops, n_ops, aux; };
-__device__ __forceinline__ RecCigar record_cigar(const uint8_t *d, int64_t s, int64_t end)
-{
-    const int32_t tid = static_cast<int32_t>(ld32(d, s)), pos = static_cast<int32_t>(ld32(d, s + 4));
-    const int64_t l_name = d[s + 8], n_cig = ld16(d, s + 12), l_seq = ld32(d, s + 16);
-    const int64_t cg = s + 32 + l_name;
-    RecCigar c{cg, n_cig, cg + 4 * n_cig + (l_seq + 1) / 2 + l_seq};
-    if (n_cig > 0 && tid >= 0 && pos >= 0 && (ld32(d, cg) & 15u) == 4 && static_cast<int64_t>(ld32(d, cg) >> 4) == l_seq) {
-        for (int64_t x = c.aux; x + 3 <= end;) {
-            const int64_t v = x + 3;
-            const uint32_t type = d[x + 2];
-            const uint64_t sz = aux_size(d, type, v, end);
-            if (!sz || sz > static_cast<uint64_t>(end - v)) break;
-            if (d[x] == 'C' && d[x + 1] == 'G') {                            // the first CG tag decides
-                if (type == 'B' && (d[v] == 'I' || d[v] == 'i') && ld32(d, v + 1) >= static_cast<uint32_t>(n_cig) && ld32(d, v + 1) < (1u << 29)) {
-                    c.ops = v + 5;
-                    c.n_ops = ld32(d, v + 1);
-                }
-                break;
-            }
-            x = v + static_cast<int64_t>(sz);
-        }
-    }
-    return c;
-}
-
-// f(tid, pos, len) for every match segment of the record whose refID lies at s, in operation order
-template <class F>
-__device__ __forceinline__ void record_segments(const uint8_t *d, int64_t s, int32_t n_ref, F f)
-{
-    const int64_t end = s + static_cast<int64_t>(ld32(d, s - 4));
-    const int32_t tid = static_cast<int32_t>(ld32(d, s)), pos = static_cast<int32_t>(ld32(d, s + 4));
-    const uint32_t flag = ld16(d, s + 14);
-    if ((flag & 0x704u) || tid < 0 || tid >= n_ref || pos < 0) return;       // what `samtools depth` does not count
-    const RecCigar c = record_cigar(d, s, end);
-    uint32_t rl = 0;
-    for (int64_t k = 0; k < c.n_ops; k++) {
-        const uint32_t w = ld32(d, c.ops + 4 * k), op = w & 15u, len = w >> 4;
-        if (len > 0 && (op == 0 || op == 7 || op == 8)) f(tid, static_cast<int32_t>(static_cast<uint32_t>(pos) + rl), static_cast<int32_t>(len));
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;
-    }
-}
 
 constexpr int kSegThreads = 256, kScanThreads = 1024;
 
@@ -305,72 +214,6 @@ __global__ __launch_bounds__(kSegThreads) void bam_seg_emit_kernel(const uint8_t
 
 // ---- columns and SA items: decode_range's per-record columns (host/bam.cpp) ------------------------------------------------------
 
-// OpScan of the host: zero-length ops are dropped; the leading S, the trailing S when more than one op remains, the query span
-struct OpScan {
-    int32_t n_ops = 0, first_len = 0, last_len = 0;
-    bool first_s = false, last_s = false;
-    uint32_t len = 0;
-    __device__ __forceinline__ void add(int32_t n, bool is_s, bool in_read)
-    {
-        if (n <= 0) return;
-        if (!n_ops) { first_s = is_s; first_len = n; }
-        last_s = is_s; last_len = n; n_ops++;
-        if (in_read) len += static_cast<uint32_t>(n);
-    }
-    __device__ __forceinline__ int32_t clip_s() const { return n_ops && first_s ? first_len : 0; }
-    __device__ __forceinline__ int32_t clip_e() const { return n_ops > 1 && last_s ? last_len : 0; }
-};
-
-// the C-string view of the read name: up to the first NUL inside l_read_name, else l_read_name - 1 bytes (l_read_name >= 1: the walk)
-__device__ __forceinline__ int64_t name_len(const uint8_t *d, int64_t s)
-{
-    const int64_t l_name = d[s + 8];
-    for (int64_t k = 0; k < l_name; k++)
-        if (d[s + 32 + k] == 0) return k;
-    return l_name - 1;
-}
-
-// name_key of the host
-__device__ __forceinline__ uint64_t name_key(const uint8_t *d, int64_t at, int64_t n, uint64_t seed)
-{
-    uint64_t h = 0xcbf29ce484222325ull ^ (seed * 0x9e3779b97f4a7c15ull);
-    for (int64_t i = 0; i < n; i++) { h ^= d[at + i]; h *= 0x100000001b3ull; }
-    h ^= h >> 32; h *= 0xd6e8feb86659fd93ull; h ^= h >> 32;
-    return h;
-}
-
-// the aux scan of decode_range: the first NM field decides nm (integer types with their signedness, any other type 0), the first SA
-// field of type Z is the SA text [sa, sa + sa_len); the scan stops at a field of unknown size or past the record, and once both are found
-struct RecAux { int32_t nm; int64_t sa, sa_len; };
-__device__ __forceinline__ RecAux record_aux(const uint8_t *d, int64_t x0, int64_t end)
-{
-    RecAux a{0, -1, 0};
-    bool have_nm = false, have_sa = false;
-    for (int64_t x = x0; x + 3 <= end && !(have_nm && have_sa);) {
-        const int64_t v = x + 3;
-        const uint32_t type = d[x + 2];
-        const uint64_t sz = aux_size(d, type, v, end);
-        if (!sz || sz > static_cast<uint64_t>(end - v)) break;
-        if (!have_nm && d[x] == 'N' && d[x + 1] == 'M') {
-            have_nm = true;
-            switch (type) {
-            case 'c': a.nm = static_cast<int8_t>(d[v]); break;
-            case 'C': a.nm = d[v]; break;
-            case 's': a.nm = static_cast<int16_t>(ld16(d, v)); break;
-            case 'S': a.nm = static_cast<int32_t>(ld16(d, v)); break;
-            case 'i': case 'I': a.nm = static_cast<int32_t>(ld32(d, v)); break;
-            default: a.nm = 0;
-            }
-        } else if (!have_sa && d[x] == 'S' && d[x + 1] == 'A' && type == 'Z') {
-            have_sa = true;
-            a.sa = v;
-            a.sa_len = static_cast<int64_t>(sz) - 1;
-        }
-        x = v + static_cast<int64_t>(sz);
-    }
-    return a;
-}
-
 struct ColsOut {
     int32_t *tid, *pos, *mtid, *mpos, *nm, *ref_len, *read_len, *clip_s, *clip_e;
     uint16_t *flag;
@@ -393,19 +236,11 @@ __global__ __launch_bounds__(kColThreads) void bam_columns_kernel(const uint8_t 
     o.mpos[i] = static_cast<int32_t>(ld32(d, s + 24));
     o.qkey[i] = name_key(d, s + 32, name_len(d, s), seed);
     const RecCigar c = record_cigar(d, s, end);
-    uint32_t rl = 0, ql = 0;
-    OpScan sc;
-    for (int64_t k = 0; k < c.n_ops; k++) {
-        const uint32_t w = ld32(d, c.ops + 4 * k), op = w & 15u, len = w >> 4;
-        const bool in_read = op == 0 || op == 1 || op == 4 || op == 7 || op == 8;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;
-        if (in_read) ql += len;
-        sc.add(static_cast<int32_t>(len), op == 4, in_read);
-    }
-    o.ref_len[i] = static_cast<int32_t>(rl);
-    o.read_len[i] = static_cast<int32_t>(ql);
-    o.clip_s[i] = c.n_ops ? sc.clip_s() : -1;
-    o.clip_e[i] = sc.clip_e();
+    const RecOps r = record_ops(d, s, c, false, [](int32_t, int32_t, int32_t) {});
+    o.ref_len[i] = static_cast<int32_t>(r.ref_len);
+    o.read_len[i] = static_cast<int32_t>(r.read_len);
+    o.clip_s[i] = c.n_ops ? r.sc.clip_s() : -1;
+    o.clip_e[i] = r.sc.clip_e();
     o.nm[i] = record_aux(d, c.aux, end).nm;
 }
 
@@ -494,83 +329,6 @@ __device__ __forceinline__ int32_t tid_of(const palace_bam_names &t, const uint8
     }
 }
 
-__device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || (c >= 9 && c <= 13); }      // isspace of the C locale
-__device__ __forceinline__ bool is_digit(uint8_t c) { return c >= '0' && c <= '9'; }
-
-// parseSAItem's cut of one item [b, e) (parse_sa of the host): six comma fields in getline's sense -- a field exists iff at least
-// one byte, possibly just its delimiter, is left -- trimmed at both ends; an empty name or position fails the item
-struct SaFields { int64_t b[6], e[6]; };
-__device__ __forceinline__ bool sa_fields(const uint8_t *d, int64_t b, int64_t e, SaFields *f)
-{
-    int64_t p = b;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        if (p >= e) return false;
-        int64_t q = p;
-        while (q < e && d[q] != ',') q++;
-        f->b[k] = p;
-        f->e[k] = q;
-        p = q < e ? q + 1 : e;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        while (f->b[k] < f->e[k] && is_space(d[f->b[k]])) f->b[k]++;
-        while (f->e[k] > f->b[k] && is_space(d[f->e[k] - 1])) f->e[k]--;
-    }
-    return f->b[0] != f->e[0] && f->b[1] != f->e[1];
-}
-
-// glibc's atoi on [b, e): (int) strtol -- optional sign, digits up to the first non-digit, 0 without digits; beyond the range of
-// long the value saturates, and the conversion to int keeps its low 32 bits.  (The fields are trimmed: no leading blanks are left.)
-__device__ __forceinline__ int32_t atoi_field(const uint8_t *d, int64_t b, int64_t e)
-{
-    bool neg = false, over = false;
-    if (b < e && (d[b] == '-' || d[b] == '+')) { neg = d[b] == '-'; b++; }
-    const uint64_t limit = neg ? 0x8000000000000000ull : 0x7fffffffffffffffull;
-    uint64_t v = 0;
-    for (; b < e && is_digit(d[b]); b++) {
-        const uint64_t digit = d[b] - '0';
-        if (v > (limit - digit) / 10) over = true;
-        else v = v * 10 + digit;
-    }
-    if (over) v = limit;
-    return static_cast<int32_t>(static_cast<uint32_t>(neg ? 0 - v : v));
-}
-
-// clip_from_text of the host on [b, e): any non-digit byte ends an op; empty text gives clip_s = -1
-__device__ __forceinline__ void clip_from_text(const uint8_t *d, int64_t b, int64_t e, palace_sa_item *out)
-{
-    if (b == e) { out->clip_s2 = -1; out->clip_e2 = 0; out->len2 = 0; return; }
-    OpScan sc;
-    uint32_t acc = 0;
-    for (; b < e; b++) {
-        const uint8_t ch = d[b];
-        if (is_digit(ch)) acc = acc * 10 + (ch - '0');
-        else { sc.add(static_cast<int32_t>(acc), ch == 'S', ch == 'M' || ch == 'I' || ch == 'S' || ch == '=' || ch == 'X'); acc = 0; }
-    }
-    out->clip_s2 = sc.clip_s(); out->clip_e2 = sc.clip_e(); out->len2 = static_cast<int32_t>(sc.len);
-}
-
-// f(fields) for every item of record i's SA list that parses, in list order: the first SA:Z field of a record with 0 <= tid < n_ref,
-// split at ';', empty items skipped
-template <class F>
-__device__ __forceinline__ void record_sa_items(const uint8_t *d, int64_t s, int32_t n_ref, F f)
-{
-    const int32_t tid = static_cast<int32_t>(ld32(d, s));
-    if (tid < 0 || tid >= n_ref) return;
-    const int64_t end = s + static_cast<int64_t>(ld32(d, s - 4));
-    const int64_t l_name = d[s + 8], n_cig = ld16(d, s + 12), l_seq = ld32(d, s + 16);
-    const RecAux a = record_aux(d, s + 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq, end);
-    if (a.sa < 0) return;
-    for (int64_t p = a.sa, se = a.sa + a.sa_len; p < se;) {
-        int64_t ie = p;
-        while (ie < se && d[ie] != ';') ie++;
-        SaFields fl;
-        if (ie > p && sa_fields(d, p, ie, &fl)) f(fl);
-        p = ie < se ? ie + 1 : se;
-    }
-}
-
 __device__ __forceinline__ long long sa_items_of(const uint8_t *d, const int64_t *starts, int64_t i, int64_t n, int32_t n_ref)
 {
     long long cnt = 0;
@@ -599,15 +357,8 @@ __global__ __launch_bounds__(kSegThreads) void bam_sa_emit_kernel(const uint8_t 
     const int64_t s = starts[i];
     const int32_t own = static_cast<int32_t>(ld32(d, s));
     record_sa_items(d, s, t.n_ref, [&](const SaFields &f) {
-        palace_sa_item it;
-        const uint8_t *name = d + f.b[0];
-        const int64_t name_n = f.e[0] - f.b[0];
-        it.tid2 = is_name(t, own, name, name_n) ? -1 : tid_of(t, name, name_n);
-        it.pos2 = atoi_field(d, f.b[1], f.e[1]);
-        it.rev2 = (f.e[2] - f.b[2] == 1 && d[f.b[2]] == '-') ? 1 : 0;
-        clip_from_text(d, f.b[3], f.e[3], &it);
-        it.mapq2 = atoi_field(d, f.b[4], f.e[4]);
-        it.nm2 = atoi_field(d, f.b[5], f.e[5]);
+        const palace_sa_item it = sa_item(d, f, [&](const uint8_t *name, int64_t n) { return is_name(t, own, name, n); },
+                                          [&](const uint8_t *name, int64_t n) { return tid_of(t, name, n); });
         if (at < cap) items[at] = it;
         at++;
     });

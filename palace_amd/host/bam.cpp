@@ -1,4 +1,5 @@
 #include "bam.hpp"
+#include "../csrc/bam_record.hpp"
 #include "trace.hpp"
 
 #include <fcntl.h>
@@ -11,7 +12,6 @@
 #include <mutex>
 #include <chrono>
 #include <memory>
-#include <cctype>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
@@ -23,7 +23,6 @@ namespace palace_host {
 namespace {
 
 uint32_t le32(const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
-uint16_t le16(const uint8_t *p) { uint16_t v; std::memcpy(&v, p, 2); return v; }
 
 // The compressed file, mapped read-only (no copy of it is made).
 struct MappedFile {
@@ -62,107 +61,11 @@ void parallel_for(size_t n, int threads, F f)
     for (auto &th : pool) th.join();
 }
 
-// One CIGAR as parseCigarReadInterval sees it (generate_graph.cpp:330-366): zero-length ops are
-// dropped; clip_s = leading S, clip_e = trailing S when more than one op remains; len = query span.
-struct ClipInfo { int32_t clip_s, clip_e, len; };
-
-struct OpScan {
-    int n_ops = 0; int first_len = 0, last_len = 0; char first = 0, last = 0; int32_t len = 0;
-    void add(int n, char c)
-    {
-        if (n <= 0) return;
-        if (!n_ops) { first = c; first_len = n; }
-        last = c; last_len = n; n_ops++;
-        if (c == 'M' || c == 'I' || c == 'S' || c == '=' || c == 'X') len += n;
-    }
-    ClipInfo done() const
-    {
-        ClipInfo r{0, 0, len};
-        if (n_ops && first == 'S') r.clip_s = first_len;
-        if (n_ops > 1 && last == 'S') r.clip_e = last_len;
-        return r;
-    }
-};
-
-ClipInfo clip_from_text(const char *s, size_t n)
-{
-    if (n == 0) return ClipInfo{-1, 0, 0};                 // empty text: interval stays [0,0] (:332)
-    OpScan sc;
-    int acc = 0;
-    for (size_t i = 0; i < n; i++) {
-        unsigned char ch = static_cast<unsigned char>(s[i]);
-        if (std::isdigit(ch)) acc = acc * 10 + (ch - '0');
-        else { sc.add(acc, static_cast<char>(ch)); acc = 0; }
-    }
-    return sc.done();
-}
-
-void trim_ws(const char *&b, const char *&e)
-{
-    while (b < e && std::isspace(static_cast<unsigned char>(*b))) ++b;
-    while (e > b && std::isspace(static_cast<unsigned char>(e[-1]))) --e;
-}
-
-// parseSAItem (generate_graph.cpp:185-206): six comma fields must be extractable in getline's
-// sense (a field exists iff at least one byte -- possibly just its delimiter -- is left).
-bool parse_sa(const char *b, const char *e, const BamColumns &cols, int32_t own_tid, palace_sa_item &out)
-{
-    const char *fb[6], *fe[6];
-    const char *p = b;
-    for (int k = 0; k < 6; k++) {
-        if (p >= e) return false;                          // nothing left: getline fails
-        const char *c = static_cast<const char *>(std::memchr(p, ',', static_cast<size_t>(e - p)));
-        fb[k] = p;
-        fe[k] = c ? c : e;
-        p = c ? c + 1 : e;
-    }
-    for (int k = 0; k < 6; k++) trim_ws(fb[k], fe[k]);
-    if (fb[0] == fe[0] || fb[1] == fe[1]) return false;
-    const std::string_view rname(fb[0], static_cast<size_t>(fe[0] - fb[0]));
-    out.pos2 = std::atoi(std::string(fb[1], fe[1]).c_str());
-    out.rev2 = (fe[2] - fb[2] == 1 && *fb[2] == '-') ? 1 : 0;
-    ClipInfo ci = clip_from_text(fb[3], static_cast<size_t>(fe[3] - fb[3]));
-    out.clip_s2 = ci.clip_s; out.clip_e2 = ci.clip_e; out.len2 = ci.len;
-    out.mapq2 = std::atoi(std::string(fb[4], fe[4]).c_str());
-    out.nm2 = std::atoi(std::string(fb[5], fe[5]).c_str());
-    out.tid2 = -1;
-    if (own_tid >= 0 && rname != cols.target_name[own_tid]) {       // r1 == r2 -> skip (:731)
-        out.tid2 = cols.tid_of(rname);                                 // unknown name -> -1 -> skip (:733-734)
-    }
-    return true;
-}
-
-// size of one aux value at p (type byte already consumed); 0 on malformed input
-size_t aux_size(uint8_t type, const uint8_t *p, const uint8_t *end)
-{
-    switch (type) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'Z': case 'H': { const void *z = std::memchr(p, 0, static_cast<size_t>(end - p)); return z ? static_cast<const uint8_t *>(z) - p + 1 : 0; }
-    case 'B': {                                            // subtype, int32 count, count elements
-        if (end - p < 5) return 0;
-        size_t es;
-        switch (p[0]) {
-        case 'c': case 'C': es = 1; break;
-        case 's': case 'S': es = 2; break;
-        case 'i': case 'I': case 'f': es = 4; break;
-        default: return 0;
-        }
-        return 5 + es * static_cast<size_t>(le32(p + 1));
-    }
-    default: return 0;
-    }
-}
-
 }  // namespace
 
 uint64_t name_key(const char *s, size_t n, uint64_t seed)
 {
-    uint64_t h = 0xcbf29ce484222325ull ^ (seed * 0x9e3779b97f4a7c15ull);
-    for (size_t i = 0; i < n; i++) { h ^= static_cast<unsigned char>(s[i]); h *= 0x100000001b3ull; }
-    h ^= h >> 32; h *= 0xd6e8feb86659fd93ull; h ^= h >> 32;
-    return h;
+    return palace::name_key(reinterpret_cast<const uint8_t *>(s), 0, static_cast<int64_t>(n), seed);
 }
 
 void RawBuf::release()
@@ -226,29 +129,11 @@ struct BamLoad : BackMembers {
             std::this_thread::sleep_for(std::chrono::microseconds(50));
         }
     }
-    // the record walk (serial: a record's size is its first word), on a thread of its own from the moment the header's end is known
+    // the record walk (serial: a record's size is its first word; one step of it is walk_step of bam_record.hpp), on a thread of its own
+    // from the moment the header's end is known
     std::thread walker;
     std::string walk_error;
     void walk();
-    // one step of THE walk at offset p, on the bytes [0, limit) of a stream of `total` bytes: 1 = a record (its start appended by
-    // the caller, *next = the offset behind it), 0 = the stream ends or is malformed here (the walk is over), -1 = not decidable
-    // on `limit` bytes yet.  The only place the record rules live.
-    static int walk_step(const uint8_t *d, size_t p, size_t limit, size_t total, size_t *next)
-    {
-        if (p + 4 > total) return 0;
-        if (p + 4 > limit) return -1;
-        const size_t bs = le32(d + p);
-        if (bs < 32) return 0;                                        // truncated tail: stop like a failed sam_read1
-        if (p + 4 + bs > total) return 0;
-        if (p + 4 + bs > limit) return -1;
-        // the variable-length fields must fit the record (htslib's bam_read1 fails on such a record, which ends the
-        // reference's `while (sam_read1(...) >= 0)` loop at generate_graph.cpp:644): name, CIGAR, packed bases, qualities
-        const uint8_t *r = d + p + 4;
-        const size_t l_name = r[8], n_cig = le16(r + 12), l_seq = le32(r + 16);
-        if (l_name < 1 || l_seq > 0x7fffffffu || 32 + l_name + 4 * n_cig + (l_seq + 1) / 2 + l_seq > bs) return 0;
-        *next = p + 4 + bs;
-        return 1;
-    }
     // the decode of the records into columns, pipelined behind the record walk (load_bam_finish): the walker publishes how many record
     // starts it has found, the loader's threads -- done with the inflate -- take chunks of records as they become known
     static constexpr size_t kChunk = 32768;
@@ -437,18 +322,18 @@ void BamLoad::walk()
     try {
         size_t p = first_record, have = wait_for(std::min(total, p + 4), cursor), ahead = p & ~size_t{63};
         for (;;) {
-            size_t next = 0;
-            int st = walk_step(d, p, have, total, &next);
+            int64_t next = 0;
+            int st = palace::walk_step(d, static_cast<int64_t>(p), static_cast<int64_t>(have), static_cast<int64_t>(total), &next);
             if (st < 0) {                                             // behind the inflate front: wait for the bytes the step needs
                 have = wait_for(std::min(total, p + 4), cursor);
                 if (p + 4 <= have) have = wait_for(std::min(total, p + 4 + static_cast<size_t>(le32(d + p))), cursor);
-                st = walk_step(d, p, have, total, &next);
+                st = palace::walk_step(d, static_cast<int64_t>(p), static_cast<int64_t>(have), static_cast<int64_t>(total), &next);
                 if (st < 0) break;                                    // (everything that will ever come is there, and it is not enough)
             }
             if (st == 0) break;
             rec_at.push_back(p + 4);
             if ((rec_at.size() & 4095) == 0) n_walked.store(rec_at.size(), std::memory_order_release);
-            p = next;
+            p = static_cast<size_t>(next);
             // the next few record heads lie in the kilobyte behind this one, not at a fixed stride (the hardware does not see a
             // stream): every line of that kilobyte is asked for as the walk exposes it
             for (const size_t upto = std::min(have, p + 1024); ahead + 64 <= upto; ahead += 64) __builtin_prefetch(d + ahead);
@@ -459,112 +344,51 @@ void BamLoad::walk()
     walk_done.store(true, std::memory_order_release);
 }
 
-// records [a, b) of the walk into the columns (every element written exactly once, by the thread that has the chunk)
+// records [a, b) of the walk into the columns (every element written exactly once, by the thread that has the chunk): one pass per
+// record, every rule a call into bam_record.hpp -- the text the kernels of csrc/bam.hip are compiled from
 void BamLoad::decode_range(size_t a, size_t b, size_t part)
 {
+    using namespace palace;
     BamColumns &c = *this->c;
     const uint8_t *d = c.raw.data();
     const int32_t n_ref = this->n_ref;
     const uint64_t key_seed = this->key_seed;
-    static const char opchr[] = "MIDNSHP=XB??????";
-        for (size_t i = a; i < b; i++) {
-            const uint8_t *r = d + rec_at[i];
-            const uint8_t *end = r + le32(r - 4);
-            const int32_t tid = static_cast<int32_t>(le32(r));
-            c.tid[i] = tid;
-            c.nm[i] = 0;
-            sa_cnt[i] = 0;
-            c.pos[i] = static_cast<int32_t>(le32(r + 4));
-            const size_t l_name = r[8];
-            c.mapq[i] = r[9];
-            const size_t n_cig = le16(r + 12);
-            c.flag[i] = le16(r + 14);
-            const size_t l_seq = le32(r + 16);
-            c.mtid[i] = static_cast<int32_t>(le32(r + 20));
-            c.mpos[i] = static_cast<int32_t>(le32(r + 24));
-            const uint8_t *name = r + 32;
-            size_t nlen = l_name ? l_name - 1 : 0;
-            if (const void *z = std::memchr(name, 0, l_name)) nlen = static_cast<const uint8_t *>(z) - name;   // C-string view (:651)
-            c.qname_at[i] = static_cast<uint64_t>(name - d);
-            c.qname_len[i] = static_cast<uint8_t>(nlen);
-            c.qkey[i] = name_key(reinterpret_cast<const char *>(name), nlen, key_seed);
-            const uint8_t *cg = name + l_name;
-            const uint8_t *x0 = cg + 4 * n_cig + (l_seq + 1) / 2 + l_seq;      // first aux field
-            // A CIGAR of more than 65535 ops is stored in a CG:B,I tag behind a placeholder (SAM spec 4.2.2); htslib
-            // puts it back in place inside bam_read1 (bam_tag2cigar), so that is what the reference sees.
-            const uint8_t *ops = cg;
-            size_t n_ops = n_cig;
-            if (n_cig > 0 && tid >= 0 && static_cast<int32_t>(le32(r + 4)) >= 0 && (le32(cg) & 15) == 4 && (le32(cg) >> 4) == l_seq) {
-                for (const uint8_t *x = x0; x + 3 <= end;) {
-                    const uint8_t *v = x + 3;
-                    const size_t sz = aux_size(x[2], v, end);
-                    if (!sz || sz > static_cast<size_t>(end - v)) break;
-                    if (x[0] == 'C' && x[1] == 'G') {              // first CG tag decides (bam_aux_get)
-                        if (x[2] == 'B' && (v[0] == 'I' || v[0] == 'i') && le32(v + 1) >= n_cig && le32(v + 1) < (1u << 29)) {
-                            ops = v + 5;
-                            n_ops = le32(v + 1);
-                        }
-                        break;
-                    }
-                    x = v + sz;
-                }
-            }
-            int32_t rl = 0, ql = 0;
-            OpScan sc;
-            const bool depth_counts = c.want_match_segments && !(le16(r + 14) & 0x704) && tid >= 0 && tid < n_ref && static_cast<int32_t>(le32(r + 4)) >= 0;
-            for (size_t k = 0; k < n_ops; k++) {
-                uint32_t v = le32(ops + 4 * k);
-                int op = v & 15, len = static_cast<int>(v >> 4);
-                if (depth_counts && len > 0 && (op == 0 || op == 7 || op == 8)) {        // a match segment at pos + (ref consumed so far)
-                    auto &m = ms_part[part];
-                    m.push_back(tid); m.push_back(static_cast<int32_t>(le32(r + 4)) + rl); m.push_back(len);
-                }
-                if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) rl += len;   // bam_cigar2rlen
-                if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) ql += len;   // getReadLength (:385-397)
-                sc.add(len, opchr[op]);
-            }
-            ClipInfo ci = sc.done();
-            c.ref_len[i] = rl;
-            c.read_len[i] = ql;
-            c.clip_s[i] = n_ops ? ci.clip_s : -1;
-            c.clip_e[i] = ci.clip_e;
-            // aux: first NM (integer types only, like bam_aux2i) and first SA (Z)
-            const uint8_t *x = x0;
-            bool have_nm = false, have_sa = false;
-            while (x + 3 <= end && !(have_nm && have_sa)) {
-                uint8_t ty = x[2];
-                const uint8_t *v = x + 3;
-                size_t sz = aux_size(ty, v, end);
-                if (!sz || sz > static_cast<size_t>(end - v)) break;
-                if (!have_nm && x[0] == 'N' && x[1] == 'M') {
-                    have_nm = true;
-                    int64_t val = 0;
-                    switch (ty) {
-                    case 'c': val = static_cast<int8_t>(v[0]); break;
-                    case 'C': val = v[0]; break;
-                    case 's': val = static_cast<int16_t>(le16(v)); break;
-                    case 'S': val = le16(v); break;
-                    case 'i': val = static_cast<int32_t>(le32(v)); break;
-                    case 'I': val = le32(v); break;
-                    default: val = 0;
-                    }
-                    c.nm[i] = static_cast<int32_t>(val);
-                } else if (!have_sa && x[0] == 'S' && x[1] == 'A' && ty == 'Z') {
-                    have_sa = true;
-                    if (tid >= 0 && tid < n_ref) {                         // :687
-                        const char *s = reinterpret_cast<const char *>(v), *se = s + sz - 1;
-                        while (s < se) {                                   // items split at ';' (:719-720)
-                            const char *semi = static_cast<const char *>(std::memchr(s, ';', static_cast<size_t>(se - s)));
-                            const char *ie = semi ? semi : se;
-                            palace_sa_item it{};
-                            if (ie > s && parse_sa(s, ie, c, tid, it)) { sa_part[part].push_back(it); sa_cnt[i]++; }
-                            s = semi ? semi + 1 : se;
-                        }
-                    }
-                }
-                x = v + sz;
-            }
+    std::vector<int32_t> &ms = ms_part[part];
+    std::vector<palace_sa_item> &sa = sa_part[part];
+    auto view = [](const uint8_t *p, int64_t n) { return std::string_view(reinterpret_cast<const char *>(p), static_cast<size_t>(n)); };
+    for (size_t i = a; i < b; i++) {
+        const int64_t s = static_cast<int64_t>(rec_at[i]), end = s + static_cast<int64_t>(ld32(d, s - 4));
+        const int32_t tid = static_cast<int32_t>(ld32(d, s));
+        c.tid[i] = tid;
+        c.pos[i] = static_cast<int32_t>(ld32(d, s + 4));
+        c.mapq[i] = d[s + 9];
+        c.flag[i] = static_cast<uint16_t>(ld16(d, s + 14));
+        c.mtid[i] = static_cast<int32_t>(ld32(d, s + 20));
+        c.mpos[i] = static_cast<int32_t>(ld32(d, s + 24));
+        const int64_t nlen = name_len(d, s);
+        c.qname_at[i] = static_cast<uint64_t>(s + 32);
+        c.qname_len[i] = static_cast<uint8_t>(nlen);
+        c.qkey[i] = palace::name_key(d, s + 32, nlen, key_seed);
+        const RecCigar cg = record_cigar(d, s, end);
+        const RecOps r = record_ops(d, s, cg, c.want_match_segments && depth_counts(d, s, n_ref),
+                                    [&](int32_t t, int32_t pos, int32_t len) { ms.push_back(t); ms.push_back(pos); ms.push_back(len); });
+        c.ref_len[i] = static_cast<int32_t>(r.ref_len);
+        c.read_len[i] = static_cast<int32_t>(r.read_len);
+        c.clip_s[i] = cg.n_ops ? r.sc.clip_s() : -1;
+        c.clip_e[i] = r.sc.clip_e();
+        const RecAux x = record_aux(d, cg.aux, end);               // one scan: the first NM and the first SA:Z
+        c.nm[i] = x.nm;
+        int32_t n_sa = 0;
+        if (x.sa >= 0 && tid >= 0 && tid < n_ref) {                // :687
+            const std::string &own = c.target_name[static_cast<size_t>(tid)];
+            sa_text_items(d, x.sa, x.sa + x.sa_len, [&](const SaFields &f) {
+                sa.push_back(sa_item(d, f, [&](const uint8_t *p, int64_t n) { return view(p, n) == own; },
+                                     [&](const uint8_t *p, int64_t n) { return c.tid_of(view(p, n)); }));
+                n_sa++;
+            });
         }
+        sa_cnt[i] = n_sa;
+    }
 }
 
 void BamLoad::decode_chunks()

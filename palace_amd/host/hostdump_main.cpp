@@ -1,6 +1,7 @@
 // hostdump -- prints what the host-side parsers hand to the GPU, as text (no GPU needed).
 // Test tool for the CPU test suite:
-//   hostdump bam   <file.bam>          header + one line per record (decoded columns + parsed SA items)
+//   hostdump bam   <file.bam> [threads [mseg]]   header + one line per record (decoded columns + parsed SA items); with `mseg`,
+//                                      behind them one line "MS tid pos len" per match segment of the depth stage
 //   hostdump bamtime <file.bam> <threads>   load only, prints the record count (PALACE_TRACE=1: laps of the loader)
 //   hostdump fastq <file.fq> <threads> [part_bytes]  one line per sequence line
 //   hostdump fastqpack <file.fq> <threads> <part_bytes> [keep_every]   the packed form of the sequence lines (pack_fastq_part):
@@ -65,6 +66,8 @@ int main(int argc, char **argv)
                 }
                 std::printf("\n");
             }
+            if (argc > 4 && std::strcmp(argv[4], "mseg") == 0)
+                for (size_t k = 0; k < c.mseg_tid.size(); k++) std::printf("MS\t%d\t%d\t%d\n", c.mseg_tid[k], c.mseg_pos[k], c.mseg_len[k]);
         } else if (mode == "bamtime") {
             BamColumns c;
             load_bam(argv[2], argc > 3 ? std::atoi(argv[3]) : 4, 1, c);
