@@ -453,6 +453,47 @@ int palace_fastq_parse(palace_ctx *ctx, const uint8_t *d_text, int64_t n, int fi
                        uint8_t *d_bases, int64_t bases_cap, int64_t *d_offsets, int64_t offsets_cap, void *d_scratch,
                        size_t scratch_bytes);
 
+/* ---- `samtools depth` text read back: totals and per-contig runs (bamdepth --from-depth) ---------------------------------- */
+
+#define PALACE_DEPTH_TAIL_BYTES 4096       /* a line has at most this many bytes, its LF counted (csrc/depth_line.hpp) */
+
+/* Where a depth parse stands between two windows of one file (device memory; a file starts at all zeros).  The first 64 bytes are
+ * what a caller reads back per window.  lines / sum: the lines so far and the sum of their depths; bad_line: the 1-based number of
+ * the file's first line that is not `name<TAB>position<TAB>depth` (0: none so far; sums and runs mean nothing once it is set);
+ * win_runs / win_name_bytes: what the last window wrote to d_runs / d_names -- or, when error is set, what it would have written;
+ * tail_len, tail_buf, tail: the unterminated end of the text so far, tail[tail_buf][0 .. tail_len); error: the window did not fit
+ * runs_cap / names_cap: it and every later window write nothing and leave the cursor as it was but for error, win_runs and
+ * win_name_bytes (a caller may clear error and hand the same window over again with more room). */
+typedef struct {
+    int64_t lines;
+    uint64_t sum;
+    int64_t bad_line;
+    int64_t win_runs, win_name_bytes;
+    int32_t tail_len, tail_buf;
+    int32_t error, reserved0;
+    int64_t reserved1;
+    uint8_t tail[2][PALACE_DEPTH_TAIL_BYTES];
+} palace_depth_cursor;
+
+/* A run: a maximal stretch of consecutive lines of one window with byte-equal names.  A window's first line always begins one. */
+typedef struct {
+    uint64_t sum, lines;           /* of the run's lines: their depths, their number */
+    uint32_t name_off, name_len;   /* the name: d_names[name_off .. name_off + name_len) */
+} palace_depth_run;
+
+/* The text `contig<TAB>position<TAB>depth<LF>` in device memory reduced to totals and runs; the line's grammar is
+ * csrc/depth_line.hpp's (strict: 1-10 digits, values up to 2^31 - 1, no CR, no sign, exactly three columns, at most 4096 bytes).
+ * d_text[0 .. n) (16-byte aligned, n <= 2^30) is the next window of the file: any cut will do, a line may span any number of
+ * windows.  final_window != 0: the file ends with this window, and a last line without LF is a line (the empty text behind a final
+ * LF is not).  Moves *d_cursor past the window and writes the window's runs in text order to d_runs[0 .. cursor.win_runs) and their
+ * names to d_names[0 .. cursor.win_name_bytes); a line counts in the window in which it ends.  Sums are integers: the result does
+ * not depend on scheduling.  d_scratch: palace_depth_parse_scratch_bytes(n) bytes of device memory, not shared with calls in
+ * flight.  Three launches (count, scan, emit) whatever the window holds.  Enqueues only. */
+size_t palace_depth_parse_scratch_bytes(int64_t max_window);
+int palace_depth_parse(palace_ctx *ctx, const uint8_t *d_text, int64_t n, int final_window, palace_depth_cursor *d_cursor,
+                       palace_depth_run *d_runs, int64_t runs_cap, uint8_t *d_names, int64_t names_cap, void *d_scratch,
+                       size_t scratch_bytes);
+
 /* ---- gzip that is not BGZF: one DEFLATE stream inflated by many wavefronts ------------------------------------------------ */
 
 /* stride: compressed bytes between the places where a block start is searched for (one chunk per place at most); span: compressed

@@ -74,6 +74,11 @@ CAND_DTYPE = np.dtype([("ord", np.int64), ("qkey", np.uint64), ("left", np.int32
 EDGE_DTYPE = np.dtype([("left", np.int32), ("right", np.int32), ("counts", np.uint32, 4), ("oL", np.uint8),
                        ("oR", np.uint8), ("pad", np.uint8, 6)])
 FASTQ_CURSOR_DTYPE = np.dtype([("line", np.int64), ("reads", np.int64), ("bases", np.int64), ("open", np.int32), ("error", np.int32)])
+DEPTH_CURSOR_DTYPE = np.dtype([("lines", np.int64), ("sum", np.uint64), ("bad_line", np.int64), ("win_runs", np.int64), ("win_name_bytes", np.int64),
+                               ("tail_len", np.int32), ("tail_buf", np.int32), ("error", np.int32), ("reserved0", np.int32), ("reserved1", np.int64),
+                               ("tail", np.uint8, (2, 4096))])
+DEPTH_RUN_DTYPE = np.dtype([("sum", np.uint64), ("lines", np.uint64), ("name_off", np.uint32), ("name_len", np.uint32)])
+assert DEPTH_CURSOR_DTYPE.itemsize == 64 + 8192 and DEPTH_RUN_DTYPE.itemsize == 24
 assert CAND_DTYPE.itemsize == 64 and EDGE_DTYPE.itemsize == 32 and SA_ITEM_DTYPE.itemsize == 32
 
 _SIGS = {
@@ -170,6 +175,9 @@ _SIGS = {
     "palace_gzip_inflate": [C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(GzipParams), GZIP_SINK, C.c_void_p, C.POINTER(GzipStats)],
     "palace_fastq_parse": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
                            C.c_void_p, C.c_size_t],
+    "palace_depth_parse_scratch_bytes": [C.c_int64],    # (returns size_t: restype set below)
+    "palace_depth_parse": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                           C.c_void_p, C.c_size_t],
     "palace_graph_score_border": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.POINTER(GraphParams)],
     "palace_graph_resolve_ex": [C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.POINTER(GraphParams), C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)],
@@ -231,6 +239,7 @@ def lib() -> C.CDLL:
             fn.restype = C.c_int
         _LIB.palace_fastq_scratch_bytes.restype = C.c_size_t
         _LIB.palace_bam_walk_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_depth_parse_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -480,6 +489,47 @@ class Ctx:
                     d_offsets: DevBuf, offsets_cap: int, d_scratch: DevBuf):
         _check(lib().palace_fastq_parse(self.h, d_text_ptr, n, int(final_window), d_cursor.ptr, d_bases.ptr, bases_cap, d_offsets.ptr,
                                         offsets_cap, d_scratch.ptr, d_scratch.nbytes), "palace_fastq_parse")
+
+
+def depth_parse_windows(ctx: Ctx, text: bytes, cuts=(), runs_cap: int | None = None, names_cap: int | None = None, guard: int = 64):
+    """`samtools depth` text through palace_depth_parse, handed over in windows cut at the ascending positions `cuts` (equal
+    positions give empty windows).  Returns (the cursor after the last window, per window the list of its runs as
+    (name bytes, depth sum, lines) -- None for a window refused for its capacities --, whether the `guard` bytes behind d_runs and
+    d_names are as they were, whether ALL of d_runs and d_names is as it was).  runs_cap / names_cap: the capacities handed to every
+    call (default: what any window of the text could need)."""
+    text = bytes(text)
+    bounds = [0] + [min(max(int(c), 0), len(text)) for c in cuts] + [len(text)]
+    widest = max(b - a for a, b in zip(bounds, bounds[1:]))
+    runs_cap = len(text) // 2 + 2 if runs_cap is None else runs_cap
+    names_cap = len(text) + 1 if names_cap is None else names_cap
+    d_win = DevBuf(ctx, max(16, widest + 16))
+    fill = np.full(runs_cap * 24 + guard, 0xA5, np.uint8), np.full(names_cap + guard, 0xA5, np.uint8)
+    d_runs, d_names = ctx.upload(fill[0]), ctx.upload(fill[1])
+    d_scratch = DevBuf(ctx, int(lib().palace_depth_parse_scratch_bytes(widest)))
+    d_cur = ctx.upload(np.zeros(1, DEPTH_CURSOR_DTYPE))
+    windows = []
+    try:
+        for k, (a, b) in enumerate(zip(bounds, bounds[1:])):
+            chunk = np.frombuffer(text[a:b], dtype=np.uint8)
+            if len(chunk):
+                _check(lib().palace_h2d(ctx.h, d_win.ptr, chunk.ctypes.data, len(chunk)), "palace_h2d")
+            _check(lib().palace_depth_parse(ctx.h, d_win.ptr, len(chunk), int(k == len(bounds) - 2), d_cur.ptr, d_runs.ptr, runs_cap, d_names.ptr,
+                                            names_cap, d_scratch.ptr, d_scratch.nbytes), "palace_depth_parse")
+            ctx.sync()
+            cur = d_cur.to_host().view(DEPTH_CURSOR_DTYPE)[0]
+            if cur["error"]:
+                windows.append(None)
+                continue
+            raw_runs, names = d_runs.to_host(), d_names.to_host().tobytes()
+            runs = raw_runs[:int(cur["win_runs"]) * 24].view(DEPTH_RUN_DTYPE)
+            windows.append([(names[int(r["name_off"]):int(r["name_off"]) + int(r["name_len"])], int(r["sum"]), int(r["lines"])) for r in runs])
+        cur = d_cur.to_host().view(DEPTH_CURSOR_DTYPE)[0].copy()
+        intact = bool((d_runs.to_host()[runs_cap * 24:] == 0xA5).all() and (d_names.to_host()[names_cap:] == 0xA5).all())
+        untouched = bool((d_runs.to_host() == 0xA5).all() and (d_names.to_host() == 0xA5).all())
+        return cur, windows, intact, untouched
+    finally:
+        for buf in (d_win, d_runs, d_names, d_scratch, d_cur):
+            buf.free()
 
 
 def fastq_scratch_bytes(max_window: int) -> int:

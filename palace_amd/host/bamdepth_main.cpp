@@ -19,6 +19,11 @@
 // the stage is file -> device -> file.  `--bam-gpu` comes first; `--bam-gpu --depth-gz` is a usage error (that mode is host only).
 // Opt-in; the whole inflated BAM must fit the device; without a device it fails like `bamdepth <bam>`, it never falls back to
 // the host loader.  PALACE_TRACE prints the loader's laps and the walk's statistics.
+//     first_depth=$(bamdepth --from-depth <bam>.depth.gz)        bamdepth --from-depth --per-contig <bam>.depth.gz > contig_depth.tsv
+// print the same two things from the depth file itself (depth_read.hpp): plain text or BGZF, told apart by the first bytes; BGZF
+// members are inflated and CRC-checked on the device, the text is parsed there (palace_depth_parse) and never comes to the host.
+// `--from-depth` comes first and goes with no other mode.  Opt-in; without a device it fails, there is no host parser behind it.
+// PALACE_TRACE prints the laps.
 // (`generateGraph <bam> <fai> <out> auto` uses the same number without a second pass over the BAM.)
 #include <algorithm>
 #include <iostream>
@@ -28,6 +33,7 @@
 #include "bam_stream_device.hpp"
 #include "device_pick.hpp"
 #include "depth_host.hpp"
+#include "depth_read.hpp"
 #include "depthgz.hpp"
 #include "depthgz_device.hpp"
 
@@ -81,9 +87,48 @@ static int main_bam_gpu(bool per_contig, bool depth_gz_gpu, const char *gz_path,
     return code;
 }
 
+// `bamdepth --from-depth [--per-contig] <depth file>`
+static int main_from_depth(bool per_contig, const char *file)
+{
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
+    int code = 0;
+    try {
+        const bool trace = std::getenv("PALACE_TRACE") != nullptr;
+        DepthReadTimes tm;
+        const DepthReadResult r = read_depth_file(ctx, file, trace ? &tm : nullptr);
+        if (trace)
+            std::fprintf(stderr, "[bamdepth] from-depth ms: index %.1f upload %.1f inflate %.1f crc %.1f parse %.1f merge %.1f; text %llu B, lines %llu, "
+                         "runs %llu, members inflated on the host %llu\n", tm.index, tm.upload, tm.inflate, tm.crc, tm.parse, tm.merge,
+                         static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.lines), static_cast<unsigned long long>(r.runs),
+                         static_cast<unsigned long long>(r.host_inflated));
+        if (per_contig) {
+            std::string out;
+            for (size_t t = 0; t < r.name.size(); t++) out += r.name[t] + "\t" + std::to_string(r.contig_sum[t]) + "\t" + std::to_string(r.contig_lines[t]) + "\n";
+            std::cout << out;
+        } else if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
+        else std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
+    } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; code = 1; }
+    palace_ctx_destroy(ctx);
+    return code;
+}
+
+static int usage(const char *prog)
+{
+    std::cerr << "Usage: " << prog << " [--bam-gpu] [--per-contig | --depth-gz <out.depth.gz> | --depth-gz-gpu <out.depth.gz>] <bam>"
+              << "   (--bam-gpu: the BAM is read on the device; not with --depth-gz, the host-only mode)"
+              << "  |  " << prog << " --from-depth [--per-contig] <depth file>   (the depth file, plain or BGZF, read back on the device)\n";
+    return 1;
+}
+
 int main(int argc, char **argv)
 {
     const char *prog = argv[0];
+    if (argc >= 2 && std::string(argv[1]) == "--from-depth") {       // its own command line: [--per-contig] <depth file>, nothing else
+        const bool pc = argc >= 3 && std::string(argv[2]) == "--per-contig";
+        if (argc != (pc ? 4 : 3) || std::string(argv[argc - 1]).rfind("--", 0) == 0) return usage(prog);
+        return main_from_depth(pc, argv[argc - 1]);
+    }
     const bool bam_gpu = argc >= 2 && std::string(argv[1]) == "--bam-gpu";
     if (bam_gpu) { argc--; argv++; }                 // the rest is parsed as without it
     const bool per_contig = argc >= 3 && std::string(argv[1]) == "--per-contig";
@@ -91,9 +136,7 @@ int main(int argc, char **argv)
     const bool depth_gz_gpu = argc >= 4 && std::string(argv[1]) == "--depth-gz-gpu";
     const bool depth_gz = argc >= 4 && gz_mode;
     if (argc < 2 || (per_contig && argc < 3) || (gz_mode && argc < 4) || (bam_gpu && depth_gz && !depth_gz_gpu)) {
-        std::cerr << "Usage: " << prog << " [--bam-gpu] [--per-contig | --depth-gz <out.depth.gz> | --depth-gz-gpu <out.depth.gz>] <bam>"
-                  << "   (--bam-gpu: the BAM is read on the device; not with --depth-gz, the host-only mode)\n";
-        return 1;
+        return usage(prog);
     }
     const char *bam = depth_gz ? argv[3] : per_contig ? argv[2] : argv[1];
     const int threads = static_cast<int>(std::max(1u, std::min(16u, std::thread::hardware_concurrency())));

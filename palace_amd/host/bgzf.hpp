@@ -18,8 +18,10 @@ struct BgzfMember { uint64_t in_off, in_len, out_off, out_len; };
 
 // The members of a mapped file.  Every field that comes from the file is checked against the file before it is used: a member is
 // 12 + XLEN header bytes, the deflate stream and an 8-byte trailer, BSIZE + 1 bytes in all.  Fewer than 18 bytes behind the last
-// member are ignored (like a missing EOF member).  Throws std::runtime_error.
-inline std::vector<BgzfMember> bgzf_members(const uint8_t *file, size_t file_size, size_t *total_out)
+// member are ignored (like a missing EOF member).  Throws std::runtime_error.  walk_end (optional): the offset the walk stopped at
+// -- of the member it threw on, or behind the last member -- and whether it threw because that member is no BGZF member at all.
+struct BgzfWalkEnd { size_t offset = 0; bool not_bgzf = false; };
+inline std::vector<BgzfMember> bgzf_members(const uint8_t *file, size_t file_size, size_t *total_out, BgzfWalkEnd *walk_end = nullptr)
 {
     auto le16 = [](const uint8_t *p) { uint16_t v; std::memcpy(&v, p, 2); return v; };
     auto le32 = [](const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; };
@@ -27,6 +29,7 @@ inline std::vector<BgzfMember> bgzf_members(const uint8_t *file, size_t file_siz
     size_t p = 0, total = 0;
     while (p + 18 <= file_size) {
         const uint8_t *h = file + p;
+        if (walk_end) { walk_end->offset = p; walk_end->not_bgzf = true; }
         if (h[0] != 31 || h[1] != 139 || h[2] != 8 || !(h[3] & 4)) throw std::runtime_error("Failed to read BAM header");
         const size_t xlen = le16(h + 10), left = file_size - p;
         if (12 + xlen + 8 > left) throw std::runtime_error("truncated BGZF block");
@@ -37,6 +40,7 @@ inline std::vector<BgzfMember> bgzf_members(const uint8_t *file, size_t file_siz
             if (h[q] == 'B' && h[q + 1] == 'C' && slen == 2) bsize = static_cast<size_t>(le16(h + q + 4)) + 1;
             q += 4 + slen;
         }
+        if (walk_end) walk_end->not_bgzf = bsize == 0;                       // no BC subfield
         if (bsize < 12 + xlen + 8 || bsize > left) throw std::runtime_error("truncated BGZF block");
         const size_t isize = le32(h + bsize - 4);
         if (isize > 65536) throw std::runtime_error("malformed BGZF block (ISIZE > 64 KiB)");
@@ -44,6 +48,7 @@ inline std::vector<BgzfMember> bgzf_members(const uint8_t *file, size_t file_siz
         total += isize;
         p += bsize;
     }
+    if (walk_end) { walk_end->offset = p; walk_end->not_bgzf = false; }
     *total_out = total;
     return members;
 }

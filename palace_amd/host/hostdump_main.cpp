@@ -12,6 +12,8 @@
 //   hostdump fasta <file.fa> [threads] one line per record (ordinal, name, length, sequence); with threads: parse_fasta_mt
 //   hostdump bamtrace <bam> <fai> [..] what `generateGraph --debug` writes to stderr for the file's records (debug_trace.hpp), on stdout
 //   hostdump devicepick x              "<ordinal handed to palace_ctx_create> <ROCR_VISIBLE_DEVICES afterwards>" (device_pick.hpp)
+//   hostdump depthline <file>          the grammar of a `samtools depth` line (csrc/depth_line.hpp, the text the kernels of
+//                                      depth_parse.hip compile) on every LF-ended line of the file: "ok <name bytes> <pos> <depth>" or "bad"
 //   hostdump forkcheck x               "1" when the executables would stay one process here (fast_exit.hpp: a profiler / preload in
 //                                      the environment, or a GPU runtime already open), else "0"
 #include <algorithm>
@@ -21,6 +23,7 @@
 #include <iostream>
 #include <string>
 
+#include "../csrc/depth_line.hpp"
 #include "bam.hpp"
 #include "fast_exit.hpp"
 #include "device_pick.hpp"
@@ -49,6 +52,17 @@ int main(int argc, char **argv)
             if (argc > 8) prm.max_span_frac = std::atof(argv[8]);
             const std::string t = debug_trace(c, argv[3], prm);
             std::fwrite(t.data(), 1, t.size(), stdout);
+        } else if (mode == "depthline") {
+            const std::vector<char> txt = read_file(argv[2]);
+            const uint8_t *p = reinterpret_cast<const uint8_t *>(txt.data());
+            for (size_t a = 0; a < txt.size();) {
+                const void *lf = std::memchr(p + a, '\n', txt.size() - a);
+                const size_t e = lf ? static_cast<size_t>(static_cast<const uint8_t *>(lf) - p) : txt.size();
+                const palace::DepthLine d = palace::depth_line_parse(p + a, static_cast<int64_t>(e - a));
+                if (d.error) std::printf("bad\n");
+                else std::printf("ok %d %u %u\n", d.name_len, d.pos, d.depth);
+                a = e + 1;
+            }
         } else if (mode == "devicepick") {
             const int ord = pick_device();
             const char *v = std::getenv("ROCR_VISIBLE_DEVICES");
