@@ -781,6 +781,84 @@ int palace_stage04_match(palace_ctx *ctx, palace_stage04 *s, const palace_graph_
 int palace_stage04_result(palace_ctx *ctx, palace_stage04 *s, palace_match_result **out, const int32_t **contig_of_out,
                           int64_t *n_segs_filtered_out);
 
+/* ---- paths -> FASTA: the assembly's index, its names, and the output text gathered on the device (make_fa_from_path) ------- */
+
+#define PALACE_FASTA_TILE_BYTES 4096       /* bytes of text one workgroup of the index kernels looks at */
+
+/* One record of a FASTA text in device memory, what a `.fai` row holds (48 bytes): the name is text[name_off .. name_off +
+ * name_len), the bytes behind '>' up to the first space, TAB, CR or LF; seq_off: offset of the byte behind the header line's LF
+ * (the text's length when the header line is the text's last and has no LF); length: sequence bytes; line_bases / line_width:
+ * those of the record's first sequence line (width = bases + CR + LF as present; both 0 when no line follows the header in the
+ * record).  Base p of the record is text[seq_off + p / line_bases * line_width + p % line_bases]. */
+typedef struct {
+    int64_t name_off, name_len, seq_off, length, line_bases, line_width;
+} palace_fasta_rec;
+
+#define PALACE_FASTA_OK 0
+#define PALACE_FASTA_ETEXT 1      /* the text does not begin with '>' (reported at line 1) */
+#define PALACE_FASTA_ENAME 2      /* a header line without a name */
+#define PALACE_FASTA_ERAGGED 3    /* a sequence line behind a line that is not the first line's bases and width, or longer than it */
+#define PALACE_FASTA_EBLANK 4     /* a sequence line behind a blank line of its record */
+#define PALACE_FASTA_EBYTE 5      /* a sequence byte outside 0x21-0x7E (a CR directly before the LF is not one) */
+
+/* n_records: header lines of the text; error / bad_line: the smallest (1-based line, code) pair among the text's faults, 0 / 0
+ * when it has none */
+typedef struct {
+    int64_t n_records, bad_line;
+    int32_t error, reserved;
+} palace_fasta_status;
+
+/* The index of the FASTA text d_text[0 .. n) (16-byte aligned), the rules of samtools faidx restated line by line so that every
+ * line is judged by itself, its successor and its record's first line -- the verdict does not depend on how the text falls into
+ * tiles: lines end at LF, a last line without LF is a line; a line that begins with '>' begins a record; a blank line has no
+ * bases.  A sequence line L with bases that is not its record's first is at fault when the line P before it is blank (EBLANK),
+ * when P's bases or width differ from the first line's, or when L has more bases than the first line (ERAGGED): a record's last
+ * line may be shorter, blank lines may only follow it.  Writes the records in file order to d_recs[0 .. n_records) when
+ * n_records <= recs_cap and nothing otherwise (a record is at least 3 bytes of text; a caller may also ask with recs_cap = 0
+ * and come back); with a fault the records mean nothing.  Four launches whatever the text holds (count, scan, records, lines)
+ * over tiles of PALACE_FASTA_TILE_BYTES; a line or a record may span any number of tiles.  d_scratch:
+ * palace_fasta_index_scratch_bytes(n) bytes of device memory.  Waits for the stream (it hands the status back). */
+size_t palace_fasta_index_scratch_bytes(int64_t n);
+int palace_fasta_index(palace_ctx *ctx, const uint8_t *d_text, int64_t n, palace_fasta_rec *d_recs, int64_t recs_cap, void *d_scratch,
+                       size_t scratch_bytes, palace_fasta_status *status_out);
+
+/* The records' names as a hash table on the device, built from the text where it lies (d_text and d_recs stay the caller's and
+ * must outlive the table; n_records < 2^29).  Of records with byte-equal names the FIRST is the one a look-up finds; d_dup, when
+ * not null, gets one byte per record: 1 when an earlier record has its name.  Enqueues only; destroy waits for the stream. */
+typedef struct palace_fasta_names palace_fasta_names;
+int palace_fasta_names_create(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, int64_t n_records, uint8_t *d_dup,
+                              palace_fasta_names **out);
+int palace_fasta_names_destroy(palace_ctx *ctx, palace_fasta_names *names);
+
+#define PALACE_PATH_NOTHING (-1)   /* the token contributes no sequence */
+#define PALACE_PATH_NOT_FOUND (-2) /* neither the name nor the name without its last '_' part is a record */
+#define PALACE_PATH_REVERSE 1      /* bit 0 of a code >= 0: the record is taken reverse-complemented */
+#define PALACE_PATH_SECOND_TRY 2   /* bit 1: found only without its last '_'-separated part; the record is code >> 2 */
+
+/* Tokens of a paths file looked up: token t is d_tok[d_tok_off[t] .. d_tok_off[t + 1]), spaces removed and white space stripped
+ * by the host.  A token of at most one byte contributes nothing; a last byte '+' or '-' is the strand and the rest the name,
+ * otherwise the whole token is the name, taken forward; a name that is no record is tried once more cut before its last '_' (a
+ * name without '_' becomes the empty name, which no record has).  d_code[t] gets one of the values above.  Enqueues only. */
+int palace_path_resolve(palace_ctx *ctx, const palace_fasta_names *names, const uint8_t *d_tok, const int64_t *d_tok_off, int64_t n_tok,
+                        int32_t *d_code);
+
+/* Path p holds the tokens d_path_off[p] .. d_path_off[p + 1] (n_paths + 1 ascending entries, the last one n_tok).  Writes
+ * d_tok_cum[0 .. n_tok]: the sequence bytes of all tokens in front of token t (a token without record has none), and
+ * d_path_len[p]: the sequence bytes of path p -- a scan over the tokens, the paths' sums are differences of it.  Enqueues only. */
+int palace_path_fasta_lengths(palace_ctx *ctx, const palace_fasta_rec *d_recs, const int32_t *d_code, int64_t n_tok, const int64_t *d_path_off,
+                              int64_t n_paths, int64_t *d_tok_cum, int64_t *d_path_len);
+
+/* Bytes [lo, hi) of the output text to d_out[0 .. hi - lo) (d_out 16-byte aligned; nothing outside that range is written).  The
+ * text is, path by path, '>' header LF sequence LF: path p begins at byte d_path_out[p] (n_paths + 1 entries: d_path_out[p + 1] =
+ * d_path_out[p] + header length + sequence length + 3), its header is d_hdr[d_hdr_off[p] .. d_hdr_off[p + 1]), its sequence the
+ * tokens' records one behind the other, a reversed one read from its end with A<->T, C<->G, a<->t, c<->g swapped and every other
+ * byte as it is.  d_code, d_tok_cum, d_path_off as palace_path_fasta_lengths left them.  Any 0 <= lo <= hi <= d_path_out[n_paths]
+ * will do.  A lane writes 16 aligned bytes of d_out; the path of a tile's first and last byte is searched once per tile, a lane
+ * searches its token once and walks on from there.  Enqueues only. */
+int palace_path_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const int32_t *d_code,
+                            const int64_t *d_tok_cum, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_hdr,
+                            const int64_t *d_hdr_off, const int64_t *d_path_out, int64_t lo, int64_t hi, uint8_t *d_out);
+
 #ifdef __cplusplus
 }
 #endif

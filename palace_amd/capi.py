@@ -79,6 +79,16 @@ DEPTH_CURSOR_DTYPE = np.dtype([("lines", np.int64), ("sum", np.uint64), ("bad_li
                                ("tail", np.uint8, (2, 4096))])
 DEPTH_RUN_DTYPE = np.dtype([("sum", np.uint64), ("lines", np.uint64), ("name_off", np.uint32), ("name_len", np.uint32)])
 assert DEPTH_CURSOR_DTYPE.itemsize == 64 + 8192 and DEPTH_RUN_DTYPE.itemsize == 24
+FASTA_REC_DTYPE = np.dtype([(k, np.int64) for k in ("name_off", "name_len", "seq_off", "length", "line_bases", "line_width")])
+FASTA_TILE_BYTES = 4096                 # PALACE_FASTA_TILE_BYTES
+PATH_NOTHING, PATH_NOT_FOUND, PATH_REVERSE, PATH_SECOND_TRY = -1, -2, 1, 2
+
+
+class FastaStatus(C.Structure):
+    """palace_fasta_status"""
+    _fields_ = [("n_records", C.c_int64), ("bad_line", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
+
+
 assert CAND_DTYPE.itemsize == 64 and EDGE_DTYPE.itemsize == 32 and SA_ITEM_DTYPE.itemsize == 32
 
 _SIGS = {
@@ -202,6 +212,14 @@ _SIGS = {
     "palace_stage04_counts": [C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
     "palace_stage04_match": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32],
     "palace_stage04_result": [C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64)],
+    "palace_fasta_index_scratch_bytes": [C.c_int64],    # (returns size_t: restype set below)
+    "palace_fasta_index": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.POINTER(FastaStatus)],
+    "palace_fasta_names_create": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_void_p)],
+    "palace_fasta_names_destroy": [C.c_void_p, C.c_void_p],
+    "palace_path_resolve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "palace_path_fasta_lengths": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "palace_path_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
 }
 
 
@@ -240,6 +258,7 @@ def lib() -> C.CDLL:
         _LIB.palace_fastq_scratch_bytes.restype = C.c_size_t
         _LIB.palace_bam_walk_scratch_bytes.restype = C.c_size_t
         _LIB.palace_depth_parse_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_fasta_index_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -882,3 +901,91 @@ def window_minimums(hit_ratio: float, perfect_ratio: float):
     """int(500 * float32(ratio)) -- the expression of extract_ref.cpp:513-514."""
     w = np.float32(500)
     return int(w * np.float32(hit_ratio)), int(w * np.float32(perfect_ratio))
+
+
+def fasta_index(ctx: Ctx, text: bytes, recs_cap: int | None = None):
+    """FASTA text through palace_fasta_index: (status, records as FASTA_REC_DTYPE or None when they did not fit recs_cap, the text
+    on the device, the records on the device).  recs_cap None: asked for first (a call with room for no record), then given."""
+    a = np.frombuffer(text, dtype=np.uint8)
+    d_text = ctx.upload(a)
+    d_scratch = DevBuf(ctx, max(int(lib().palace_fasta_index_scratch_bytes(len(a))), 1))
+    st = FastaStatus()
+    if recs_cap is None:
+        _check(lib().palace_fasta_index(ctx.h, d_text.ptr, len(a), None, 0, d_scratch.ptr, d_scratch.nbytes, C.byref(st)), "palace_fasta_index")
+        recs_cap = int(st.n_records)
+    d_recs = ctx.empty((max(recs_cap, 1),), FASTA_REC_DTYPE)
+    _check(lib().palace_fasta_index(ctx.h, d_text.ptr, len(a), d_recs.ptr, recs_cap, d_scratch.ptr, d_scratch.nbytes, C.byref(st)), "palace_fasta_index")
+    d_scratch.free()
+    recs = d_recs.to_host()[:int(st.n_records)] if int(st.n_records) <= recs_cap else None
+    return st, recs, d_text, d_recs
+
+
+class PathFasta:
+    """The chain behind make_fa_from_path at the ABI: an indexed FASTA with its name table, then per paths file resolve ->
+    lengths -> write.  The host's part -- tokens, headers, the paths' places in the output -- is the caller's (tests/path_fasta_cases.py)."""
+
+    def __init__(self, ctx: Ctx, text: bytes):
+        self.ctx = ctx
+        self.status, self.recs, self.d_text, self.d_recs = fasta_index(ctx, text)
+        assert self.status.error == 0, (self.status.error, self.status.bad_line)
+        self.n = int(self.status.n_records)
+        self.d_dup = ctx.empty((max(self.n, 1),), np.uint8)
+        self.names = C.c_void_p()
+        _check(lib().palace_fasta_names_create(ctx.h, self.d_text.ptr, self.d_recs.ptr, self.n, self.d_dup.ptr, C.byref(self.names)), "palace_fasta_names_create")
+
+    def duplicates(self) -> np.ndarray:
+        return self.d_dup.to_host()[:self.n]
+
+    def resolve(self, tokens):
+        """tokens: cleaned token bytes in file order -> (codes on the host, device buffer of the codes)"""
+        off = np.zeros(len(tokens) + 1, np.int64)
+        np.cumsum([len(t) for t in tokens], out=off[1:])
+        d_tok = self.ctx.upload(np.frombuffer(b"".join(tokens), np.uint8))
+        d_off = self.ctx.upload(off)
+        d_code = self.ctx.empty((max(len(tokens), 1),), np.int32)
+        _check(lib().palace_path_resolve(self.ctx.h, self.names, d_tok.ptr, d_off.ptr, len(tokens), d_code.ptr), "palace_path_resolve")
+        return d_code.to_host()[:len(tokens)], d_code
+
+    def lengths(self, d_code: DevBuf, path_off: np.ndarray):
+        n_tok, n_paths = int(path_off[-1]), len(path_off) - 1
+        d_path_off = self.ctx.upload(np.asarray(path_off, np.int64))
+        d_cum = self.ctx.empty((n_tok + 1,), np.int64)
+        d_len = self.ctx.empty((max(n_paths, 1),), np.int64)
+        _check(lib().palace_path_fasta_lengths(self.ctx.h, self.d_recs.ptr, d_code.ptr, n_tok, d_path_off.ptr, n_paths, d_cum.ptr, d_len.ptr),
+               "palace_path_fasta_lengths")
+        return d_len.to_host()[:n_paths], d_cum, d_path_off
+
+    def writer(self, d_code: DevBuf, d_cum: DevBuf, d_path_off: DevBuf, headers, lens):
+        """-> (total bytes of the output text, windows(cuts))"""
+        n_paths = len(headers)
+        hdr_off = np.zeros(n_paths + 1, np.int64)
+        np.cumsum([len(h) for h in headers], out=hdr_off[1:])
+        path_out = np.zeros(n_paths + 1, np.int64)
+        np.cumsum([len(h) + int(l) + 3 for h, l in zip(headers, lens)], out=path_out[1:])
+        d_hdr = self.ctx.upload(np.frombuffer(b"".join(headers), np.uint8))
+        d_hdr_off, d_path_out = self.ctx.upload(hdr_off), self.ctx.upload(path_out)
+
+        def windows(cuts, guard: int = 32):
+            """the text in the windows [0, c1), [c1, c2), ... [ck, total) for the ascending cuts c1 .. ck (equal neighbours: an empty
+            window), every window in a slot of its own of one device buffer with `guard` bytes (a multiple of 16) in front of and
+            behind it -> (the windows' bytes joined, every guard byte untouched)"""
+            total = int(path_out[-1])
+            bounds = [0] + [int(c) for c in cuts] + [total]
+            slots, at = [], 0
+            for lo, hi in zip(bounds, bounds[1:]):
+                slots.append(at + guard)
+                at += guard + (hi - lo + 15) // 16 * 16 + guard
+            d_out = self.ctx.upload(np.full(max(at, 1), 0xA5, np.uint8))
+            for (lo, hi), slot in zip(zip(bounds, bounds[1:]), slots):
+                _check(lib().palace_path_fasta_write(self.ctx.h, self.d_text.ptr, self.d_recs.ptr, d_code.ptr, d_cum.ptr, d_path_off.ptr, n_paths, d_hdr.ptr,
+                                                     d_hdr_off.ptr, d_path_out.ptr, lo, hi, d_out.ptr + slot), "palace_path_fasta_write")
+            got = d_out.to_host()
+            d_out.free()
+            keep = np.zeros(len(got), bool)
+            for (lo, hi), slot in zip(zip(bounds, bounds[1:]), slots):
+                keep[slot:slot + hi - lo] = True
+            return got[keep].tobytes(), bool((got[~keep] == 0xA5).all())
+        return int(path_out[-1]), windows
+
+    def close(self):
+        _check(lib().palace_fasta_names_destroy(self.ctx.h, self.names), "palace_fasta_names_destroy")

@@ -27,6 +27,7 @@
 // palace_bam_names_differ compares them where they lie.  Every read lies inside the record the walk accepted.
 #include "common.hpp"
 #include "bam_record.hpp"
+#include "name_hash.hpp"
 
 namespace palace {
 namespace {
@@ -287,20 +288,6 @@ struct palace_bam_names {
 namespace palace {
 namespace {
 
-__device__ __forceinline__ uint32_t hash_name(const uint8_t *p, int64_t n)
-{
-    uint64_t h = 0xcbf29ce484222325ull;
-    for (int64_t i = 0; i < n; i++) { h ^= p[i]; h *= 0x100000001b3ull; }
-    h ^= h >> 29; h *= 0xbf58476d1ce4e5b9ull; h ^= h >> 32;
-    return static_cast<uint32_t>(h);
-}
-__device__ __forceinline__ bool same_bytes(const uint8_t *a, int64_t na, const uint8_t *b, int64_t nb)
-{
-    if (na != nb) return false;
-    for (int64_t i = 0; i < na; i++)
-        if (a[i] != b[i]) return false;
-    return true;
-}
 __device__ __forceinline__ bool is_name(const palace_bam_names &t, int32_t tid, const uint8_t *p, int64_t n)
 {
     return same_bytes(t.names + t.off[tid], t.off[tid + 1] - t.off[tid], p, n);

@@ -1,0 +1,258 @@
+// make_fa_from_path <assembly.fasta> <paths> <out.fasta> <mode>: the reference's share/palace/scripts/make_fa_from_path.py (call
+// sites palace:697-700, 747-750, 778-781) with its command line and its stdout, the FASTA indexed and the output text gathered
+// on the device (csrc/path_fasta.hip; the rules: DESIGN.md 8).  The host reads the files, splits the paths file into tokens
+// (path_tokens.hpp), writes the headers and the output file; no sequence byte is produced here.
+//   make_fa_from_path --batch <list> <assembly.fasta>: one `<paths> <out.fasta> <mode>` per line of <list>; the FASTA is
+//   uploaded, indexed and hashed once, every output is what a run of its own writes (the step-5 loop of palace:672-806).
+// The FASTA has to fit the device whole: there is no path around the device.  PALACE_PATHFA_WINDOW: bytes of output text per
+// window (default 256 MiB); a window is copied back and written to the file while the next one is computed.
+#include <cstdio>
+#include <cstdlib>
+#include <fstream>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/palace_hip.h"
+#include "device_pick.hpp"
+#include "fast_exit.hpp"
+#include "fastx.hpp"
+#include "path_tokens.hpp"
+#include "textio.hpp"
+#include "trace.hpp"
+
+namespace {
+
+struct Failure : std::runtime_error { using std::runtime_error::runtime_error; };
+
+#define HIP_OK(call)                                                                     \
+    do {                                                                                 \
+        if ((call) != PALACE_OK) throw Failure(std::string(#call " failed: ") + palace_last_error()); \
+    } while (0)
+
+// device memory that goes with its scope
+struct Dev {
+    palace_ctx *ctx;
+    void *p = nullptr;
+    Dev(palace_ctx *c, size_t bytes, const char *what) : ctx(c)
+    {
+        if (palace_malloc(ctx, bytes ? bytes : 1, &p) != PALACE_OK)
+            throw Failure(std::string(what) + " (" + std::to_string(bytes) + " bytes) does not fit the device: " + palace_last_error());
+    }
+    ~Dev() { if (p) palace_free(ctx, p); }
+    Dev(const Dev &) = delete;
+    Dev &operator=(const Dev &) = delete;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+template <class T>
+std::unique_ptr<Dev> uploaded(palace_ctx *ctx, const T *src, size_t count, const char *what)
+{
+    auto d = std::make_unique<Dev>(ctx, count * sizeof(T), what);
+    if (count) HIP_OK(palace_h2d(ctx, d->p, src, count * sizeof(T)));
+    return d;
+}
+
+const char *fault_text(int code)
+{
+    switch (code) {
+    case PALACE_FASTA_ETEXT: return "text before the first '>'";
+    case PALACE_FASTA_ENAME: return "a header line without a name";
+    case PALACE_FASTA_ERAGGED: return "a sequence line behind a line of another length than the record's first (only a record's last line may be shorter)";
+    case PALACE_FASTA_EBLANK: return "a sequence line behind a blank line of its record";
+    case PALACE_FASTA_EBYTE: return "a sequence byte outside 0x21-0x7E";
+    }
+    return "malformed";
+}
+
+// the assembly on the device: text, index, names
+struct Assembly {
+    palace_ctx *ctx;
+    std::string path;
+    palace_host::MappedText text;
+    std::unique_ptr<Dev> d_text, d_recs;
+    palace_fasta_names *names = nullptr;
+    int64_t n_records = 0;
+
+    Assembly(palace_ctx *c, const std::string &fasta, palace_host::Trace &tr) : ctx(c), path(fasta)
+    {
+        try { text.open(fasta); }
+        catch (const std::exception &) { throw Failure("cannot open " + fasta); }
+        tr.lap("FASTA read");
+        const int64_t n = static_cast<int64_t>(text.size);
+        d_text = uploaded(ctx, reinterpret_cast<const uint8_t *>(text.data), text.size, "the FASTA is read on the device and has no other path: it");
+        tr.lap("FASTA uploaded");
+        Dev scratch(ctx, palace_fasta_index_scratch_bytes(n), "the index's scratch");
+        palace_fasta_status st{};
+        HIP_OK(palace_fasta_index(ctx, d_text->as<uint8_t>(), n, nullptr, 0, scratch.p, palace_fasta_index_scratch_bytes(n), &st));      // how many records
+        d_recs = std::make_unique<Dev>(ctx, static_cast<size_t>(st.n_records) * sizeof(palace_fasta_rec), "the FASTA's index");
+        HIP_OK(palace_fasta_index(ctx, d_text->as<uint8_t>(), n, d_recs->as<palace_fasta_rec>(), st.n_records, scratch.p, palace_fasta_index_scratch_bytes(n), &st));
+        if (st.error) throw Failure(fasta + ": line " + std::to_string(st.bad_line) + ": " + fault_text(st.error));
+        n_records = st.n_records;
+        tr.lap("FASTA indexed");
+        Dev dup(ctx, static_cast<size_t>(n_records), "the duplicate flags");
+        HIP_OK(palace_fasta_names_create(ctx, d_text->as<uint8_t>(), d_recs->as<palace_fasta_rec>(), n_records, dup.as<uint8_t>(), &names));
+        std::vector<uint8_t> h_dup(static_cast<size_t>(n_records));
+        if (n_records) HIP_OK(palace_d2h(ctx, h_dup.data(), dup.p, h_dup.size()));
+        size_t k = 0;
+        for (; k < h_dup.size() && !h_dup[k]; k++) {}
+        if (k < h_dup.size()) {                                             // (rare: the records come to the host only to name them)
+            std::vector<palace_fasta_rec> recs(h_dup.size());
+            HIP_OK(palace_d2h(ctx, recs.data(), d_recs->p, recs.size() * sizeof(palace_fasta_rec)));
+            for (; k < h_dup.size(); k++)
+                if (h_dup[k])
+                    std::fprintf(stderr, "make_fa_from_path: warning: %s: sequence name '%.*s' appears again in record %zu: the first one is used\n", fasta.c_str(),
+                                 static_cast<int>(recs[k].name_len), text.data + recs[k].name_off, k + 1);
+        }
+        tr.lap("names hashed");
+    }
+    ~Assembly() { if (names) palace_fasta_names_destroy(ctx, names); }
+};
+
+int64_t window_bytes()
+{
+    const char *e = std::getenv("PALACE_PATHFA_WINDOW");
+    const long long v = (e && *e) ? std::atoll(e) : 0;
+    return v > 0 ? static_cast<int64_t>(v) : (256ll << 20);
+}
+
+struct Job { std::string paths, out, mode; };
+
+// one paths file -> one FASTA.  The output file exists (empty) from the start; nothing is written to it before every token is resolved
+void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly> &assembly, const Job &job, palace_host::Trace &tr)
+{
+    std::fputs("make_fa_from_path.py running\n", stdout);
+    if (!assembly) assembly = std::make_unique<Assembly>(ctx, fasta, tr);
+    const Assembly &as = *assembly;
+    palace_host::MappedText ptext;
+    try { ptext.open(job.paths); }
+    catch (const std::exception &) { throw Failure("cannot open " + job.paths); }
+    std::FILE *out = std::fopen(job.out.c_str(), "wb");
+    if (!out) throw Failure("cannot write " + job.out);
+    struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{out};
+    const palace_host::PathTokens tk = palace_host::split_paths(ptext.data, ptext.size);
+    const int64_t n_tok = static_cast<int64_t>(tk.tokens()), n_paths = static_cast<int64_t>(tk.lines());
+    tr.lap("paths split");
+
+    auto d_tok = uploaded(ctx, reinterpret_cast<const uint8_t *>(tk.clean.data()), tk.clean.size(), "the tokens");
+    auto d_tok_off = uploaded(ctx, tk.clean_off.data(), tk.clean_off.size(), "the tokens' offsets");
+    Dev d_code(ctx, static_cast<size_t>(n_tok) * sizeof(int32_t), "the tokens' records");
+    HIP_OK(palace_path_resolve(ctx, as.names, d_tok->as<uint8_t>(), d_tok_off->as<int64_t>(), n_tok, d_code.as<int32_t>()));
+    std::vector<int32_t> code(static_cast<size_t>(n_tok));
+    if (n_tok) HIP_OK(palace_d2h(ctx, code.data(), d_code.p, code.size() * sizeof(int32_t)));
+    for (int64_t l = 0; l < n_paths; l++)
+        for (int64_t t = tk.line_tok[static_cast<size_t>(l)]; t < tk.line_tok[static_cast<size_t>(l) + 1]; t++) {
+            const int32_t c = code[static_cast<size_t>(t)];
+            if (c == PALACE_PATH_NOTHING) continue;
+            const std::string token = tk.clean.substr(static_cast<size_t>(tk.clean_off[static_cast<size_t>(t)]),
+                                                      static_cast<size_t>(tk.clean_off[static_cast<size_t>(t) + 1] - tk.clean_off[static_cast<size_t>(t)]));
+            const bool oriented = token.back() == '+' || token.back() == '-';
+            if (!oriented && (c == PALACE_PATH_NOT_FOUND || (c & PALACE_PATH_SECOND_TRY))) {
+                const size_t cut = token.rfind('_');
+                std::printf("Contig not found: %s\n", cut == std::string::npos ? "" : token.substr(0, cut).c_str());
+            }
+            if (c == PALACE_PATH_NOT_FOUND) {
+                std::fflush(stdout);
+                throw Failure(job.paths + ": line " + std::to_string(tk.line_index[static_cast<size_t>(l)] + 1) + ": contig of token '" + token +
+                              "' is not in " + fasta);
+            }
+        }
+    tr.lap("tokens resolved");
+
+    auto d_path_off = uploaded(ctx, tk.line_tok.data(), tk.line_tok.size(), "the paths' tokens");
+    Dev d_cum(ctx, static_cast<size_t>(n_tok + 1) * sizeof(int64_t), "the tokens' places");
+    Dev d_len(ctx, static_cast<size_t>(n_paths) * sizeof(int64_t), "the paths' lengths");
+    HIP_OK(palace_path_fasta_lengths(ctx, as.d_recs->as<palace_fasta_rec>(), d_code.as<int32_t>(), n_tok, d_path_off->as<int64_t>(), n_paths, d_cum.as<int64_t>(),
+                                     d_len.as<int64_t>()));
+    std::vector<int64_t> len(static_cast<size_t>(n_paths));
+    if (n_paths) HIP_OK(palace_d2h(ctx, len.data(), d_len.p, len.size() * sizeof(int64_t)));
+    std::string hdr;
+    std::vector<int64_t> hdr_off{0}, path_out{0};
+    for (int64_t l = 0; l < n_paths; l++) {
+        if (job.mode == "0") hdr += "res_" + std::to_string(tk.line_index[static_cast<size_t>(l)] + 1) + "_" + std::to_string(len[static_cast<size_t>(l)]);
+        else hdr.append(tk.raw, static_cast<size_t>(tk.raw_off[static_cast<size_t>(tk.line_tok[static_cast<size_t>(l)])]),
+                        static_cast<size_t>(tk.raw_off[static_cast<size_t>(tk.line_tok[static_cast<size_t>(l) + 1])] - tk.raw_off[static_cast<size_t>(tk.line_tok[static_cast<size_t>(l)])]));
+        path_out.push_back(path_out.back() + (static_cast<int64_t>(hdr.size()) - hdr_off.back()) + len[static_cast<size_t>(l)] + 3);
+        hdr_off.push_back(static_cast<int64_t>(hdr.size()));
+    }
+    const int64_t total = path_out.back();
+    auto d_hdr = uploaded(ctx, reinterpret_cast<const uint8_t *>(hdr.data()), hdr.size(), "the headers");
+    auto d_hdr_off = uploaded(ctx, hdr_off.data(), hdr_off.size(), "the headers' offsets");
+    auto d_path_out = uploaded(ctx, path_out.data(), path_out.size(), "the paths' places");
+    tr.lap("lengths and headers");
+
+    // windows of the output text: window w is computed and copied back while window w - 1 goes to the file
+    const int64_t win = total < window_bytes() ? total : window_bytes();
+    if (total) {
+        Dev d_win0(ctx, static_cast<size_t>(win), "an output window"), d_win1(ctx, static_cast<size_t>(win), "an output window");
+        void *pin[2] = {nullptr, nullptr};
+        struct Pinned { palace_ctx *c; void **p; ~Pinned() { for (int i = 0; i < 2; i++) if (p[i]) palace_host_free(c, p[i]); } } pinned{ctx, pin};
+        for (int i = 0; i < 2; i++)
+            if (palace_host_alloc(ctx, static_cast<size_t>(win), &pin[i]) != PALACE_OK) throw Failure(std::string("no pinned memory for an output window: ") + palace_last_error());
+        uint8_t *d_win[2] = {d_win0.as<uint8_t>(), d_win1.as<uint8_t>()};
+        auto flush = [&](int64_t w) {
+            const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
+            HIP_OK(palace_mark_wait(ctx, static_cast<int>(w & 1)));
+            if (std::fwrite(pin[w & 1], 1, static_cast<size_t>(hi - lo), out) != static_cast<size_t>(hi - lo)) throw Failure("cannot write " + job.out);
+        };
+        const int64_t n_win = (total + win - 1) / win;
+        for (int64_t w = 0; w < n_win; w++) {
+            const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
+            HIP_OK(palace_path_fasta_write(ctx, as.d_text->as<uint8_t>(), as.d_recs->as<palace_fasta_rec>(), d_code.as<int32_t>(), d_cum.as<int64_t>(),
+                                           d_path_off->as<int64_t>(), n_paths, d_hdr->as<uint8_t>(), d_hdr_off->as<int64_t>(), d_path_out->as<int64_t>(), lo, hi,
+                                           d_win[w & 1]));
+            HIP_OK(palace_d2h_async(ctx, pin[w & 1], d_win[w & 1], static_cast<size_t>(hi - lo)));
+            HIP_OK(palace_mark(ctx, static_cast<int>(w & 1)));
+            if (w) flush(w - 1);
+        }
+        flush(n_win - 1);
+    }
+    closer.f = nullptr;
+    if (std::fclose(out) != 0) throw Failure("cannot write " + job.out);
+    tr.lap("output written");
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    std::vector<Job> jobs;
+    std::string fasta, list;
+    if (argc == 5 && std::string(argv[1]) != "--batch") { fasta = argv[1]; jobs.push_back(Job{argv[2], argv[3], argv[4]}); }
+    else if (argc == 4 && std::string(argv[1]) == "--batch") { list = argv[2]; fasta = argv[3]; }
+    else {
+        std::fputs("Usage: make_fa_from_path <fasta_file> <paths_file> <output_file> <mode>\n"
+                   "       make_fa_from_path --batch <list of '<paths_file> <output_file> <mode>' lines> <fasta_file>\n", stderr);
+        return 1;
+    }
+    palace_host::FastExit fast_exit = palace_host::fast_exit_begin();   // from here on this is the worker process (fast_exit.hpp)
+    const int device = palace_host::pick_device();                       // PALACE_DEVICE (device_pick.hpp): before anything touches HIP
+    palace_host::Trace tr("make_fa_from_path");
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
+        std::fprintf(stderr, "make_fa_from_path: no GPU device to work on (%s); there is no CPU path\n", palace_last_error());
+        return 1;
+    }
+    tr.lap("device up");
+    try {
+        if (!list.empty()) {
+            std::ifstream lf(list);
+            if (!lf) throw Failure("cannot open batch list " + list);
+            for (std::string line; std::getline(lf, line);) {
+                std::vector<palace_host::sv> t;
+                palace_host::split_ws(line, t);
+                if (t.empty()) continue;
+                if (t.size() != 3) throw Failure("batch list: expected '<paths> <out.fasta> <mode>' per line");
+                jobs.push_back(Job{std::string(t[0]), std::string(t[1]), std::string(t[2])});
+            }
+        }
+        std::unique_ptr<Assembly> assembly;
+        for (const Job &j : jobs) run_job(ctx, fasta, assembly, j, tr);
+    } catch (const std::exception &e) {
+        std::fflush(stdout);
+        std::fprintf(stderr, "make_fa_from_path: %s\n", e.what());
+        return 1;
+    }
+    fast_exit.done(0);          // outputs are complete and closed: the caller goes on, the teardown happens behind it
+}
