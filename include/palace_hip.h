@@ -859,6 +859,55 @@ int palace_path_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palace
                             const int64_t *d_tok_cum, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_hdr,
                             const int64_t *d_hdr_off, const int64_t *d_path_out, int64_t lo, int64_t hi, uint8_t *d_out);
 
+/* ---- FASTG -> node FASTA and the `.fai` rows of both, on the device (split_fastg; the rules: DESIGN.md 8) -------------------- */
+
+/* Faults of a FASTG text beyond those of palace_fasta_index, reported in a palace_fasta_status like them */
+#define PALACE_FASTG_EPLUS 6      /* a sequence line that begins with '+' or '@' */
+#define PALACE_FASTG_EHIGH 7      /* a byte of 0x80 or above in a header line */
+#define PALACE_FASTG_ECR 8        /* a CR in a header line that is not directly before the LF */
+#define PALACE_FASTG_ENOLF 9      /* the text's last byte is not LF (reported at the last line) */
+#define PALACE_FASTG_EEMPTY 10    /* the text is empty (reported at line 1) */
+#define PALACE_FASTG_ENONAME 11   /* a header whose V (see palace_fastg_derive) is empty */
+#define PALACE_FASTG_EBASE 12     /* a byte other than A, C, G, T (either case) in the sequence of a primed record */
+
+/* The records of an indexed FASTG text (d_recs[0 .. n_records) as palace_fasta_index left them; that index's verdict is not asked
+ * for: name_off and seq_off hold whatever it is) named by the rule of split_fastg.py.  T: the bytes behind '>' up to the first
+ * space or the line's end (a CR directly before the LF is not the line's); U: T without its last byte; V: U up to its first ':'
+ * or ','; V ending in ' makes the record primed and the name V without that byte (it may be empty), otherwise the name is V.
+ * d_name_recs[r] is d_recs[r] with name_len the derived name's -- palace_fasta_names_create takes them as they are -- and
+ * d_primed[r] the primed bit.  status_out: n_records as given, and the smallest (1-based line, code) among the PALACE_FASTG_
+ * faults above (0 / 0: none); the caller takes the smaller of it and the index's.  One lane per record for the names, one per
+ * 16 bytes of text for everything else (the bases of a primed record are checked where they lie, however long the record); a
+ * fault is reduced as the smallest offset per code and its line counted afterwards, so the verdict does not depend on tiling.
+ * Waits for the stream. */
+int palace_fastg_derive(palace_ctx *ctx, const uint8_t *d_text, int64_t n, const palace_fasta_rec *d_recs, int64_t n_records,
+                        palace_fasta_rec *d_name_recs, uint8_t *d_primed, palace_fasta_status *status_out);
+
+/* The output's layout.  d_dup: palace_fasta_names_create's flags over d_name_recs; a record whose flag is set is dropped.  (That
+ * table never finds the name of no bytes and flags every record that has it: here the first of those is kept, and d_dup is put
+ * right.)  d_out_off[0 .. n_records]: the 64-bit exclusive scan of 1 + name_len + 1 + length + 1 over the kept records, the last
+ * entry the output's bytes; d_out_recs (may be null): record r as a record of the OUTPUT text -- name_off and name_len as
+ * given (the name's bytes stay in the FASTG text), seq_off its sequence's place in the output, length, and line_bases = length,
+ * line_width = length + 1 (both 0 for a record without bases) -- meaningful for kept records.  Waits for the stream. */
+int palace_fastg_plan(palace_ctx *ctx, const palace_fasta_rec *d_name_recs, uint8_t *d_dup, int64_t n_records, int64_t *d_out_off,
+                      palace_fasta_rec *d_out_recs, int64_t *n_kept_out, int64_t *out_bytes_out);
+
+/* Bytes [lo, hi) of the output text to d_out[0 .. hi - lo) (d_out 16-byte aligned; nothing outside that range is written): per
+ * kept record '>' name LF sequence LF in file order.  A forward record's bases are copied as they are; a primed record's are read
+ * from the end, upper-cased and complemented (A<->T, C<->G).  Only for a text without fault.  Any 0 <= lo <= hi <=
+ * d_out_off[n_records] will do; a lane writes 16 aligned bytes, the records of a tile's first and last byte are searched once
+ * per tile; a record may span any number of tiles and a tile may hold any number of records.  Enqueues only. */
+int palace_fastg_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_name_recs, const uint8_t *d_primed,
+                       const int64_t *d_out_off, int64_t n_records, int64_t lo, int64_t hi, uint8_t *d_out);
+
+/* The `.fai` rows of records whose names lie in a text on the device: name TAB length TAB seq_off TAB line_bases TAB line_width LF
+ * in decimal, none for a record with d_skip[r] set (d_skip may be null).  plan: d_row_off[0 .. n_records], the 64-bit scan of the
+ * rows' lengths, and their sum (waits for the stream); write: all rows to d_out[0 .. that sum), one lane per row (enqueues only). */
+int palace_fai_rows_plan(palace_ctx *ctx, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records, int64_t *d_row_off,
+                         int64_t *bytes_out);
+int palace_fai_rows_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records,
+                          const int64_t *d_row_off, uint8_t *d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,6 +218,11 @@ _SIGS = {
     "palace_fasta_names_destroy": [C.c_void_p, C.c_void_p],
     "palace_path_resolve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
     "palace_path_fasta_lengths": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "palace_fastg_derive": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(FastaStatus)],
+    "palace_fastg_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "palace_fastg_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_fai_rows_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_fai_rows_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "palace_path_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
 }
@@ -989,3 +994,86 @@ class PathFasta:
 
     def close(self):
         _check(lib().palace_fasta_names_destroy(self.ctx.h, self.names), "palace_fasta_names_destroy")
+
+
+FASTG_EPLUS, FASTG_EHIGH, FASTG_ECR, FASTG_ENOLF, FASTG_EEMPTY, FASTG_ENONAME, FASTG_EBASE = range(6, 13)
+
+
+class FastgSplit:
+    """The chain behind split_fastg at the ABI: palace_fasta_index -> palace_fastg_derive -> palace_fasta_names_create ->
+    palace_fastg_plan -> palace_fastg_write, and the `.fai` rows of the output and of the FASTG itself.  verdict: (code, line), the
+    smaller of the index's and the FASTG faults' (line, code); with one nothing behind derive is run."""
+
+    def __init__(self, ctx: Ctx, text: bytes):
+        self.ctx, self.names, self.whole_names = ctx, C.c_void_p(), C.c_void_p()
+        self.index_status, self.recs, self.d_text, self.d_recs = fasta_index(ctx, text)
+        self.n = int(self.index_status.n_records)
+        self.d_name_recs = ctx.empty((max(self.n, 1),), FASTA_REC_DTYPE)
+        self.d_primed = ctx.empty((max(self.n, 1),), np.uint8)
+        st = FastaStatus()
+        _check(lib().palace_fastg_derive(ctx.h, self.d_text.ptr, len(text), self.d_recs.ptr, self.n, self.d_name_recs.ptr, self.d_primed.ptr, C.byref(st)),
+               "palace_fastg_derive")
+        self.new_verdict = (int(st.error), int(st.bad_line))
+        faults = [(l, c) for c, l in (self.new_verdict, (int(self.index_status.error), int(self.index_status.bad_line))) if c]
+        self.verdict = min(faults)[::-1] if faults else (0, 0)
+        self.total = self.n_kept = 0
+        if self.verdict != (0, 0):
+            return
+        self.d_dup = ctx.empty((max(self.n, 1),), np.uint8)
+        _check(lib().palace_fasta_names_create(ctx.h, self.d_text.ptr, self.d_name_recs.ptr, self.n, self.d_dup.ptr, C.byref(self.names)), "palace_fasta_names_create")
+        self.d_out_off = ctx.empty((self.n + 1,), np.int64)
+        self.d_out_recs = ctx.empty((max(self.n, 1),), FASTA_REC_DTYPE)
+        kept, total = C.c_int64(), C.c_int64()
+        _check(lib().palace_fastg_plan(ctx.h, self.d_name_recs.ptr, self.d_dup.ptr, self.n, self.d_out_off.ptr, self.d_out_recs.ptr, C.byref(kept), C.byref(total)),
+               "palace_fastg_plan")
+        self.n_kept, self.total = int(kept.value), int(total.value)
+
+    def derived(self):
+        """-> (name records, primed bits, duplicate flags, output offsets) on the host"""
+        return self.d_name_recs.to_host()[:self.n], self.d_primed.to_host()[:self.n], self.d_dup.to_host()[:self.n], self.d_out_off.to_host()
+
+    def windows(self, cuts, guard: int = 32):
+        """the output in the windows [0, c1), [c1, c2), ... [ck, total), every window in a slot of its own of one device buffer with
+        `guard` bytes in front of and behind it -> (the windows' bytes joined, every guard byte untouched)"""
+        bounds = [0] + [int(c) for c in cuts] + [self.total]
+        slots, at = [], 0
+        for lo, hi in zip(bounds, bounds[1:]):
+            slots.append(at + guard)
+            at += guard + (hi - lo + 15) // 16 * 16 + guard
+        d_out = self.ctx.upload(np.full(max(at, 1), 0xA5, np.uint8))
+        for (lo, hi), slot in zip(zip(bounds, bounds[1:]), slots):
+            _check(lib().palace_fastg_write(self.ctx.h, self.d_text.ptr, self.d_name_recs.ptr, self.d_primed.ptr, self.d_out_off.ptr, self.n, lo, hi,
+                                            d_out.ptr + slot), "palace_fastg_write")
+        got = d_out.to_host()
+        d_out.free()
+        keep = np.zeros(len(got), bool)
+        for (lo, hi), slot in zip(zip(bounds, bounds[1:]), slots):
+            keep[slot:slot + hi - lo] = True
+        return got[keep].tobytes(), bool((got[~keep] == 0xA5).all())
+
+    def _rows(self, d_recs: DevBuf, d_skip: DevBuf) -> bytes:
+        d_off = self.ctx.empty((self.n + 1,), np.int64)
+        total = C.c_int64()
+        _check(lib().palace_fai_rows_plan(self.ctx.h, d_recs.ptr, d_skip.ptr, self.n, d_off.ptr, C.byref(total)), "palace_fai_rows_plan")
+        d_out = self.ctx.upload(np.full(int(total.value) + 16, 0xA5, np.uint8))
+        _check(lib().palace_fai_rows_write(self.ctx.h, self.d_text.ptr, d_recs.ptr, d_skip.ptr, self.n, d_off.ptr, d_out.ptr), "palace_fai_rows_write")
+        got = d_out.to_host()
+        assert (got[int(total.value):] == 0xA5).all(), "bytes behind the rows were written"
+        return got[:int(total.value)].tobytes()
+
+    def output_fai(self) -> bytes:
+        return self._rows(self.d_out_recs, self.d_dup)
+
+    def graph_fai(self):
+        """-> (rows, flags of the records left out)"""
+        d_skip = self.ctx.empty((max(self.n, 1),), np.uint8)
+        if not self.whole_names:
+            _check(lib().palace_fasta_names_create(self.ctx.h, self.d_text.ptr, self.d_recs.ptr, self.n, d_skip.ptr, C.byref(self.whole_names)),
+                   "palace_fasta_names_create")
+        return self._rows(self.d_recs, d_skip), d_skip.to_host()[:self.n]
+
+    def close(self):
+        for t in (self.names, self.whole_names):
+            if t:
+                _check(lib().palace_fasta_names_destroy(self.ctx.h, t), "palace_fasta_names_destroy")
+        self.names, self.whole_names = C.c_void_p(), C.c_void_p()

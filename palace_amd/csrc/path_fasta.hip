@@ -17,6 +17,7 @@
 // the text; see DESIGN.md 4 for the loads it issues.
 #include "common.hpp"
 #include "name_hash.hpp"
+#include "scan64.hpp"
 #include "text_lanes.hpp"
 
 #include <climits>
@@ -33,7 +34,6 @@ namespace palace {
 namespace {
 
 constexpr int kTileThreads = 256, kTileBytes = kTileThreads * kLaneBytes;
-constexpr int kScanThreads = 1024;
 constexpr int64_t kNone = INT64_MAX;
 
 static_assert(kTileBytes == PALACE_FASTA_TILE_BYTES, "the header states the tile");
@@ -358,26 +358,6 @@ __global__ __launch_bounds__(kScanThreads) void path_tok_scan_kernel(const palac
     if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
 }
 
-// one workgroup: sums[0 .. nb) become their exclusive prefix sums, sums[nb] the total
-__global__ __launch_bounds__(kScanThreads) void path_block_scan_kernel(long long *sums, int64_t nb)
-{
-    __shared__ long long s_scan[kScanThreads / 64 + 1];
-    const int64_t per = (nb + kScanThreads - 1) / kScanThreads;
-    const int64_t b0 = threadIdx.x * per < nb ? threadIdx.x * per : nb, b1 = b0 + per < nb ? b0 + per : nb;
-    long long mine = 0, total;
-    for (int64_t k = b0; k < b1; k++) mine += sums[k];
-    long long run = block_exclusive<long long, kScanThreads>(mine, s_scan, &total);
-    for (int64_t k = b0; k < b1; k++) { const long long v = sums[k]; sums[k] = run; run += v; }
-    if (threadIdx.x == 0) sums[nb] = total;
-}
-
-__global__ __launch_bounds__(kScanThreads) void path_tok_base_kernel(int64_t n_tok, int64_t *cum, const long long *block_base, int64_t nb)
-{
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kScanThreads + threadIdx.x;
-    if (i < n_tok) cum[i] += block_base[blockIdx.x];
-    if (i == 0) cum[n_tok] = block_base[nb];
-}
-
 __global__ __launch_bounds__(256) void path_len_kernel(const int64_t *cum, const int64_t *path_off, int64_t n_paths, int64_t *len)
 {
     const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -385,16 +365,6 @@ __global__ __launch_bounds__(256) void path_len_kernel(const int64_t *cum, const
 }
 
 // ---- the writer -------------------------------------------------------------------------------------------------------------------
-
-// the last index in [a, b] whose entry is <= v (v >= arr[a])
-__device__ __forceinline__ int64_t last_le(const int64_t *arr, int64_t a, int64_t b, int64_t v)
-{
-    while (a < b) {
-        const int64_t mid = a + (b - a + 1) / 2;
-        if (arr[mid] <= v) a = mid; else b = mid - 1;
-    }
-    return a;
-}
 
 // A<->T, C<->G in either case; every other byte as it is
 __device__ __forceinline__ uint32_t complement(uint32_t b)
@@ -582,8 +552,8 @@ extern "C" int palace_path_fasta_lengths(palace_ctx *ctx, const palace_fasta_rec
         if (rc) return rc;
         long long *sums = static_cast<long long *>(ctx->ws.ptr);
         hipLaunchKernelGGL(path_tok_scan_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, d_recs, d_code, n_tok, d_tok_cum, sums);
-        hipLaunchKernelGGL(path_block_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
-        hipLaunchKernelGGL(path_tok_base_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n_tok, d_tok_cum, sums, nb);
+        hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
+        hipLaunchKernelGGL(add_block_base_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n_tok, d_tok_cum, sums, nb);
     }
     if (n_paths)
         hipLaunchKernelGGL(path_len_kernel, dim3(static_cast<unsigned>((n_paths + 255) / 256)), dim3(256), 0, ctx->stream, d_tok_cum, d_path_off, n_paths, d_path_len);

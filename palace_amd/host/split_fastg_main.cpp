@@ -1,0 +1,240 @@
+// split_fastg -g <assembly_graph.fastg> [-o <nodes.fasta>] [--fai]: the reference's share/palace/scripts/split_fastg.py (call
+// site palace:389-397) with its command line, the FASTG indexed, its records named and the FASTA gathered on the device
+// (csrc/fastg_split.hip; the rules: DESIGN.md 8).  The host reads the file, asks for the verdict and writes what comes back; no
+// name is derived and no base is turned here.
+//   --fai: also <output>.fai and <graph>.fai, the rows of the three `samtools faidx` runs behind the script (palace:399-406),
+//   written as decimal text on the device.  In <graph>.fai a record whose whole name an earlier record has is left out, with one
+//   warning line on stderr.
+// The FASTG, the output and the tables have to fit the device: there is no path around it.  Exit 0 with nothing on stdout; 1
+// for a text outside the grammar (the message names the smallest line at fault; the output file is left empty) or any other
+// failure; 2 for a usage error.
+#include <cstdio>
+#include <cstdlib>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <vector>
+
+#include "../../include/palace_hip.h"
+#include "device_pick.hpp"
+#include "fast_exit.hpp"
+#include "fastx.hpp"
+#include "trace.hpp"
+
+namespace {
+
+struct Failure : std::runtime_error { using std::runtime_error::runtime_error; };
+
+#define HIP_OK(call)                                                                     \
+    do {                                                                                 \
+        if ((call) != PALACE_OK) throw Failure(std::string(#call " failed: ") + palace_last_error()); \
+    } while (0)
+
+// device memory that goes with its scope
+struct Dev {
+    palace_ctx *ctx;
+    void *p = nullptr;
+    Dev(palace_ctx *c, size_t bytes, const char *what) : ctx(c)
+    {
+        if (palace_malloc(ctx, bytes ? bytes : 1, &p) != PALACE_OK)
+            throw Failure(std::string(what) + " (" + std::to_string(bytes) + " bytes) does not fit the device: " + palace_last_error());
+    }
+    ~Dev() { if (p) palace_free(ctx, p); }
+    Dev(const Dev &) = delete;
+    Dev &operator=(const Dev &) = delete;
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+struct Names {
+    palace_ctx *ctx;
+    palace_fasta_names *t = nullptr;
+    ~Names() { if (t) palace_fasta_names_destroy(ctx, t); }
+};
+
+const char *fault_text(int code)
+{
+    switch (code) {
+    case PALACE_FASTA_ETEXT: return "text before the first '>'";
+    case PALACE_FASTA_ENAME: return "a header line without a name";
+    case PALACE_FASTA_ERAGGED: return "a sequence line behind a line of another length than the record's first (only a record's last line may be shorter)";
+    case PALACE_FASTA_EBLANK: return "a sequence line behind a blank line of its record";
+    case PALACE_FASTA_EBYTE: return "a sequence byte outside 0x21-0x7E";
+    case PALACE_FASTG_EPLUS: return "a sequence line that begins with '+' or '@'";
+    case PALACE_FASTG_EHIGH: return "a byte of 0x80 or above in a header line";
+    case PALACE_FASTG_ECR: return "a CR in a header line that is not directly before the LF";
+    case PALACE_FASTG_ENOLF: return "the text does not end in LF";
+    case PALACE_FASTG_EEMPTY: return "the file is empty";
+    case PALACE_FASTG_ENONAME: return "a header without a name in front of its last byte, its first ':' or ','";
+    case PALACE_FASTG_EBASE: return "a base other than A, C, G, T in a primed record";
+    }
+    return "malformed";
+}
+
+// a device buffer of `bytes` bytes to the file, in pieces
+void to_file(palace_ctx *ctx, const uint8_t *d, int64_t bytes, std::FILE *f, const std::string &path)
+{
+    const int64_t piece = 64ll << 20;
+    std::vector<uint8_t> buf(static_cast<size_t>(bytes < piece ? bytes : piece));
+    for (int64_t at = 0; at < bytes; at += piece) {
+        const size_t k = static_cast<size_t>(bytes - at < piece ? bytes - at : piece);
+        HIP_OK(palace_d2h(ctx, buf.data(), d + at, k));
+        if (std::fwrite(buf.data(), 1, k, f) != k) throw Failure("cannot write " + path);
+    }
+}
+
+// the `.fai` rows of d_recs (none where d_skip is set) to `path`
+void write_fai(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records, const std::string &path)
+{
+    Dev d_off(ctx, static_cast<size_t>(n_records + 1) * sizeof(int64_t), "the rows' places");
+    int64_t bytes = 0;
+    HIP_OK(palace_fai_rows_plan(ctx, d_recs, d_skip, n_records, d_off.as<int64_t>(), &bytes));
+    Dev d_rows(ctx, static_cast<size_t>(bytes), "the index rows");
+    HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off.as<int64_t>(), d_rows.as<uint8_t>()));
+    std::FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) throw Failure("cannot write " + path);
+    struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{f};
+    to_file(ctx, d_rows.as<uint8_t>(), bytes, f, path);
+    closer.f = nullptr;
+    if (std::fclose(f) != 0) throw Failure("cannot write " + path);
+}
+
+void run(palace_ctx *ctx, const std::string &graph, const std::string &output, bool fai, palace_host::Trace &tr)
+{
+    palace_host::MappedText text;
+    try { text.open(graph); }
+    catch (const std::exception &) { throw Failure("cannot open " + graph); }
+    std::FILE *out = std::fopen(output.c_str(), "wb");                       // (exists, empty, from here on: as the script's)
+    if (!out) throw Failure("cannot write " + output);
+    struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{out};
+    tr.lap("FASTG read");
+    const int64_t n = static_cast<int64_t>(text.size);
+    Dev d_text(ctx, text.size, "the FASTG is read on the device and has no other path: it");
+    if (n) HIP_OK(palace_h2d(ctx, d_text.p, text.data, text.size));
+    tr.lap("FASTG uploaded");
+
+    palace_fasta_status st{}, fg{};
+    int64_t n_records = 0;
+    std::unique_ptr<Dev> d_recs;
+    {
+        const size_t sb = palace_fasta_index_scratch_bytes(n);
+        Dev scratch(ctx, sb, "the index's scratch");
+        HIP_OK(palace_fasta_index(ctx, d_text.as<uint8_t>(), n, nullptr, 0, scratch.p, sb, &st));                     // how many records
+        n_records = st.n_records;
+        d_recs = std::make_unique<Dev>(ctx, static_cast<size_t>(n_records) * sizeof(palace_fasta_rec), "the FASTG's index");
+        HIP_OK(palace_fasta_index(ctx, d_text.as<uint8_t>(), n, d_recs->as<palace_fasta_rec>(), n_records, scratch.p, sb, &st));
+    }
+    tr.lap("FASTG indexed");
+    Dev d_name_recs(ctx, static_cast<size_t>(n_records) * sizeof(palace_fasta_rec), "the records' names");
+    Dev d_primed(ctx, static_cast<size_t>(n_records), "the primed bits");
+    HIP_OK(palace_fastg_derive(ctx, d_text.as<uint8_t>(), n, d_recs->as<palace_fasta_rec>(), n_records, d_name_recs.as<palace_fasta_rec>(), d_primed.as<uint8_t>(),
+                               &fg));
+    tr.lap("names derived, text checked");
+    if (fg.error && (!st.error || fg.bad_line < st.bad_line || (fg.bad_line == st.bad_line && fg.error < st.error))) st = fg;
+    if (st.error) throw Failure(graph + ": line " + std::to_string(st.bad_line) + ": " + fault_text(st.error));
+
+    Names names{ctx};
+    Dev d_dup(ctx, static_cast<size_t>(n_records), "the duplicate flags");
+    HIP_OK(palace_fasta_names_create(ctx, d_text.as<uint8_t>(), d_name_recs.as<palace_fasta_rec>(), n_records, d_dup.as<uint8_t>(), &names.t));
+    Dev d_out_off(ctx, static_cast<size_t>(n_records + 1) * sizeof(int64_t), "the records' places");
+    Dev d_out_recs(ctx, fai ? static_cast<size_t>(n_records) * sizeof(palace_fasta_rec) : 0, "the output's index");
+    int64_t n_kept = 0, total = 0;
+    HIP_OK(palace_fastg_plan(ctx, d_name_recs.as<palace_fasta_rec>(), d_dup.as<uint8_t>(), n_records, d_out_off.as<int64_t>(),
+                             fai ? d_out_recs.as<palace_fasta_rec>() : nullptr, &n_kept, &total));
+    tr.lap("names hashed, output planned");
+    {
+        Dev d_out(ctx, static_cast<size_t>(total), "the output is gathered on the device and has no other path: it");
+        HIP_OK(palace_fastg_write(ctx, d_text.as<uint8_t>(), d_name_recs.as<palace_fasta_rec>(), d_primed.as<uint8_t>(), d_out_off.as<int64_t>(), n_records, 0, total,
+                                  d_out.as<uint8_t>()));
+        HIP_OK(palace_sync(ctx));
+        tr.lap("output gathered");
+        to_file(ctx, d_out.as<uint8_t>(), total, out, output);
+    }
+    closer.f = nullptr;
+    if (std::fclose(out) != 0) throw Failure("cannot write " + output);
+    tr.lap("output written");
+    if (!fai) return;
+
+    write_fai(ctx, d_text.as<uint8_t>(), d_out_recs.as<palace_fasta_rec>(), d_dup.as<uint8_t>(), n_records, output + ".fai");
+    Names whole{ctx};
+    Dev d_skip(ctx, static_cast<size_t>(n_records), "the duplicate flags");
+    HIP_OK(palace_fasta_names_create(ctx, d_text.as<uint8_t>(), d_recs->as<palace_fasta_rec>(), n_records, d_skip.as<uint8_t>(), &whole.t));
+    write_fai(ctx, d_text.as<uint8_t>(), d_recs->as<palace_fasta_rec>(), d_skip.as<uint8_t>(), n_records, graph + ".fai");
+    std::vector<uint8_t> skip(static_cast<size_t>(n_records));
+    if (n_records) HIP_OK(palace_d2h(ctx, skip.data(), d_skip.p, skip.size()));
+    size_t k = 0;
+    for (; k < skip.size() && !skip[k]; k++) {}
+    if (k < skip.size()) {                                                   // (rare: the records come to the host only to name them)
+        std::vector<palace_fasta_rec> recs(skip.size());
+        HIP_OK(palace_d2h(ctx, recs.data(), d_recs->p, recs.size() * sizeof(palace_fasta_rec)));
+        for (; k < skip.size(); k++)
+            if (skip[k])
+                std::fprintf(stderr, "split_fastg: warning: %s: sequence name '%.*s' appears again in record %zu: left out of %s.fai\n", graph.c_str(),
+                             static_cast<int>(recs[k].name_len), text.data + recs[k].name_off, k + 1, graph.c_str());
+    }
+    tr.lap("index rows written");
+}
+
+int usage(const char *why)
+{
+    std::fprintf(stderr, "usage: split_fastg [-h] -g GRAPH [-o OUTPUT] [--fai]\nsplit_fastg: error: %s\n", why);
+    return 2;
+}
+
+// the script's default: X.fastg -> X.nodes.fasta (what os.path.splitext makes of the name); "" for any other name, whose default
+// would be the graph itself
+std::string default_output(const std::string &graph)
+{
+    const size_t slash = graph.rfind('/');
+    size_t base = slash == std::string::npos ? 0 : slash + 1;
+    while (base < graph.size() && graph[base] == '.') base++;                // leading dots belong to the root
+    const std::string ext = ".fastg", rest = graph.substr(base);
+    if (rest.size() <= ext.size() || rest.compare(rest.size() - ext.size(), ext.size(), ext) != 0) return "";
+    return graph.substr(0, graph.size() - ext.size()) + ".nodes.fasta";
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    std::string graph, output;
+    bool have_graph = false, have_output = false, fai = false;
+    for (int i = 1; i < argc; i++) {
+        const std::string a = argv[i];
+        auto value = [&](const std::string &shrt, const std::string &lng, std::string *into, bool *have) -> int {      // 1 taken, 0 not this option, -1 no value
+            if (a == shrt || a == lng) {
+                if (i + 1 >= argc) return -1;
+                *into = argv[++i]; *have = true;
+                return 1;
+            }
+            for (const std::string &o : {shrt, lng})
+                if (a.compare(0, o.size() + 1, o + "=") == 0) { *into = a.substr(o.size() + 1); *have = true; return 1; }
+            return 0;
+        };
+        if (a == "--fai") { fai = true; continue; }
+        int r = value("-g", "--graph", &graph, &have_graph);
+        if (r == 0) r = value("-o", "--output", &output, &have_output);
+        if (r < 0) return usage(("argument " + a + ": expected one argument").c_str());
+        if (r == 0) return usage(("unrecognized arguments: " + a).c_str());
+    }
+    if (!have_graph) return usage("the following arguments are required: -g/--graph");
+    if (!have_output || output.empty()) {                                    // (the script takes an empty -o for none)
+        output = default_output(graph);
+        if (output.empty()) return usage("without -o the graph has to be named X.fastg (the output is then X.nodes.fasta)");
+    }
+    palace_host::FastExit fast_exit = palace_host::fast_exit_begin();   // from here on this is the worker process (fast_exit.hpp)
+    const int device = palace_host::pick_device();                       // PALACE_DEVICE (device_pick.hpp): before anything touches HIP
+    palace_host::Trace tr("split_fastg");
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
+        std::fprintf(stderr, "split_fastg: no GPU device to work on (%s); there is no CPU path\n", palace_last_error());
+        return 1;
+    }
+    tr.lap("device up");
+    try {
+        run(ctx, graph, output, fai, tr);
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "split_fastg: %s\n", e.what());
+        return 1;
+    }
+    fast_exit.done(0);          // outputs are complete and closed: the caller goes on, the teardown happens behind it
+}
