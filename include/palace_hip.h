@@ -908,6 +908,81 @@ int palace_fai_rows_plan(palace_ctx *ctx, const palace_fasta_rec *d_recs, const 
 int palace_fai_rows_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records,
                           const int64_t *d_row_off, uint8_t *d_out);
 
+/* ---- bamsort: a BAM coordinate-sorted and indexed where its inflated stream lies (the rules: DESIGN.md 8) --------------------- */
+
+/* One sort key per record of the stream (d_starts as palace_bam_walk leaves them): t << 33 | uint32(pos + 1) << 1 | reverse bit,
+ * t = n_ref for refID = -1, else refID -- contig order with the records without a contig last, then position with pos = -1 first,
+ * then forward before reverse (csrc/bam_record.hpp: sort_key).  A record with refID < -1, refID >= n_ref or pos < -1 has no key:
+ * such records are counted into *n_bad_out and the smallest ordinal among them goes to *first_bad_out (-1: none).  Waits. */
+int palace_bam_sort_keys(palace_ctx *ctx, const uint8_t *d_stream, int64_t total, const int64_t *d_starts, int64_t n_records,
+                         int32_t n_ref, uint64_t *d_key, int64_t *n_bad_out, int64_t *first_bad_out);
+
+#define PALACE_SORT_TILE 4096              /* T: the keys one workgroup of palace_sort_u64 ranks per pass (256 lanes x 16) */
+
+/* A STABLE sort of n 64-bit keys (n < 2^31) by their low key_bits bits (0 .. 64); bits above key_bits may hold anything and are
+ * IGNORED: keys that agree in the low key_bits bits keep their input order.  d_key comes out sorted (whole keys, the ignored bits
+ * with them), d_perm[k] = the input ordinal of the key now at k (written, not read).  LSD radix sort, ceil(key_bits / 8) passes of
+ * 8 bits (the last one narrower), three launches each: every workgroup ranks a tile of T = PALACE_SORT_TILE keys -- a wave takes
+ * 64 consecutive keys at a time, the lanes with an equal digit find each other with eight ballots and rank themselves by the lanes
+ * below, one lane per digit adds the group to the wave's own counters in LDS (no atomics; 4 KiB per workgroup) -- and leaves its
+ * digit counts; one workgroup scans the counts digit-major; the tiles are ranked again and scattered.  The result depends neither
+ * on key_bits being tight nor on T.  d_scratch: palace_sort_u64_scratch_bytes(n) bytes, 256-byte aligned.  Enqueues only. */
+size_t palace_sort_u64_scratch_bytes(int64_t n);
+int palace_sort_u64(palace_ctx *ctx, uint64_t *d_key, uint32_t *d_perm, int64_t n, int32_t key_bits, void *d_scratch,
+                    size_t scratch_bytes);
+
+/* The layout of the sorted stream: d_out_off[k] (n_records + 1 entries) = head_bytes + the bytes (4 + block_size each) of the
+ * records d_perm[0 .. k), the last entry the stream's length, also in *out_bytes_out; d_out_starts (may be null): d_out_off[k] + 4,
+ * the sorted stream's record starts as palace_bam_walk would leave them.  Waits for the stream. */
+int palace_bam_gather_plan(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d_starts, const uint32_t *d_perm, int64_t n_records,
+                           int64_t head_bytes, int64_t *d_out_off, int64_t *d_out_starts, int64_t *out_bytes_out);
+/* Record d_perm[k]'s bytes, block_size word included, copied unchanged to d_out + d_out_off[k] for every k: bytes
+ * [d_out_off[0], d_out_off[n_records]) of d_out (16-byte aligned; out_bytes = d_out_off[n_records] as the plan returned it) are
+ * written and no others.  Output-driven: a lane owns 16 aligned bytes of d_out and finds its record in d_out_off, the records of a
+ * tile's first and last byte are searched once per tile; source and destination have no alignment to each other.  Enqueues only. */
+int palace_bam_gather_write(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d_starts, const uint32_t *d_perm,
+                            const int64_t *d_out_off, int64_t n_records, int64_t out_bytes, uint8_t *d_out);
+
+/* What a .bai (SAM specification 5.2) files each record of a coordinate-sorted stream under.  refID < 0: d_ref = -1, the record is
+ * not indexed and counted into n_no_coor.  Else beg = pos, end = pos + the reference bases of the CIGAR the record really has (M, D,
+ * N, =, X; the CG tag's behind a placeholder), pos + 1 for flag 0x4, no ops or no reference bases; d_bin = reg2bin(beg, end), the
+ * record's own bin field is not looked at; d_win_beg / d_win_end = beg >> 14, (end - 1) >> 14; d_unmapped = flag 0x4.  n_bad /
+ * first_bad: the records a .bai cannot hold (refID >= n_ref or < -1, pos < 0 with a refID, end > 2^29) and the first one's
+ * ordinal (-1: none); first_unsorted: the first ordinal whose sort key is smaller than its predecessor's (-1: the stream is
+ * coordinate-sorted).  Waits for the stream. */
+typedef struct {
+    int64_t n_bad, first_bad, first_unsorted, n_no_coor;
+} palace_bai_status;
+int palace_bai_records(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d_starts, int64_t n_records, int32_t n_ref,
+                       int32_t *d_ref, int32_t *d_bin, int32_t *d_win_beg, int32_t *d_win_end, uint8_t *d_unmapped,
+                       palace_bai_status *status_out);
+
+/* The chunks: a run is a maximal stretch of consecutive records with equal (d_ref, d_bin); *n_runs_out = the number of runs.
+ * Counted first, written second: with cap >= that number the runs are listed ordered by (refID, bin, file order) -- the unplaced
+ * records' runs, d_chunk_ref = -1, last -- each as refID, bin, the stream offset of its first record's block_size word and the
+ * offset behind its last record (four arrays of cap entries).  The run heads are compacted by a scan and ordered with
+ * palace_sort_u64.  Temporaries come from the context's workspace.  Waits for the stream. */
+int palace_bai_chunks(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d_starts, const int32_t *d_ref, const int32_t *d_bin,
+                      int64_t n_records, int32_t n_ref, int32_t *d_chunk_ref, int32_t *d_chunk_bin, int64_t *d_chunk_beg,
+                      int64_t *d_chunk_end, int64_t cap, int64_t *n_runs_out);
+
+/* The linear index and the pseudo-bin's numbers.  Without d_lin: d_n_intv[t] = 1 + the largest d_win_end of reference t's records
+ * (0 without records) and d_ref_stat, four arrays of n_ref entries one behind the other: records with flag 0x4 clear, records with
+ * it set, the stream offset of the first record's block_size word, the offset behind the last record (the last two undefined for
+ * a reference without records).  With d_lin (n_lin entries) and d_lin_off (n_ref + 1 entries, the exclusive sums of d_n_intv, the
+ * last one n_lin): d_lin[d_lin_off[t] + w] = the smallest record start (block_size word) among t's records with d_win_beg <= w <=
+ * d_win_end; a window no record touches takes the next touched window's value.  Enqueues only. */
+int palace_bai_linear(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d_starts, const int32_t *d_ref, const int32_t *d_win_beg,
+                      const int32_t *d_win_end, const uint8_t *d_unmapped, int64_t n_records, int32_t n_ref, int32_t *d_n_intv,
+                      int64_t *d_ref_stat, const int64_t *d_lin_off, int64_t n_lin, int64_t *d_lin);
+
+/* Stream offsets to BGZF virtual offsets: member m holds the stream bytes from d_member_u[m] and lies at file offset d_member_c[m]
+ * (n_members >= 1 entries, d_member_u ascending; the last entry stands for the stream's end: the EOF member, or the file's end
+ * where there is none).  d_voff[k] = c_m << 16 | (d_u[k] - u_m) for the LAST m with u_m <= d_u[k]: an offset on a member boundary
+ * belongs to the member that starts there.  An offset outside [u_0, u_last] gives ~0.  Enqueues only. */
+int palace_bgzf_voffsets(palace_ctx *ctx, const int64_t *d_u, int64_t n, const int64_t *d_member_u, const int64_t *d_member_c,
+                         int64_t n_members, uint64_t *d_voff);
+
 #ifdef __cplusplus
 }
 #endif

@@ -84,6 +84,14 @@ FASTA_TILE_BYTES = 4096                 # PALACE_FASTA_TILE_BYTES
 PATH_NOTHING, PATH_NOT_FOUND, PATH_REVERSE, PATH_SECOND_TRY = -1, -2, 1, 2
 
 
+class BaiStatus(C.Structure):
+    """palace_bai_status"""
+    _fields_ = [("n_bad", C.c_int64), ("first_bad", C.c_int64), ("first_unsorted", C.c_int64), ("n_no_coor", C.c_int64)]
+
+
+SORT_TILE = 4096        # PALACE_SORT_TILE: the keys one workgroup of palace_sort_u64 ranks per pass
+
+
 class FastaStatus(C.Structure):
     """palace_fasta_status"""
     _fields_ = [("n_records", C.c_int64), ("bad_line", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
@@ -225,6 +233,18 @@ _SIGS = {
     "palace_fai_rows_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "palace_path_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_bam_sort_keys": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "palace_sort_u64_scratch_bytes": [C.c_int64],       # (returns size_t: restype set below)
+    "palace_sort_u64": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t],
+    "palace_bam_gather_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_bam_gather_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_bai_records": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.POINTER(BaiStatus)],
+    "palace_bai_chunks": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                          C.c_int64, C.POINTER(C.c_int64)],
+    "palace_bai_linear": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
+                          C.c_void_p, C.c_int64, C.c_void_p],
+    "palace_bgzf_voffsets": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
 }
 
 
@@ -264,6 +284,7 @@ def lib() -> C.CDLL:
         _LIB.palace_bam_walk_scratch_bytes.restype = C.c_size_t
         _LIB.palace_depth_parse_scratch_bytes.restype = C.c_size_t
         _LIB.palace_fasta_index_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_sort_u64_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -699,6 +720,59 @@ def bam_match_segments(ctx: Ctx, stream: bytes, starts, n_ref: int):
                                                want, C.byref(n)), "palace_bam_match_segments")
         assert n.value == want
         return tuple(b.to_host()[:want].copy() for b in out)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def sort_u64(ctx: Ctx, keys, key_bits: int):
+    """palace_sort_u64 -> (the keys sorted by their low key_bits bits, the permutation: input ordinal of the key at each place)"""
+    k = np.ascontiguousarray(keys, dtype=np.uint64)
+    n = len(k)
+    nscr = int(lib().palace_sort_u64_scratch_bytes(n))
+    bufs = [ctx.upload(k if n else np.zeros(1, np.uint64)), ctx.empty(max(1, n), np.uint32), DevBuf(ctx, max(nscr, 256))]
+    try:
+        _check(lib().palace_sort_u64(ctx.h, bufs[0].ptr, bufs[1].ptr, n, key_bits, bufs[2].ptr, nscr), "palace_sort_u64")
+        return bufs[0].to_host()[:n].copy(), bufs[1].to_host()[:n].copy()
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bam_sort_keys(ctx: Ctx, stream: bytes, starts, n_ref: int):
+    """palace_bam_sort_keys -> (keys uint64, records without a key, the first one's ordinal or -1)"""
+    stream = bytes(stream)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    bufs = [ctx.upload(np.frombuffer(stream, dtype=np.uint8) if stream else np.zeros(1, np.uint8)), ctx.upload(st if len(st) else np.zeros(1, np.int64)),
+            ctx.empty(max(1, len(st)), np.uint64)]
+    n_bad, first_bad = C.c_int64(), C.c_int64()
+    try:
+        _check(lib().palace_bam_sort_keys(ctx.h, bufs[0].ptr, len(stream), bufs[1].ptr, len(st), n_ref, bufs[2].ptr, C.byref(n_bad), C.byref(first_bad)),
+               "palace_bam_sort_keys")
+        return bufs[2].to_host()[:len(st)].copy(), int(n_bad.value), int(first_bad.value)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bam_gather(ctx: Ctx, stream: bytes, starts, perm, head: bytes):
+    """palace_bam_gather_plan and palace_bam_gather_write -> (output offsets int64 (n + 1), the sorted stream's record starts, the output
+    stream with `head` in front and 0xAA where nothing may be written: 16 guard bytes behind it)"""
+    stream = bytes(stream)
+    st, pm = np.ascontiguousarray(starts, dtype=np.int64), np.ascontiguousarray(perm, dtype=np.uint32)
+    n = len(st)
+    bufs = [ctx.upload(np.frombuffer(stream, dtype=np.uint8) if stream else np.zeros(1, np.uint8)), ctx.upload(st if n else np.zeros(1, np.int64)),
+            ctx.upload(pm if n else np.zeros(1, np.uint32)), ctx.empty(n + 1, np.int64), ctx.empty(max(1, n), np.int64)]
+    total = C.c_int64()
+    try:
+        _check(lib().palace_bam_gather_plan(ctx.h, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, n, len(head), bufs[3].ptr, bufs[4].ptr, C.byref(total)),
+               "palace_bam_gather_plan")
+        image = np.full(total.value + 16, 0xAA, np.uint8)
+        image[:len(head)] = np.frombuffer(head, dtype=np.uint8)
+        d_out = ctx.upload(image)
+        bufs.append(d_out)
+        _check(lib().palace_bam_gather_write(ctx.h, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, bufs[3].ptr, n, total.value, d_out.ptr), "palace_bam_gather_write")
+        return bufs[3].to_host().copy(), bufs[4].to_host()[:n].copy(), d_out.to_host().tobytes()
     finally:
         for b in bufs:
             b.free()

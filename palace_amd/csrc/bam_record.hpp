@@ -157,6 +157,49 @@ PALACE_BAM_FN void record_segments(const uint8_t *d, int64_t s, int32_t n_ref, F
     record_ops(d, s, record_cigar(d, s, s + static_cast<int64_t>(ld32(d, s - 4))), true, f);
 }
 
+// The coordinate-sort key of a record in a file of n_ref targets (the order of samtools' bam1_cmp_core): the contig, records without
+// one last; then pos + 1, so that pos = -1 comes first; then the strand bit, forward first.  31 + 32 + 1 bits.  sort_key_ok: the
+// record has a key at all (refID in [-1, n_ref), pos >= -1).
+PALACE_BAM_FN bool sort_key_ok(const uint8_t *d, int64_t s, int32_t n_ref)
+{
+    const int32_t tid = static_cast<int32_t>(ld32(d, s)), pos = static_cast<int32_t>(ld32(d, s + 4));
+    return tid >= -1 && tid < n_ref && pos >= -1;
+}
+PALACE_BAM_FN uint64_t sort_key(const uint8_t *d, int64_t s, int32_t n_ref)
+{
+    const int32_t tid = static_cast<int32_t>(ld32(d, s));
+    const uint64_t t = static_cast<uint32_t>(tid < 0 ? n_ref : tid);
+    return t << 33 | static_cast<uint64_t>(ld32(d, s + 4) + 1u) << 1 | (ld16(d, s + 14) >> 4 & 1u);
+}
+
+// reg2bin of the SAM specification 5.3 for the interval [beg, end), 0 <= beg < end <= 2^29
+PALACE_BAM_FN uint32_t reg2bin(int64_t beg, int64_t end)
+{
+    --end;
+    if (beg >> 14 == end >> 14) return static_cast<uint32_t>(((1 << 15) - 1) / 7 + (beg >> 14));
+    if (beg >> 17 == end >> 17) return static_cast<uint32_t>(((1 << 12) - 1) / 7 + (beg >> 17));
+    if (beg >> 20 == end >> 20) return static_cast<uint32_t>(((1 << 9) - 1) / 7 + (beg >> 20));
+    if (beg >> 23 == end >> 23) return static_cast<uint32_t>(((1 << 6) - 1) / 7 + (beg >> 23));
+    if (beg >> 26 == end >> 26) return static_cast<uint32_t>(((1 << 3) - 1) / 7 + (beg >> 26));
+    return 0;
+}
+
+// The interval a .bai files a record under: [pos, pos + ref_len) of the CIGAR the record really has (record_cigar: the CG tag's
+// N already carries the placeholder's span), one base for an unmapped record (flag 0x4), one without ops or without reference bases.
+// ok: a .bai can hold it (pos >= 0, end <= 2^29).  Asked only of records with refID >= 0.
+struct BaiSpan { int64_t beg, end; bool ok; };
+PALACE_BAM_FN BaiSpan bai_span(const uint8_t *d, int64_t s)
+{
+    const int64_t beg = static_cast<int32_t>(ld32(d, s + 4));
+    int64_t len = 0;
+    if (!(ld16(d, s + 14) & 4u)) {
+        const RecCigar c = record_cigar(d, s, s + static_cast<int64_t>(ld32(d, s - 4)));
+        len = record_ops(d, s, c, false, [](int32_t, int32_t, int32_t) {}).ref_len;
+    }
+    const int64_t end = beg + (len > 0 ? len : 1);
+    return BaiSpan{beg, end, beg >= 0 && end <= (1ll << 29)};
+}
+
 // the C-string view of the read name (:651): up to the first NUL inside l_read_name, else l_read_name - 1 bytes (l_read_name >= 1: the walk)
 PALACE_BAM_FN int64_t name_len(const uint8_t *d, int64_t s)
 {

@@ -1,0 +1,322 @@
+// bamsort -- the two commands between `bwa` and generateGraph that the driver gives to samtools (palace:425-433):
+//     $SAMTOOLS sort -@ "$threads" tmp.bam -O BAM -o first_bam ; $SAMTOOLS index first_bam
+// as   bamsort -@ "$threads" tmp.bam -O BAM -o first_bam --bai      (the argument list of `samtools sort`, in any order, + --bai)
+// or   bamsort ... -o first_bam ; bamsort --index first_bam [<out.bai>]
+// The BAM is inflated, CRC-checked and walked on the device (bam_stream_device.hpp), its records are keyed (palace_bam_sort_keys),
+// the keys sorted with a stable radix sort (palace_sort_u64), the records gathered behind the rewritten header
+// (palace_bam_gather_plan / _write), the stream cut into members of 0xff00 bytes that the device coder deflates (palace_crc32_members,
+// palace_bgzf_deflate, palace_bgzf_compact; the batch loop of depthgz_device.hpp), and the .bai computed from the stream that was
+// written (bai.hpp).  The host rewrites the header and lays out the index, nothing else.  The rules are DESIGN.md 8.
+// Needs a device: there is no host path behind it.  On any failure no output file is left.
+//   -@ <n>                           host threads that inflate the header's members; otherwise ignored
+//   PALACE_DEVICE, PALACE_TRACE      as in the other tools
+//   PALACE_OPT_BAMSORT_BATCH=<n>     members per deflate batch (tests); PALACE_OPT_BAM_BATCH / PALACE_OPT_BAM_CHUNK on the input side
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <chrono>
+#include <iostream>
+
+#include "bai.hpp"
+#include "bam_stream_device.hpp"
+#include "device_pick.hpp"
+
+using namespace palace_host;
+
+namespace {
+
+int usage()
+{
+    std::cerr << "Usage: bamsort [-@ <threads>] [-O BAM] -o <out.bam> [--bai] <in.bam>   (coordinate sort; --bai also writes <out.bam>.bai)\n"
+              << "       bamsort --index <sorted.bam> [<out.bai>]                       (default <sorted.bam>.bai)\n"
+              << "no other option of `samtools sort` / `samtools index` is taken\n";
+    return 1;
+}
+
+// members per deflate batch: 8192, as the depth file's writer; PALACE_OPT_BAMSORT_BATCH=<members> for tests
+size_t bamsort_batch_members()
+{
+    const char *e = std::getenv("PALACE_OPT_BAMSORT_BATCH");
+    const long v = e ? std::atol(e) : 0;
+    return v > 0 ? static_cast<size_t>(std::min<long>(v, 8192)) : 8192;
+}
+
+int bits_of(uint32_t v) { int b = 0; while (v) { b++; v >>= 1; } return b; }
+
+// The header [0, first) of the input stream as the output's: the text's @HD line says SO:coordinate, nothing else changes.
+std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &in)
+{
+    uint32_t l_text;
+    std::memcpy(&l_text, in.data() + 4, 4);
+    std::string text(reinterpret_cast<const char *>(in.data()) + 8, l_text);
+    if (text.rfind("@HD\t", 0) == 0) {
+        const size_t eol = std::min(text.find('\n'), text.size());
+        size_t so = std::string::npos;
+        for (size_t f = 3; f < eol;) {                                       // text[f] is the TAB in front of a field
+            const size_t b = f + 1, e = std::min(text.find('\t', b), eol);
+            if (e - b >= 3 && text.compare(b, 3, "SO:") == 0) { so = b; break; }
+            f = e;
+        }
+        if (so == std::string::npos) text.insert(eol, "\tSO:coordinate");
+        else text.replace(so + 3, std::min(text.find('\t', so), eol) - (so + 3), "coordinate");
+    } else
+        text.insert(0, "@HD\tVN:1.6\tSO:coordinate\n");
+    std::vector<uint8_t> out(in.begin(), in.begin() + 4);
+    const uint32_t n = static_cast<uint32_t>(text.size());
+    for (int k = 0; k < 4; k++) out.push_back(static_cast<uint8_t>(n >> (8 * k)));
+    out.insert(out.end(), text.begin(), text.end());
+    out.insert(out.end(), in.begin() + 8 + l_text, in.end());
+    return out;
+}
+
+struct Laps {
+    using clk = std::chrono::steady_clock;
+    palace_ctx *ctx;
+    bool on;
+    clk::time_point t0 = clk::now();
+    double keys = 0, sort = 0, gather = 0, deflate = 0, copy_write = 0, index = 0;
+    void restart() { t0 = clk::now(); }
+    void lap(double *acc)
+    {
+        if (!on) return;
+        if (palace_sync(ctx)) throw std::runtime_error(std::string("palace_sync: ") + palace_last_error());
+        const auto t1 = clk::now();
+        *acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
+        t0 = t1;
+    }
+};
+
+void ck(int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); }
+
+void require_whole(const DeviceBamStream &st)
+{
+    if (st.stop != st.total) throw std::runtime_error("malformed record at offset " + std::to_string(st.stop) + " (the stream has " + std::to_string(st.total) + " bytes)");
+    if (st.n_records > 0x7fffffffll) throw std::runtime_error("more than 2^31 - 1 records");
+}
+
+int main_sort(const std::string &in, const std::string &out, bool bai, int threads)
+{
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamsort: " << palace_last_error() << "\n"; return 1; }
+    int code = 0;
+    bool out_made = false, bai_made = false;
+    FILE *f = nullptr;
+    try {
+        const bool trace = std::getenv("PALACE_TRACE") != nullptr;
+        Laps laps{ctx, trace};
+        BamDeviceTimes bt;
+        DeviceBamStream st;
+        try {
+            load_bam_stream_device(ctx, in, threads, st, trace ? &bt : nullptr);
+            require_whole(st);
+        } catch (const BamDeviceNoRoom &e) { throw;
+        } catch (const std::exception &e) { throw std::runtime_error(in + ": " + e.what()); }
+        const size_t n = static_cast<size_t>(st.n_records);
+        BamsortDevice dev(ctx);
+
+        // the header: the one part the host touches
+        std::vector<uint8_t> head(static_cast<size_t>(st.first));
+        ck(palace_d2h(ctx, head.data(), st.d_stream, head.size()), "palace_d2h");
+        const std::vector<uint8_t> new_head = rewrite_header(head);
+
+        laps.restart();
+        uint64_t *d_key = dev.array<uint64_t>(n, "the sort keys");
+        int64_t n_bad = 0, first_bad = -1;
+        ck(palace_bam_sort_keys(ctx, st.d_stream, st.total, st.d_starts, st.n_records, st.n_ref, d_key, &n_bad, &first_bad), "palace_bam_sort_keys");
+        if (n_bad)
+            throw std::runtime_error(in + ": record " + std::to_string(first_bad) + ": refID or pos outside what the header's " + std::to_string(st.n_ref) +
+                                     " targets allow (" + std::to_string(n_bad) + " such records)");
+        laps.lap(&laps.keys);
+        uint32_t *d_perm = dev.array<uint32_t>(n, "the permutation");
+        const size_t sort_bytes = palace_sort_u64_scratch_bytes(st.n_records);
+        void *d_sort = dev.alloc(sort_bytes, "the sort's scratch");
+        ck(palace_sort_u64(ctx, d_key, d_perm, st.n_records, 33 + bits_of(static_cast<uint32_t>(st.n_ref)), d_sort, sort_bytes), "palace_sort_u64");
+        ck(palace_sync(ctx), "palace_sync");
+        laps.lap(&laps.sort);
+        dev.give_back(d_sort);
+        dev.give_back(d_key);
+
+        int64_t *d_out_off = dev.array<int64_t>(n + 1, "the output offsets");
+        int64_t *d_out_starts = bai ? dev.array<int64_t>(n, "the output's record starts") : nullptr;
+        int64_t out_bytes = 0;
+        ck(palace_bam_gather_plan(ctx, st.d_stream, st.d_starts, d_perm, st.n_records, static_cast<int64_t>(new_head.size()), d_out_off, d_out_starts, &out_bytes),
+           "palace_bam_gather_plan");
+        uint8_t *d_out = static_cast<uint8_t *>(dev.alloc(static_cast<size_t>(out_bytes) + 64, "the sorted stream"));
+        ck(palace_h2d(ctx, d_out, new_head.data(), new_head.size()), "palace_h2d");
+        ck(palace_bam_gather_write(ctx, st.d_stream, st.d_starts, d_perm, d_out_off, st.n_records, out_bytes, d_out), "palace_bam_gather_write");
+        ck(palace_sync(ctx), "palace_sync");
+        laps.lap(&laps.gather);
+        st.release();                                                        // the input has been copied
+        dev.give_back(d_perm);
+        dev.give_back(d_out_off);
+
+        // the file: members of 0xff00 bytes, a batch at a time
+        std::vector<int64_t> member_u, member_c;
+        const size_t n_members = (static_cast<size_t>(out_bytes) + kBgzfText - 1) / kBgzfText, batch = std::min(bamsort_batch_members(), std::max<size_t>(1, n_members));
+        uint64_t file_bytes = 0;
+        f = std::fopen(out.c_str(), "wb");
+        if (!f) throw std::runtime_error("cannot open " + out + " for writing");
+        out_made = true;
+        {
+            BamsortDevice bd(ctx);
+            uint8_t *d_slots = static_cast<uint8_t *>(bd.alloc(batch * 65536, "a batch of members")), *d_file = static_cast<uint8_t *>(bd.alloc(batch * 65536, "a batch of members"));
+            int64_t *d_off = bd.array<int64_t>(batch, "a batch of members"), *d_moff = bd.array<int64_t>(batch + 1, "a batch of members");
+            int32_t *d_len = bd.array<int32_t>(batch, "a batch of members"), *d_mlen = bd.array<int32_t>(batch, "a batch of members");
+            uint32_t *d_crc = bd.array<uint32_t>(batch, "a batch of members");
+            std::vector<int64_t> off(batch), moff(batch + 1);
+            std::vector<int32_t> lens(batch);
+            for (size_t k = 0; k < batch; k++) off[k] = static_cast<int64_t>(k * kBgzfText);
+            ck(palace_h2d(ctx, d_off, off.data(), batch * 8), "palace_h2d");
+            void *h_file = nullptr;
+            ck(palace_host_alloc(ctx, batch * 65536, &h_file), "palace_host_alloc");
+            struct Pinned { palace_ctx *ctx; void *p; ~Pinned() { palace_host_free(ctx, p); } } pinned{ctx, h_file};
+            for (size_t m0 = 0; m0 < n_members; m0 += batch) {
+                const size_t nm = std::min(batch, n_members - m0);
+                const uint64_t t_beg = m0 * kBgzfText, t_end = std::min<uint64_t>(static_cast<uint64_t>(out_bytes), (m0 + nm) * kBgzfText);
+                for (size_t k = 0; k < nm; k++) lens[k] = static_cast<int32_t>(std::min<uint64_t>(kBgzfText, t_end - (t_beg + k * kBgzfText)));
+                laps.restart();
+                ck(palace_h2d(ctx, d_len, lens.data(), nm * 4), "palace_h2d");
+                const uint8_t *d_text = d_out + t_beg;
+                ck(palace_crc32_members(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc), "palace_crc32_members");
+                ck(palace_bgzf_deflate(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc, d_slots, d_mlen), "palace_bgzf_deflate");
+                ck(palace_bgzf_compact(ctx, d_slots, static_cast<int64_t>(nm), d_mlen, d_file, d_moff), "palace_bgzf_compact");
+                laps.lap(&laps.deflate);
+                ck(palace_d2h(ctx, moff.data(), d_moff, (nm + 1) * 8), "palace_d2h");
+                const size_t bytes = static_cast<size_t>(moff[nm]);
+                ck(palace_d2h(ctx, h_file, d_file, bytes), "palace_d2h");
+                for (size_t k = 0; k < nm; k++) {
+                    member_u.push_back(static_cast<int64_t>((m0 + k) * kBgzfText));
+                    member_c.push_back(static_cast<int64_t>(file_bytes) + moff[k]);
+                }
+                if (std::fwrite(h_file, 1, bytes, f) != bytes) throw std::runtime_error("write failed: " + out);
+                file_bytes += bytes;
+                laps.lap(&laps.copy_write);
+            }
+        }
+        member_u.push_back(out_bytes);                                       // the EOF member stands for the stream's end
+        member_c.push_back(static_cast<int64_t>(file_bytes));
+        if (std::fwrite(bgzf_eof_member(), 1, 28, f) != 28) throw std::runtime_error("write failed: " + out);
+        file_bytes += 28;
+        const int rc_close = std::fclose(f);
+        f = nullptr;
+        if (rc_close != 0) throw std::runtime_error("write failed: " + out);
+        laps.lap(&laps.copy_write);
+
+        if (bai) {
+            laps.restart();
+            bai_made = true;
+            write_bai_device(ctx, out, d_out, d_out_starts, st.n_records, st.n_ref, member_u, member_c, out + ".bai");
+            laps.lap(&laps.index);
+        }
+        if (trace)
+            std::fprintf(stderr, "[bamsort] ms: member index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f | keys %.1f sort %.1f gather %.1f "
+                         "crc+deflate %.1f copy+write %.1f index %.1f; records %lld, stream %lld B -> %lld B, file %llu B, members inflated on the host %lld\n",
+                         bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, laps.keys, laps.sort, laps.gather, laps.deflate, laps.copy_write, laps.index,
+                         static_cast<long long>(st.n_records), static_cast<long long>(st.total), static_cast<long long>(out_bytes),
+                         static_cast<unsigned long long>(file_bytes), static_cast<long long>(st.host_inflated));
+    } catch (const std::exception &e) {
+        std::cerr << "bamsort: " << e.what() << "\n";
+        code = 1;
+        if (f) std::fclose(f);
+        if (out_made) std::remove(out.c_str());
+        if (bai_made) std::remove((out + ".bai").c_str());
+    }
+    palace_ctx_destroy(ctx);
+    return code;
+}
+
+int main_index(const std::string &bam, const std::string &bai_path, int threads)
+{
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamsort: " << palace_last_error() << "\n"; return 1; }
+    int code = 0;
+    try {
+        const bool trace = std::getenv("PALACE_TRACE") != nullptr;
+        Laps laps{ctx, trace};
+        BamDeviceTimes bt;
+        DeviceBamStream st;
+        std::vector<int64_t> member_u, member_c;
+        try {
+            load_bam_stream_device(ctx, bam, threads, st, trace ? &bt : nullptr);
+            require_whole(st);
+            // the file's own member table (the loader has checked it)
+            const int fd = ::open(bam.c_str(), O_RDONLY);
+            struct stat sb;
+            if (fd < 0 || ::fstat(fd, &sb) != 0) { if (fd >= 0) ::close(fd); throw std::runtime_error("Failed to open BAM"); }
+            const size_t size = static_cast<size_t>(sb.st_size);
+            void *m = size ? ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
+            ::close(fd);
+            if (size && m == MAP_FAILED) throw std::runtime_error("Failed to read BAM");
+            struct Unmap { void *p; size_t n; ~Unmap() { if (p) ::munmap(p, n); } } unmap{m, size};
+            size_t total = 0;
+            BgzfWalkEnd end;
+            const std::vector<BgzfMember> mem = bgzf_members(static_cast<const uint8_t *>(m), size, &total, &end);
+            for (size_t i = 0; i < mem.size(); i++) {
+                member_u.push_back(static_cast<int64_t>(mem[i].out_off));
+                member_c.push_back(static_cast<int64_t>(i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : 0));
+            }
+            if (mem.empty() || mem.back().out_len != 0) {                    // no EOF member: the file's end stands for the stream's
+                member_u.push_back(static_cast<int64_t>(total));
+                member_c.push_back(static_cast<int64_t>(end.offset));
+            }
+        } catch (const BamDeviceNoRoom &e) { throw;
+        } catch (const std::exception &e) { throw std::runtime_error(bam + ": " + e.what()); }
+        laps.restart();
+        write_bai_device(ctx, bam, st.d_stream, st.d_starts, st.n_records, st.n_ref, member_u, member_c, bai_path);
+        laps.lap(&laps.index);
+        if (trace)
+            std::fprintf(stderr, "[bamsort] index ms: member index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f | index %.1f; records %lld, stream %lld B\n",
+                         bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, laps.index, static_cast<long long>(st.n_records), static_cast<long long>(st.total));
+    } catch (const std::exception &e) {
+        std::cerr << "bamsort: " << e.what() << "\n";
+        code = 1;
+    }
+    palace_ctx_destroy(ctx);
+    return code;
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    std::vector<std::string> a(argv + 1, argv + argc);
+    int threads = 1;
+    if (std::find(a.begin(), a.end(), "--index") != a.end()) {
+        std::vector<std::string> pos;
+        for (const std::string &s : a) {
+            if (s == "--index") continue;
+            if (s.size() > 1 && s[0] == '-') return usage();
+            pos.push_back(s);
+        }
+        if (pos.empty() || pos.size() > 2) return usage();
+        return main_index(pos[0], pos.size() == 2 ? pos[1] : pos[0] + ".bai", 16);
+    }
+    std::string in, out, fmt = "BAM";
+    bool bai = false, have_in = false;
+    for (size_t i = 0; i < a.size(); i++) {
+        const std::string &s = a[i];
+        auto value = [&](std::string *v) {                                   // `-x value` or `-xvalue`
+            if (s.size() > 2) { *v = s.substr(2); return true; }
+            if (i + 1 >= a.size()) return false;
+            *v = a[++i];
+            return true;
+        };
+        if (s == "--bai") bai = true;
+        else if (s.rfind("-@", 0) == 0) {
+            std::string v;
+            if (!value(&v) || v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 6) return usage();
+            threads = std::max(1, std::atoi(v.c_str()));
+        } else if (s.rfind("-O", 0) == 0) {
+            if (!value(&fmt)) return usage();
+        } else if (s.rfind("-o", 0) == 0) {
+            if (!value(&out) || out.empty()) return usage();
+        } else if (s.size() > 1 && s[0] == '-') return usage();
+        else if (have_in) return usage();
+        else { in = s; have_in = true; }
+    }
+    if (!have_in || out.empty()) return usage();
+    if (fmt != "BAM" && fmt != "bam") { std::cerr << "bamsort: -O " << fmt << ": only BAM is written\n"; return 1; }
+    return main_sort(in, out, bai, std::min(threads, 64));
+}
