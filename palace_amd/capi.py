@@ -577,6 +577,141 @@ def depth_parse_windows(ctx: Ctx, text: bytes, cuts=(), runs_cap: int | None = N
             buf.free()
 
 
+_FILL64 = 0xA5A5A5A5A5A5A5A5
+
+
+def _depth_inputs(ctx: Ctx, tlen, segs, tbase_entries: int):
+    """the device arrays the depth entry points share: tlen (int32), tbase (int64, the first `tbase_entries` exclusive prefixes) and the
+    three segment columns exactly as given -- nothing filtered, nothing sorted -> (buffers, n_targets, total_len, n_segs)"""
+    tl = np.ascontiguousarray(tlen, dtype=np.int32).reshape(-1)
+    tbase = np.concatenate([np.zeros(1, np.int64), np.cumsum(tl, dtype=np.int64)])
+    if isinstance(segs, np.ndarray) and segs.ndim == 2:
+        assert segs.shape[1] == 3
+        segs = (segs[:, 0], segs[:, 1], segs[:, 2])
+    cols = [np.asarray(c) for c in segs]
+    assert len(cols) == 3 and all(c.ndim == 1 and len(c) == len(cols[0]) and c.dtype == np.int32 for c in cols), "segments are three int32 columns"
+    bufs = [ctx.upload(c) for c in cols] + [ctx.upload(tl), ctx.upload(tbase[:tbase_entries])]
+    return bufs, len(tl), int(tbase[-1]), len(cols[0])
+
+
+def depth_sum_covered(ctx: Ctx, tlen, segs):
+    """palace_depth_sum_covered -> (sum, covered).  segs: three int32 arrays (tid, pos, len) or one (n, 3) array; d_tbase has exactly
+    n_targets entries, as the header says."""
+    bufs, n_targets, total_len, n = _depth_inputs(ctx, tlen, segs, len(np.atleast_1d(tlen)))
+    s, c = C.c_uint64(_FILL64), C.c_uint64(_FILL64)
+    try:
+        _check(lib().palace_depth_sum_covered(ctx.h, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, n_targets, bufs[3].ptr, bufs[4].ptr, total_len,
+                                              C.byref(s), C.byref(c)), "palace_depth_sum_covered")
+        return int(s.value), int(c.value)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def depth_per_contig(ctx: Ctx, tlen, segs):
+    """palace_depth_per_contig -> (sum, covered, contig_sum[], contig_covered[]).  The two device arrays hold a non-zero pattern
+    before the call, so an entry the call leaves alone shows."""
+    bufs, n_targets, total_len, n = _depth_inputs(ctx, tlen, segs, len(np.atleast_1d(tlen)))
+    bufs += [ctx.upload(np.full(max(n_targets, 1), _FILL64, np.uint64)) for _ in range(2)]
+    s, c = C.c_uint64(_FILL64), C.c_uint64(_FILL64)
+    try:
+        _check(lib().palace_depth_per_contig(ctx.h, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, n_targets, bufs[3].ptr, bufs[4].ptr, total_len,
+                                             C.byref(s), C.byref(c), bufs[5].ptr, bufs[6].ptr), "palace_depth_per_contig")
+        ctx.sync()
+        return int(s.value), int(c.value), bufs[5].to_host()[:n_targets].copy(), bufs[6].to_host()[:n_targets].copy()
+    finally:
+        for b in bufs:
+            b.free()
+
+
+class DepthText:
+    """palace_depth_text_create and what is asked of its handle.  tlen, tbase (n_targets + 1 entries), the names blob and the name
+    offsets stay on the device until close(), as the header demands; the segments are passed as given and freed after create."""
+
+    def __init__(self, ctx: Ctx, tlen, names, segs):
+        self.ctx, self.h, self._keep = ctx, C.c_void_p(), []
+        names = [bytes(x) for x in names]
+        assert len(names) == len(np.atleast_1d(tlen))
+        name_off = np.concatenate([np.zeros(1, np.int64), np.cumsum([len(x) for x in names], dtype=np.int64)])
+        bufs, self.n_targets, self.total_len, n = _depth_inputs(ctx, tlen, segs, len(names) + 1)
+        self._keep = bufs[3:] + [ctx.upload(np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)), ctx.upload(name_off)]
+        tb, ln, sm = C.c_uint64(_FILL64), C.c_uint64(_FILL64), C.c_uint64(_FILL64)
+        try:
+            _check(lib().palace_depth_text_create(ctx.h, n, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, self.n_targets, self._keep[0].ptr, self._keep[1].ptr,
+                                                  self.total_len, self._keep[2].ptr, self._keep[3].ptr, C.byref(self.h), C.byref(tb), C.byref(ln),
+                                                  C.byref(sm)), "palace_depth_text_create")
+        except PalaceError:
+            self.close()
+            raise
+        finally:
+            for b in bufs[:3]:
+                b.free()
+        self.text_bytes, self.lines, self.sum = int(tb.value), int(ln.value), int(sm.value)
+
+    def emit_many(self, ranges, guard: int = 64):
+        """every [begin, end) of `ranges` through palace_depth_text_emit, each into a slot of its own of device buffers filled with
+        0xA5, `guard` such bytes in front of and behind its end - begin bytes -> [(bytes, guards untouched)].  A refused range raises
+        PalaceError; its `untouched` says whether every byte of the buffer is still as it was."""
+        ranges = [(int(a), int(b)) for a, b in ranges]
+        out, k = [], 0
+        while k < len(ranges):
+            slots, at = [], 0
+            while k + len(slots) < len(ranges) and (not slots or at < (32 << 20)):
+                a, b = ranges[k + len(slots)]
+                slots.append(at + guard)
+                at += guard + max(b - a, 0) + guard
+            d_out = self.ctx.upload(np.full(max(at, 1), 0xA5, np.uint8))
+            try:
+                for (a, b), slot in zip(ranges[k:], slots):
+                    rc = lib().palace_depth_text_emit(self.ctx.h, self.h, C.c_uint64(a & (2 ** 64 - 1)), C.c_uint64(b & (2 ** 64 - 1)), d_out.ptr + slot)
+                    if rc != 0:
+                        err = PalaceError(f"palace_depth_text_emit [{a}, {b}) -> {rc}: {lib().palace_last_error().decode()}")
+                        self.ctx.sync()
+                        err.untouched = bool((d_out.to_host() == 0xA5).all())
+                        raise err
+                self.ctx.sync()
+                got = d_out.to_host()
+            finally:
+                d_out.free()
+            ends = [s + max(b - a, 0) for (a, b), s in zip(ranges[k:], slots)]
+            for s, e, nxt in zip(slots, ends, slots[1:] + [at + guard]):
+                out.append((got[s:e].tobytes(), bool((got[s - guard:s] == 0xA5).all() and (got[e:nxt - guard] == 0xA5).all())))
+            k += len(slots)
+        return out
+
+    def emit(self, begin: int, end: int, guard: int = 64):
+        """bytes [begin, end) of the text -> (bytes, whether the `guard` bytes on both sides of them are untouched)"""
+        return self.emit_many([(begin, end)], guard)[0]
+
+    def windows(self, beg, end):
+        """palace_depth_text_windows -> (text_beg[], text_end[], lines[]) of the ranges [beg[w], end[w]) of global positions"""
+        wb, we = np.ascontiguousarray(beg, dtype=np.int64), np.ascontiguousarray(end, dtype=np.int64)
+        assert wb.shape == we.shape and wb.ndim == 1
+        n = len(wb)
+        bufs = [self.ctx.upload(wb), self.ctx.upload(we)] + [self.ctx.upload(np.full(max(n, 1), _FILL64, np.uint64)) for _ in range(3)]
+        try:
+            _check(lib().palace_depth_text_windows(self.ctx.h, self.h, n, *(b.ptr for b in bufs)), "palace_depth_text_windows")
+            self.ctx.sync()
+            return tuple(b.to_host()[:n].copy() for b in bufs[2:])
+        finally:
+            for b in bufs:
+                b.free()
+
+    def close(self):
+        if self.h:
+            _check(lib().palace_depth_text_destroy(self.ctx.h, self.h), "palace_depth_text_destroy")
+            self.h = C.c_void_p()
+        for b in self._keep:
+            b.free()
+        self._keep = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def fastq_scratch_bytes(max_window: int) -> int:
     return int(lib().palace_fastq_scratch_bytes(max_window))
 
