@@ -983,6 +983,67 @@ int palace_bai_linear(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d
 int palace_bgzf_voffsets(palace_ctx *ctx, const int64_t *d_u, int64_t n, const int64_t *d_member_u, const int64_t *d_member_c,
                          int64_t n_members, uint64_t *d_voff);
 
+/* ---- samview: SAM text encoded as BAM records where the text lies (the rules: DESIGN.md 8, csrc/sam_line.hpp) ------------------- */
+
+/* What is wrong with a SAM text.  Parity with samtools is UNPINNED: htslib is not at hand, these rules are the behaviour. */
+#define PALACE_SAM_EAT 1          /* a line that begins with '@' behind the first alignment line */
+#define PALACE_SAM_EEMPTY 2       /* an empty line */
+#define PALACE_SAM_EFIELDS 3      /* fewer than 11 TAB-separated fields */
+#define PALACE_SAM_EQNAME 4       /* QNAME: not 1 .. 254 bytes of '!' .. '~' */
+#define PALACE_SAM_EFLAG 5        /* FLAG: not a decimal in 0 .. 65535 */
+#define PALACE_SAM_ERNAME 6       /* RNAME: neither '*' nor a target of the header */
+#define PALACE_SAM_EPOS 7         /* POS: not a decimal in 0 .. 2^31 - 1 */
+#define PALACE_SAM_EMAPQ 8        /* MAPQ: not a decimal in 0 .. 255 */
+#define PALACE_SAM_ECIGAR 9       /* CIGAR: neither '*' nor ([0-9]+[MIDNSHP=X])+, a length of 2^28 or more, more than 65535 ops */
+#define PALACE_SAM_ERNEXT 10      /* RNEXT: none of '*', '=' and a target of the header */
+#define PALACE_SAM_EPNEXT 11      /* PNEXT: not a decimal in 0 .. 2^31 - 1 */
+#define PALACE_SAM_ETLEN 12       /* TLEN: not a decimal with an optional '-' within int32 */
+#define PALACE_SAM_ESEQ 13        /* SEQ: an empty field */
+#define PALACE_SAM_ECIGLEN 14     /* the CIGAR's query length (M, I, S, =, X) is not SEQ's length */
+#define PALACE_SAM_EQUAL 15       /* QUAL: neither '*' nor as many bytes of 33 .. 126 as SEQ has */
+#define PALACE_SAM_ETAG 16        /* a tag that is not XX:T:value with a type and a value this converter takes */
+#define PALACE_SAM_ETAGRANGE 17   /* an integer of a tag outside its type: i within -2^31 .. 2^32 - 1, a B element within its subtype */
+#define PALACE_SAM_ETAGFLOAT 18   /* a tag of type f or B:f: text to float is not done on the device */
+#define PALACE_SAM_ETAGHEX 19     /* an H tag with an odd count of digits or a byte that is no hex digit */
+#define PALACE_SAM_EHDSQ 20       /* header (host): an @SQ line without SN, or without an LN in 1 .. 2^31 - 1 */
+#define PALACE_SAM_EHDDUP 21      /* header (host): two @SQ lines with one SN */
+
+#define PALACE_SAM_TILE 4096               /* T: the text bytes one workgroup of palace_sam_lines takes (256 lanes x 16) */
+
+/* The lines of a text of n bytes on the device (d_text 16-byte aligned): cut at LF, a last line without LF is a line, CR is a byte
+ * like any other.  Every workgroup counts the LFs of its tile of T bytes, one workgroup scans the counts, the tiles are taken again
+ * and each LF in front of the last byte writes the start behind it.  out[0] = the number of lines, always.  With d_line_start and
+ * cap >= out[0] + 1: d_line_start[k] = the offset of line k's first byte, d_line_start[lines] = n + 1 for a text whose last byte is
+ * no LF, else n -- so that line k is [d_line_start[k], d_line_start[k + 1] - 1) -- and out[1] = the header lines (the lines beginning
+ * with '@' in front of the first line that does not), out[2] = the alignment lines (all others), out[3] / out[4] = the smallest
+ * 1-based number of a line that is empty (PALACE_SAM_EEMPTY) or begins with '@' behind an alignment line (PALACE_SAM_EAT) and that
+ * code, 0 / 0 for none.  Otherwise (the count) out[1 .. 4] = -1.  A line of more than 2^29 bytes is refused (PALACE_EINVAL).
+ * d_scratch: palace_sam_scratch_bytes(n) bytes.  Waits for the stream. */
+size_t palace_sam_scratch_bytes(int64_t n);
+int palace_sam_lines(palace_ctx *ctx, const uint8_t *d_text, int64_t n, void *d_scratch, size_t scratch_bytes, int64_t *d_line_start,
+                     int64_t cap, int64_t *out);
+
+/* Alignment line i = [d_line_start[i], d_line_start[i + 1] - 1) for i < n_lines (the caller passes the entry of the first
+ * alignment line; n_lines < 2^31), its number in the text line0 + i.  A wavefront owns a line: its lanes stride the bytes, the TABs
+ * are found by ballot and the field cuts kept in LDS; QUAL's bytes, the CIGAR's ops and the tags are checked a lane each.  Every line
+ * is validated in full; a valid line whose FLAG as written has a bit of `mask` is dropped.  RNAME and RNEXT are looked up in
+ * `names` (palace_bam_names_create over the header's targets).  d_size[i] = the record's bytes with its block_size word, 0 for a
+ * dropped line; d_off[0 .. n_lines] = head_bytes + the exclusive sums of d_size, the last entry the stream's length; d_ord[i] = the
+ * kept lines in front of line i.  out[0] = kept, out[1] = dropped, out[2] = d_off[n_lines], out[3] / out[4] = the smallest number of
+ * a line with an error and that line's code (0 / 0: none; then the other outputs mean nothing).  Waits for the stream. */
+int palace_sam_plan(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, int64_t n_lines, int64_t line0,
+                    const palace_bam_names *names, uint32_t mask, int64_t head_bytes, int32_t *d_size, int64_t *d_off,
+                    int32_t *d_ord, int64_t *out);
+
+/* Every kept line's record (SAM specification 4.2) at d_out + d_off[i], and d_starts[d_ord[i]] = d_off[i] + 4, the offset of its
+ * refID, as palace_bam_walk would leave it.  Only for a text palace_sam_plan found no error in, with that call's arrays.  Bytes
+ * [d_off[0], d_off[n_lines]) of d_out are written and no others; the stream has no alignment, every store is a byte's.  SEQ is
+ * packed and QUAL shifted by the lanes of the line's wavefront, a byte of output each; string tags are copied the same way.
+ * Enqueues only. */
+int palace_sam_encode(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, int64_t n_lines,
+                      const palace_bam_names *names, const int32_t *d_size, const int64_t *d_off, const int32_t *d_ord,
+                      uint8_t *d_out, int64_t *d_starts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -245,6 +245,11 @@ _SIGS = {
     "palace_bai_linear": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                           C.c_void_p, C.c_int64, C.c_void_p],
     "palace_bgzf_voffsets": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "palace_sam_scratch_bytes": [C.c_int64],            # (returns size_t: restype set below)
+    "palace_sam_lines": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)],
+    "palace_sam_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                        C.POINTER(C.c_int64)],
+    "palace_sam_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
 }
 
 
@@ -285,6 +290,7 @@ def lib() -> C.CDLL:
         _LIB.palace_depth_parse_scratch_bytes.restype = C.c_size_t
         _LIB.palace_fasta_index_scratch_bytes.restype = C.c_size_t
         _LIB.palace_sort_u64_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_sam_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -911,6 +917,80 @@ def bam_gather(ctx: Ctx, stream: bytes, starts, perm, head: bytes):
     finally:
         for b in bufs:
             b.free()
+
+
+SAM_TILE = 4096          # PALACE_SAM_TILE of include/palace_hip.h
+
+
+def sam_lines(ctx: Ctx, text: bytes):
+    """palace_sam_lines, the count and then the starts -> (line starts int64 (lines + 1), header lines, alignment lines,
+    the first faulty line's number or 0, its PALACE_SAM_E* code or 0)"""
+    text = bytes(text)
+    n = len(text)
+    nscr = int(lib().palace_sam_scratch_bytes(n))
+    bufs = [ctx.upload(np.frombuffer(text, dtype=np.uint8) if n else np.zeros(1, np.uint8)), ctx.empty(nscr, np.uint8)]
+    out = (C.c_int64 * 5)()
+    try:
+        _check(lib().palace_sam_lines(ctx.h, bufs[0].ptr, n, bufs[1].ptr, nscr, None, 0, out), "palace_sam_lines")
+        n_lines = int(out[0])
+        assert list(out)[1:] == [-1] * 4
+        bufs.append(ctx.empty(n_lines + 1, np.int64))
+        _check(lib().palace_sam_lines(ctx.h, bufs[0].ptr, n, bufs[1].ptr, nscr, bufs[2].ptr, n_lines + 1, out), "palace_sam_lines")
+        assert int(out[0]) == n_lines
+        return bufs[2].to_host()[:n_lines + 1].copy(), int(out[1]), int(out[2]), int(out[3]), int(out[4])
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def _sam_run(ctx: Ctx, text: bytes, starts, n_header: int, names, mask: int, head: bytes, encode: bool, guard: int = 16):
+    text = bytes(text)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    n = len(st) - 1 - n_header
+    blob = b"".join(names)
+    off = np.zeros(len(names) + 1, np.int64)
+    off[1:] = np.cumsum([len(x) for x in names])
+    bufs = [ctx.upload(np.frombuffer(text, dtype=np.uint8) if text else np.zeros(1, np.uint8)), ctx.upload(st[n_header:]),
+            ctx.upload(np.frombuffer(blob, dtype=np.uint8) if blob else np.zeros(1, np.uint8)), ctx.upload(off),
+            ctx.empty(max(1, n), np.int32), ctx.empty(n + 1, np.int64), ctx.empty(max(1, n), np.int32)]
+    d_text, d_st, d_blob, d_off, d_size, d_out_off, d_ord = bufs
+    table = C.c_void_p()
+    out = (C.c_int64 * 5)()
+    try:
+        _check(lib().palace_bam_names_create(ctx.h, d_blob.ptr, d_off.ptr, len(names), C.byref(table)), "palace_bam_names_create")
+        _check(lib().palace_sam_plan(ctx.h, d_text.ptr, d_st.ptr, n, n_header + 1, table, mask, len(head), d_size.ptr, d_out_off.ptr, d_ord.ptr, out),
+               "palace_sam_plan")
+        res = {"size": d_size.to_host()[:n].copy(), "off": d_out_off.to_host()[:n + 1].copy(), "ord": d_ord.to_host()[:n].copy(), "kept": int(out[0]),
+               "dropped": int(out[1]), "bytes": int(out[2]), "err_line": int(out[3]), "err_code": int(out[4])}
+        if not encode or res["err_code"]:
+            return res
+        image = np.full(res["bytes"] + guard, 0xAA, np.uint8)
+        image[:len(head)] = np.frombuffer(head, dtype=np.uint8)
+        d_image = ctx.upload(image)
+        d_starts = ctx.empty(max(1, res["kept"]), np.int64)
+        bufs += [d_image, d_starts]
+        _check(lib().palace_sam_encode(ctx.h, d_text.ptr, d_st.ptr, n, table, d_size.ptr, d_out_off.ptr, d_ord.ptr, d_image.ptr, d_starts.ptr), "palace_sam_encode")
+        ctx.sync()
+        res["stream"] = d_image.to_host().tobytes()
+        res["starts"] = d_starts.to_host()[:res["kept"]].copy()
+        return res
+    finally:
+        if table:
+            lib().palace_bam_names_destroy(ctx.h, table)
+        for b in bufs:
+            b.free()
+
+
+def sam_plan(ctx: Ctx, text: bytes, starts, n_header: int, names, mask: int, head_bytes: int):
+    """palace_sam_plan over the alignment lines of `text` (starts / n_header as sam_lines left them; names = the header's targets, bytes,
+    in order) -> dict: size int32, off int64 (n + 1), ord int32, kept, dropped, bytes, err_line, err_code"""
+    return _sam_run(ctx, text, starts, n_header, names, mask, b"\0" * head_bytes, False)
+
+
+def sam_encode(ctx: Ctx, text: bytes, starts, n_header: int, names, mask: int, head: bytes, guard: int = 16):
+    """palace_sam_plan and palace_sam_encode -> the plan's dict and, for a text without error, stream: `head`, the records, and `guard`
+    bytes of 0xAA where nothing may be written; starts: the kept records' starts int64"""
+    return _sam_run(ctx, text, starts, n_header, names, mask, head, True, guard)
 
 
 BAM_COLUMNS = (("tid", np.int32), ("pos", np.int32), ("mtid", np.int32), ("mpos", np.int32), ("nm", np.int32), ("ref_len", np.int32),

@@ -27,7 +27,7 @@
 // palace_bam_names_differ compares them where they lie.  Every read lies inside the record the walk accepted.
 #include "common.hpp"
 #include "bam_record.hpp"
-#include "name_hash.hpp"
+#include "bam_names.hpp"
 
 namespace palace {
 namespace {
@@ -272,27 +272,7 @@ __global__ __launch_bounds__(kColThreads) void bam_names_differ_kernel(const uin
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(differ, static_cast<unsigned long long>(__popcll(m)));
 }
 
-}  // namespace
-}  // namespace palace
-
-// the header's contig names on the device: the blob and offsets are the caller's, the table is this object's.  slots[k] = a tid or -1;
-// equal names share one slot that holds the largest tid (the last duplicate wins, as BamColumns::tid_of)
-struct palace_bam_names {
-    const uint8_t *names;
-    const int64_t *off;
-    int32_t n_ref;
-    uint32_t mask;
-    int32_t *slots;
-};
-
-namespace palace {
-namespace {
-
-__device__ __forceinline__ bool is_name(const palace_bam_names &t, int32_t tid, const uint8_t *p, int64_t n)
-{
-    return same_bytes(t.names + t.off[tid], t.off[tid + 1] - t.off[tid], p, n);
-}
-
+// (the table and its probe: bam_names.hpp)
 // linear probing without removals: a name sits between its hash's slot and the first empty one (the table is at most half full)
 __global__ __launch_bounds__(kColThreads) void bam_names_build_kernel(palace_bam_names t)
 {
@@ -304,15 +284,6 @@ __global__ __launch_bounds__(kColThreads) void bam_names_build_kernel(palace_bam
         const int32_t old = atomicCAS(&t.slots[at], -1, tid);
         if (old < 0) return;
         if (is_name(t, old, p, n)) { atomicMax(&t.slots[at], tid); return; }
-    }
-}
-
-__device__ __forceinline__ int32_t tid_of(const palace_bam_names &t, const uint8_t *p, int64_t n)
-{
-    for (uint32_t at = hash_name(p, n) & t.mask;; at = (at + 1) & t.mask) {
-        const int32_t tid = t.slots[at];
-        if (tid < 0) return -1;
-        if (is_name(t, tid, p, n)) return tid;
     }
 }
 

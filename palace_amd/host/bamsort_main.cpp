@@ -2,6 +2,8 @@
 //     $SAMTOOLS sort -@ "$threads" tmp.bam -O BAM -o first_bam ; $SAMTOOLS index first_bam
 // as   bamsort -@ "$threads" tmp.bam -O BAM -o first_bam --bai      (the argument list of `samtools sort`, in any order, + --bai)
 // or   bamsort ... -o first_bam ; bamsort --index first_bam [<out.bai>]
+// or   bwa mem ... | bamsort --sam -F 0x0800 -@ "$threads" - -O BAM -o first_bam --bai     (palace:421-433 as one command: the input is
+//      bwa's SAM text, encoded on the device as `samview` does it (sam_device.hpp), and tmp.bam never exists)
 // The BAM is inflated, CRC-checked and walked on the device (bam_stream_device.hpp), its records are keyed (palace_bam_sort_keys),
 // the keys sorted with a stable radix sort (palace_sort_u64), the records gathered behind the rewritten header
 // (palace_bam_gather_plan / _write), the stream cut into members of 0xff00 bytes that the device coder deflates (palace_crc32_members,
@@ -21,7 +23,9 @@
 
 #include "bai.hpp"
 #include "bam_stream_device.hpp"
+#include "bgzf_members_device.hpp"
 #include "device_pick.hpp"
+#include "sam_device.hpp"
 
 using namespace palace_host;
 
@@ -30,6 +34,7 @@ namespace {
 int usage()
 {
     std::cerr << "Usage: bamsort [-@ <threads>] [-O BAM] -o <out.bam> [--bai] <in.bam>   (coordinate sort; --bai also writes <out.bam>.bai)\n"
+              << "       bamsort --sam [-F <mask>] ... -o <out.bam> [--bai] <in.sam | ->     (the input is SAM text, as samview takes it)\n"
               << "       bamsort --index <sorted.bam> [<out.bai>]                       (default <sorted.bam>.bai)\n"
               << "no other option of `samtools sort` / `samtools index` is taken\n";
     return 1;
@@ -71,23 +76,6 @@ std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &in)
     return out;
 }
 
-struct Laps {
-    using clk = std::chrono::steady_clock;
-    palace_ctx *ctx;
-    bool on;
-    clk::time_point t0 = clk::now();
-    double keys = 0, sort = 0, gather = 0, deflate = 0, copy_write = 0, index = 0;
-    void restart() { t0 = clk::now(); }
-    void lap(double *acc)
-    {
-        if (!on) return;
-        if (palace_sync(ctx)) throw std::runtime_error(std::string("palace_sync: ") + palace_last_error());
-        const auto t1 = clk::now();
-        *acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-    }
-};
-
 void ck(int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); }
 
 void require_whole(const DeviceBamStream &st)
@@ -96,7 +84,7 @@ void require_whole(const DeviceBamStream &st)
     if (st.n_records > 0x7fffffffll) throw std::runtime_error("more than 2^31 - 1 records");
 }
 
-int main_sort(const std::string &in, const std::string &out, bool bai, int threads)
+int main_sort(const std::string &in, const std::string &out, bool bai, int threads, bool sam, uint32_t mask)
 {
     palace_ctx *ctx = nullptr;
     if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamsort: " << palace_last_error() << "\n"; return 1; }
@@ -107,11 +95,14 @@ int main_sort(const std::string &in, const std::string &out, bool bai, int threa
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
         Laps laps{ctx, trace};
         BamDeviceTimes bt;
+        SamTimes sam_tm;
         DeviceBamStream st;
         try {
-            load_bam_stream_device(ctx, in, threads, st, trace ? &bt : nullptr);
+            if (sam) load_sam_stream_device(ctx, in, mask, st, trace ? &sam_tm : nullptr);
+            else load_bam_stream_device(ctx, in, threads, st, trace ? &bt : nullptr);
             require_whole(st);
         } catch (const BamDeviceNoRoom &e) { throw;
+        } catch (const SamDeviceNoRoom &e) { throw;
         } catch (const std::exception &e) { throw std::runtime_error(in + ": " + e.what()); }
         const size_t n = static_cast<size_t>(st.n_records);
         BamsortDevice dev(ctx);
@@ -154,51 +145,11 @@ int main_sort(const std::string &in, const std::string &out, bool bai, int threa
 
         // the file: members of 0xff00 bytes, a batch at a time
         std::vector<int64_t> member_u, member_c;
-        const size_t n_members = (static_cast<size_t>(out_bytes) + kBgzfText - 1) / kBgzfText, batch = std::min(bamsort_batch_members(), std::max<size_t>(1, n_members));
         uint64_t file_bytes = 0;
         f = std::fopen(out.c_str(), "wb");
         if (!f) throw std::runtime_error("cannot open " + out + " for writing");
         out_made = true;
-        {
-            BamsortDevice bd(ctx);
-            uint8_t *d_slots = static_cast<uint8_t *>(bd.alloc(batch * 65536, "a batch of members")), *d_file = static_cast<uint8_t *>(bd.alloc(batch * 65536, "a batch of members"));
-            int64_t *d_off = bd.array<int64_t>(batch, "a batch of members"), *d_moff = bd.array<int64_t>(batch + 1, "a batch of members");
-            int32_t *d_len = bd.array<int32_t>(batch, "a batch of members"), *d_mlen = bd.array<int32_t>(batch, "a batch of members");
-            uint32_t *d_crc = bd.array<uint32_t>(batch, "a batch of members");
-            std::vector<int64_t> off(batch), moff(batch + 1);
-            std::vector<int32_t> lens(batch);
-            for (size_t k = 0; k < batch; k++) off[k] = static_cast<int64_t>(k * kBgzfText);
-            ck(palace_h2d(ctx, d_off, off.data(), batch * 8), "palace_h2d");
-            void *h_file = nullptr;
-            ck(palace_host_alloc(ctx, batch * 65536, &h_file), "palace_host_alloc");
-            struct Pinned { palace_ctx *ctx; void *p; ~Pinned() { palace_host_free(ctx, p); } } pinned{ctx, h_file};
-            for (size_t m0 = 0; m0 < n_members; m0 += batch) {
-                const size_t nm = std::min(batch, n_members - m0);
-                const uint64_t t_beg = m0 * kBgzfText, t_end = std::min<uint64_t>(static_cast<uint64_t>(out_bytes), (m0 + nm) * kBgzfText);
-                for (size_t k = 0; k < nm; k++) lens[k] = static_cast<int32_t>(std::min<uint64_t>(kBgzfText, t_end - (t_beg + k * kBgzfText)));
-                laps.restart();
-                ck(palace_h2d(ctx, d_len, lens.data(), nm * 4), "palace_h2d");
-                const uint8_t *d_text = d_out + t_beg;
-                ck(palace_crc32_members(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc), "palace_crc32_members");
-                ck(palace_bgzf_deflate(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc, d_slots, d_mlen), "palace_bgzf_deflate");
-                ck(palace_bgzf_compact(ctx, d_slots, static_cast<int64_t>(nm), d_mlen, d_file, d_moff), "palace_bgzf_compact");
-                laps.lap(&laps.deflate);
-                ck(palace_d2h(ctx, moff.data(), d_moff, (nm + 1) * 8), "palace_d2h");
-                const size_t bytes = static_cast<size_t>(moff[nm]);
-                ck(palace_d2h(ctx, h_file, d_file, bytes), "palace_d2h");
-                for (size_t k = 0; k < nm; k++) {
-                    member_u.push_back(static_cast<int64_t>((m0 + k) * kBgzfText));
-                    member_c.push_back(static_cast<int64_t>(file_bytes) + moff[k]);
-                }
-                if (std::fwrite(h_file, 1, bytes, f) != bytes) throw std::runtime_error("write failed: " + out);
-                file_bytes += bytes;
-                laps.lap(&laps.copy_write);
-            }
-        }
-        member_u.push_back(out_bytes);                                       // the EOF member stands for the stream's end
-        member_c.push_back(static_cast<int64_t>(file_bytes));
-        if (std::fwrite(bgzf_eof_member(), 1, 28, f) != 28) throw std::runtime_error("write failed: " + out);
-        file_bytes += 28;
+        write_members_device(ctx, d_out, out_bytes, bamsort_batch_members(), false, f, out, laps, member_u, member_c, &file_bytes);
         const int rc_close = std::fclose(f);
         f = nullptr;
         if (rc_close != 0) throw std::runtime_error("write failed: " + out);
@@ -210,6 +161,9 @@ int main_sort(const std::string &in, const std::string &out, bool bai, int threa
             write_bai_device(ctx, out, d_out, d_out_starts, st.n_records, st.n_ref, member_u, member_c, out + ".bai");
             laps.lap(&laps.index);
         }
+        if (trace && sam)
+            std::fprintf(stderr, "[bamsort] --sam ms: read %.1f upload %.1f lines %.1f plan %.1f encode %.1f\n", sam_tm.read, sam_tm.upload, sam_tm.lines, sam_tm.plan,
+                         sam_tm.encode);
         if (trace)
             std::fprintf(stderr, "[bamsort] ms: member index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f | keys %.1f sort %.1f gather %.1f "
                          "crc+deflate %.1f copy+write %.1f index %.1f; records %lld, stream %lld B -> %lld B, file %llu B, members inflated on the host %lld\n",
@@ -294,7 +248,8 @@ int main(int argc, char **argv)
         return main_index(pos[0], pos.size() == 2 ? pos[1] : pos[0] + ".bai", 16);
     }
     std::string in, out, fmt = "BAM";
-    bool bai = false, have_in = false;
+    bool bai = false, have_in = false, sam = false, have_mask = false;
+    uint32_t mask = 0;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string &s = a[i];
         auto value = [&](std::string *v) {                                   // `-x value` or `-xvalue`
@@ -304,7 +259,13 @@ int main(int argc, char **argv)
             return true;
         };
         if (s == "--bai") bai = true;
-        else if (s.rfind("-@", 0) == 0) {
+        else if (s == "--sam") sam = true;
+        else if (s == "-" && !have_in) { in = s; have_in = true; }
+        else if (s.rfind("-F", 0) == 0) {
+            std::string v;
+            if (!value(&v) || !parse_flag_mask(v, &mask)) return usage();
+            have_mask = true;
+        } else if (s.rfind("-@", 0) == 0) {
             std::string v;
             if (!value(&v) || v.empty() || v.find_first_not_of("0123456789") != std::string::npos || v.size() > 6) return usage();
             threads = std::max(1, std::atoi(v.c_str()));
@@ -316,7 +277,7 @@ int main(int argc, char **argv)
         else if (have_in) return usage();
         else { in = s; have_in = true; }
     }
-    if (!have_in || out.empty()) return usage();
+    if (!have_in || out.empty() || (!sam && (have_mask || in == "-"))) return usage();
     if (fmt != "BAM" && fmt != "bam") { std::cerr << "bamsort: -O " << fmt << ": only BAM is written\n"; return 1; }
-    return main_sort(in, out, bai, std::min(threads, 64));
+    return main_sort(in, out, bai, std::min(threads, 64), sam, mask);
 }
