@@ -16,34 +16,16 @@
 #include <string>
 #include <vector>
 
-#include "../../include/palace_hip.h"
+#include "device_scope.hpp"
 
 namespace palace_host {
 
-// thrown when the device cannot hold what bamsort keeps there
-struct BamsortNoRoom : std::runtime_error { using std::runtime_error::runtime_error; };
-
-// device allocations of one bamsort step: freed when it leaves, or given back early
-struct BamsortDevice {
-    palace_ctx *ctx;
-    std::vector<void *> owned;
-    explicit BamsortDevice(palace_ctx *c) : ctx(c) {}
-    BamsortDevice(const BamsortDevice &) = delete;
-    BamsortDevice &operator=(const BamsortDevice &) = delete;
-    ~BamsortDevice() { for (void *p : owned) palace_free(ctx, p); }
-    void *alloc(size_t bytes, const char *what)
-    {
-        void *p = nullptr;
-        if (palace_malloc(ctx, bytes ? bytes : 1, &p))
-            throw BamsortNoRoom("the inflated BAM, the sorted stream, the per-record arrays and one batch of members are kept on the device, and " +
-                                std::to_string(bytes) + " bytes for " + what + " cannot be allocated (" + palace_last_error() +
-                                "); there is no host path, a BAM larger than device memory is out of scope");
-        owned.push_back(p);
-        return p;
-    }
-    template <class T> T *array(size_t n, const char *what) { return static_cast<T *>(alloc(n * sizeof(T), what)); }
-    void give_back(void *p) { palace_free(ctx, p); owned.erase(std::find(owned.begin(), owned.end(), p)); }
-};
+// the out-of-room text of bamsort's steps (and of the member writer behind samview)
+inline std::string bamsort_no_room(size_t bytes, const char *what, const char *err)
+{
+    return "the inflated BAM, the sorted stream, the per-record arrays and one batch of members are kept on the device, and " + std::to_string(bytes) +
+           " bytes for " + what + " cannot be allocated (" + err + "); there is no host path, a BAM larger than device memory is out of scope";
+}
 
 constexpr uint32_t kBaiPseudoBin = 37450;
 
@@ -52,8 +34,7 @@ constexpr uint32_t kBaiPseudoBin = 37450;
 inline void write_bai_device(palace_ctx *ctx, const std::string &file, const uint8_t *d_stream, const int64_t *d_starts, int64_t n_records, int32_t n_ref,
                              const std::vector<int64_t> &member_u, const std::vector<int64_t> &member_c, const std::string &bai_path)
 {
-    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
-    BamsortDevice dev(ctx);
+    DeviceScope dev(ctx, bamsort_no_room);
     const size_t n = static_cast<size_t>(n_records), nr = static_cast<size_t>(n_ref);
     int32_t *d_ref = dev.array<int32_t>(n, "the index columns"), *d_bin = dev.array<int32_t>(n, "the index columns");
     int32_t *d_wb = dev.array<int32_t>(n, "the index columns"), *d_we = dev.array<int32_t>(n, "the index columns");
@@ -83,17 +64,14 @@ inline void write_bai_device(palace_ctx *ctx, const std::string &file, const uin
     std::vector<int64_t> lin_off(nr + 1, 0);
     for (size_t t = 0; t < nr; t++) lin_off[t + 1] = lin_off[t] + n_intv[t];
     const size_t nl = static_cast<size_t>(lin_off[nr]);
-    int64_t *d_lin_off = dev.array<int64_t>(nr + 1, "the linear index");
+    const int64_t *d_lin_off = dev.upload(lin_off.data(), nr + 1, "the linear index");
     int64_t *d_lin = dev.array<int64_t>(nl, "the linear index");
-    ck(palace_h2d(ctx, d_lin_off, lin_off.data(), (nr + 1) * 8), "palace_h2d");
     ck(palace_bai_linear(ctx, d_stream, d_starts, d_ref, d_wb, d_we, d_unm, n_records, n_ref, d_n_intv, d_stat, d_lin_off, static_cast<int64_t>(nl), d_lin),
        "palace_bai_linear");
 
     // virtual offsets
     const size_t nm = member_u.size();
-    int64_t *d_mu = dev.array<int64_t>(nm, "the member table"), *d_mc = dev.array<int64_t>(nm, "the member table");
-    ck(palace_h2d(ctx, d_mu, member_u.data(), nm * 8), "palace_h2d");
-    ck(palace_h2d(ctx, d_mc, member_c.data(), nm * 8), "palace_h2d");
+    const int64_t *d_mu = dev.upload(member_u.data(), nm, "the member table"), *d_mc = dev.upload(member_c.data(), nm, "the member table");
     auto voffsets = [&](const int64_t *d_u, size_t count) {
         std::vector<uint64_t> v(count);
         if (!count) return v;

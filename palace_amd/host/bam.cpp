@@ -1,5 +1,6 @@
 #include "bam.hpp"
 #include "../csrc/bam_record.hpp"
+#include "mapped_file.hpp"
 #include "trace.hpp"
 
 #include <fcntl.h>
@@ -23,30 +24,6 @@ namespace palace_host {
 namespace {
 
 uint32_t le32(const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; }
-
-// The compressed file, mapped read-only (no copy of it is made).
-struct MappedFile {
-    const uint8_t *data = nullptr;
-    size_t size = 0;
-    explicit MappedFile(const std::string &path)
-    {
-        int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("Failed to open BAM " + path);
-        struct stat st;
-        if (::fstat(fd, &st) != 0) { ::close(fd); throw std::runtime_error("Failed to open BAM " + path); }
-        size = static_cast<size_t>(st.st_size);
-        if (size) {
-            void *m = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { ::close(fd); throw std::runtime_error("Failed to read BAM " + path); }
-            ::madvise(m, size, MADV_SEQUENTIAL);
-            data = static_cast<const uint8_t *>(m);
-        }
-        ::close(fd);
-    }
-    ~MappedFile() { if (data) ::munmap(const_cast<uint8_t *>(data), size); }
-    MappedFile(const MappedFile &) = delete;
-    MappedFile &operator=(const MappedFile &) = delete;
-};
 
 template <class F>
 void parallel_for(size_t n, int threads, F f)
@@ -177,7 +154,7 @@ struct BamLoad : BackMembers {
     }
     void finished(size_t i, bool decoded) override
     {
-        if (!decoded && !inflate_member(file->data, file->size, bgzf[i], c->raw.data() + bgzf[i].out_off)) bad = true;
+        if (!decoded && !inflate_member(file->bytes(), file->size, bgzf[i], c->raw.data() + bgzf[i].out_off)) bad = true;
         if (decoded) by_helpers.fetch_add(1, std::memory_order_relaxed);
         done[i].store(1, std::memory_order_release);
     }
@@ -195,9 +172,9 @@ BamLoad *load_bam_begin(const std::string &path, int threads, BamColumns &c, con
     std::unique_ptr<BamLoad> L(new BamLoad());
     L->c = &c;
     L->threads = threads = std::max(1, threads);
-    L->file.reset(new MappedFile(path));
+    L->file.reset(new MappedFile(path, MapHint::sequential, "Failed to open BAM ", "Failed to read BAM "));
     size_t total = 0;
-    L->bgzf = bgzf_members(L->file->data, L->file->size, &total);
+    L->bgzf = bgzf_members(L->file->bytes(), L->file->size, &total);
     c.raw.alloc(total);
     const size_t nb = L->bgzf.size();
     L->done.reset(new std::atomic<uint8_t>[nb ? nb : 1]);
@@ -207,7 +184,7 @@ BamLoad *load_bam_begin(const std::string &path, int threads, BamColumns &c, con
     // (a helper costs a device context and its buffers: not for files the threads are done with before the HIP runtime is even up)
     if (!helpers.empty() && (nb >= 4096 || std::getenv("PALACE_BAM_HOST_SHARE"))) {
         L->members = L->bgzf.data();
-        L->file_data = L->file->data;
+        L->file_data = L->file->bytes();
         L->file_size = L->file->size;
         L->out = c.raw.data();
         if (const char *e = std::getenv("PALACE_BAM_HOST_SHARE")) L->hold_at = nb * static_cast<size_t>(std::max(0, std::min(100, std::atoi(e)))) / 100;
@@ -222,7 +199,7 @@ BamLoad *load_bam_begin(const std::string &path, int threads, BamColumns &c, con
             const bool use_fast = std::getenv("PALACE_BAM_ZLIB") == nullptr;          // PALACE_BAM_ZLIB=1: zlib for every member (A/B, tests)
             for (size_t i = 0; !ld->bad && ld->claim_front(&i);) {
                 const BgzfMember &m = ld->bgzf[i];
-                if (!inflate_member(ld->file->data, ld->file->size, m, out + m.out_off, &zs, use_fast)) { ld->bad = true; break; }
+                if (!inflate_member(ld->file->bytes(), ld->file->size, m, out + m.out_off, &zs, use_fast)) { ld->bad = true; break; }
                 ld->done[i].store(1, std::memory_order_release);
             }
             inflateEnd(&zs);

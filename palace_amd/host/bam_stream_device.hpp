@@ -11,14 +11,8 @@
 // `generateGraph --bam-gpu` uses the same stream part (load_bam_stream_device: everything up to the record starts) and keeps the stream
 // and the starts alive for palace_bam_columns / palace_bam_sa_items and its read-name guard (generate_graph_main.cpp).
 #pragma once
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <functional>
@@ -30,6 +24,8 @@
 #include "../../include/palace_hip.h"
 #include "bam_device.hpp"
 #include "bgzf.hpp"
+#include "device_scope.hpp"
+#include "mapped_file.hpp"
 
 namespace palace_host {
 
@@ -50,40 +46,26 @@ inline int64_t bam_walk_chunk()
     return v > 0 ? std::max<long long>(v, 64) : 0;
 }
 
-// thrown when the device cannot hold what the mode keeps there: the message names the way out
-struct BamDeviceNoRoom : std::runtime_error { using std::runtime_error::runtime_error; };
+// the out-of-room text of the --bam-gpu modes: it names the way out
+inline std::string bam_gpu_no_room(size_t bytes, const char *what, const char *err)
+{
+    return "--bam-gpu keeps the whole inflated BAM on the device and cannot allocate " + std::to_string(bytes) + " bytes for " + what + " (" + err +
+           "); run without --bam-gpu to load the BAM on the host";
+}
 
-// device allocations of a loader: freed when it leaves, unless handed on (keep) or given back early
-struct DeviceOwner {
-    palace_ctx *ctx;
-    std::vector<void *> owned;
-    explicit DeviceOwner(palace_ctx *c) : ctx(c) {}
-    DeviceOwner(const DeviceOwner &) = delete;
-    DeviceOwner &operator=(const DeviceOwner &) = delete;
-    ~DeviceOwner() { for (void *p : owned) palace_free(ctx, p); }
-    void *alloc(size_t bytes, const char *what)
-    {
-        void *p = nullptr;
-        if (palace_malloc(ctx, bytes ? bytes : 1, &p))
-            throw BamDeviceNoRoom("--bam-gpu keeps the whole inflated BAM on the device and cannot allocate " + std::to_string(bytes) + " bytes for " + what + " (" +
-                                  palace_last_error() + "); run without --bam-gpu to load the BAM on the host");
-        owned.push_back(p);
-        return p;
-    }
-    void give_back(void *p) { palace_free(ctx, p); owned.erase(std::find(owned.begin(), owned.end(), p)); }
-    void keep(void *p) { owned.erase(std::find(owned.begin(), owned.end(), p)); }        // (the result's from here on)
-    void keep_all() { owned.clear(); }
-};
-
-// The part every --bam-gpu mode shares: the header's targets on the host; the inflated, CRC-checked stream and the record starts
-// on the device, alive as long as this object is.
-struct DeviceBamStream {
-    palace_ctx *ctx = nullptr;
+// What every reader of a BAM on the device knows of it: the header's targets and the numbers of the stream and its walk.
+struct BamStreamInfo {
     std::vector<std::string> target_name;
     std::vector<int32_t> target_len;
     int32_t n_ref = 0;
     int64_t n_records = 0, stop = 0, total = 0, first = 0, host_inflated = 0;
     int64_t walk_stats[4] = {0, 0, 0, 0};              // chunks, guesses that held, chunks repaired, chunks without a start
+};
+
+// The part every --bam-gpu mode shares: the inflated, CRC-checked stream and the record starts on the device, alive as long as this
+// object is.
+struct DeviceBamStream : BamStreamInfo {
+    palace_ctx *ctx = nullptr;
     uint8_t *d_stream = nullptr;
     int64_t *d_starts = nullptr;
     DeviceBamStream() = default;
@@ -97,13 +79,10 @@ struct DeviceBamStream {
     ~DeviceBamStream() { release(); }
 };
 
-// What the depth stage needs of a BAM: the header's targets on the host, the match segments on the device.
-struct DeviceBam {
+// What the depth stage needs of a BAM: the match segments on the device.
+struct DeviceBam : BamStreamInfo {
     palace_ctx *ctx = nullptr;
-    std::vector<std::string> target_name;
-    std::vector<int32_t> target_len;
-    int64_t n_records = 0, n_segs = 0, stop = 0, total = 0, first = 0, host_inflated = 0;
-    int64_t walk_stats[4] = {0, 0, 0, 0};              // chunks, guesses that held, chunks repaired, chunks without a start
+    int64_t n_segs = 0;
     int32_t *d_tid = nullptr, *d_pos = nullptr, *d_len = nullptr;
     DeviceBam() = default;
     DeviceBam(const DeviceBam &) = delete;
@@ -111,77 +90,57 @@ struct DeviceBam {
     ~DeviceBam() { for (void *p : {static_cast<void *>(d_tid), static_cast<void *>(d_pos), static_cast<void *>(d_len)}) if (p) palace_free(ctx, p); }
 };
 
-// a stage clock for traced runs: lap() adds the time since the last lap to *acc (waiting for the device first when asked to)
-struct BamDeviceClock {
-    using clk = std::chrono::steady_clock;
-    palace_ctx *ctx;
-    bool on;
-    clk::time_point t0 = clk::now();
-    void restart() { t0 = clk::now(); }
-    void lap(double *acc, bool device)
-    {
-        if (!on) return;
-        if (device && palace_sync(ctx)) throw std::runtime_error(std::string("palace_sync: ") + palace_last_error());
-        const auto t1 = clk::now();
-        *acc += std::chrono::duration<double, std::milli>(t1 - t0).count();
-        t0 = t1;
-    }
-};
+// The file's checked member table as palace_bgzf_voffsets takes it: stream offset and file offset of every BGZF member, the last entry
+// standing for the stream's end (the EOF member; without one, the file's end).
+struct BamMemberTable { std::vector<int64_t> u, c; };
 
 // The file map, the member index, the header, the batches with inflate and CRC, and the walk.
-// Throws std::runtime_error: load_bam's messages for what load_bam rejects, BamDeviceNoRoom, or a device error with
+// Throws std::runtime_error: load_bam's messages for what load_bam rejects, DeviceNoRoom, or a device error with
 // palace_last_error().  times: every stage waited for (traced runs).
 // on_header: called once out.target_name / target_len are there, before the first batch goes up (what depends on the names only can
-// start beside the rest; it may take the two vectors out of `out`).
+// start beside the rest; it may take the two vectors out of `out`).  members: the file's member table, for a caller who indexes it.
 inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int threads, DeviceBamStream &out, BamDeviceTimes *times = nullptr,
-                                   const std::function<void()> &on_header = {})
+                                   const std::function<void()> &on_header = {}, BamMemberTable *members = nullptr)
 {
     auto le32 = [](const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; };
-    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
     BamDeviceTimes unused;
     BamDeviceTimes &tm = times ? *times : unused;
-    BamDeviceClock clock{ctx, times != nullptr};
+    StageClock clock{ctx, times != nullptr};
     auto lap = [&](double *acc, bool device) { clock.lap(acc, device); };
     out.ctx = ctx;
-    DeviceOwner own(ctx);
+    DeviceScope own(ctx, bam_gpu_no_room);
     auto give_back = [&](void *p) { own.give_back(p); };
     auto dev = [&](size_t bytes, const char *what) { return own.alloc(bytes, what); };
 
     // ---- the file and its checked member index ----
-    struct Mapped {
-        const uint8_t *data = nullptr; size_t size = 0;
-        ~Mapped() { if (data) ::munmap(const_cast<uint8_t *>(data), size); }
-    } file;
-    {
-        const int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("Failed to open BAM " + path);
-        struct stat st;
-        if (::fstat(fd, &st) != 0) { ::close(fd); throw std::runtime_error("Failed to open BAM " + path); }
-        file.size = static_cast<size_t>(st.st_size);
-        if (file.size) {
-            void *m = ::mmap(nullptr, file.size, PROT_READ, MAP_PRIVATE, fd, 0);
-            if (m == MAP_FAILED) { ::close(fd); throw std::runtime_error("Failed to read BAM " + path); }
-            ::madvise(m, file.size, MADV_SEQUENTIAL);
-            file.data = static_cast<const uint8_t *>(m);
-        }
-        ::close(fd);
-    }
+    const MappedFile file(path, MapHint::sequential, "Failed to open BAM ", "Failed to read BAM ");
     size_t total = 0;
-    const std::vector<BgzfMember> mem = bgzf_members(file.data, file.size, &total);
+    BgzfWalkEnd end;
+    const std::vector<BgzfMember> mem = bgzf_members(file.bytes(), file.size, &total, &end);
     const size_t nb = mem.size();
     out.total = static_cast<int64_t>(total);
+    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
+    if (members) {
+        for (size_t i = 0; i < nb; i++) {
+            members->u.push_back(static_cast<int64_t>(mem[i].out_off));
+            members->c.push_back(static_cast<int64_t>(member_start(i)));
+        }
+        if (mem.empty() || mem.back().out_len != 0) {                        // no EOF member: the file's end stands for the stream's
+            members->u.push_back(static_cast<int64_t>(total));
+            members->c.push_back(static_cast<int64_t>(end.offset));
+        }
+    }
     lap(&tm.index, false);
 
     // ---- the header (BAM spec 4.2), from the front members inflated here: rounds of twice as many members, on the threads ----
     std::vector<uint8_t> hdr;
     size_t hdr_members = 0;
-    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
     // a header that cannot be read: a front member whose bytes are not the ones its trailer's CRC-32 was made of says so (checked
     // here only: a header that reads well is checked with every other member, on the device)
     auto unreadable_header = [&]() -> std::runtime_error {
         for (size_t i = 0; i < hdr_members; i++)
             if (static_cast<uint32_t>(::crc32(::crc32(0L, Z_NULL, 0), hdr.data() + mem[i].out_off, static_cast<uInt>(mem[i].out_len))) !=
-                le32(file.data + mem[i].in_off + mem[i].in_len))
+                le32(file.bytes() + mem[i].in_off + mem[i].in_len))
                 return std::runtime_error("CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i)));
         return std::runtime_error("Failed to read BAM header");
     };
@@ -193,7 +152,7 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
             std::atomic<bool> bad{false};
             auto work = [&] {
                 for (size_t i; (i = next.fetch_add(1)) < b;)
-                    if (!inflate_member(file.data, file.size, mem[i], hdr.data() + mem[i].out_off)) bad = true;
+                    if (!inflate_member(file.bytes(), file.size, mem[i], hdr.data() + mem[i].out_off)) bad = true;
             };
             std::vector<std::thread> pool;
             for (size_t t = 1; t < std::min<size_t>(static_cast<size_t>(std::max(1, threads)), b - a); t++) pool.emplace_back(work);
@@ -245,7 +204,7 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
             int32_t *status = tab.status(tab.host.data());
             uint32_t *crc = tab.crc(tab.host.data());
             clock.restart();
-            ck(palace_h2d(ctx, d_in, file.data + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
+            ck(palace_h2d(ctx, d_in, file.bytes() + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
             ck(palace_h2d(ctx, d_meta, tab.host.data(), tab.up_bytes()), "member table");
             lap(&tm.upload, true);
             ck(tab.inflate(d_in, d_out), "palace_bgzf_inflate");
@@ -253,7 +212,7 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
             for (size_t j = 0; j < n; j++) {                                 // what the device refused: the host's decoder, zlib behind it
                 if (status[j] == 0) continue;
                 const BgzfMember &m = mem[i0 + j];
-                if (!inflate_member(file.data, file.size, m, host_out.data())) throw std::runtime_error("BGZF inflate failed");
+                if (!inflate_member(file.bytes(), file.size, m, host_out.data())) throw std::runtime_error("BGZF inflate failed");
                 if (m.out_len) ck(palace_h2d(ctx, d_out + out_off[j], host_out.data(), m.out_len), "inflated upload");
                 out.host_inflated++;
             }
@@ -262,7 +221,7 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
             ck(palace_d2h(ctx, crc, tab.crc(tab.dev), 4 * n), "member CRC");
             for (size_t j = 0; j < n; j++) {
                 const BgzfMember &m = mem[i0 + j];
-                if (crc[j] != le32(file.data + m.in_off + m.in_len))
+                if (crc[j] != le32(file.bytes() + m.in_off + m.in_len))
                     throw std::runtime_error("CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i0 + j)));
             }
             lap(&tm.crc, true);
@@ -297,18 +256,14 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
 // stream and the starts are given back once the segments are there.
 inline void load_bam_device(palace_ctx *ctx, const std::string &path, int threads, DeviceBam &out, BamDeviceTimes *times = nullptr)
 {
-    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
     BamDeviceTimes unused;
     BamDeviceTimes &tm = times ? *times : unused;
     DeviceBamStream st;
     load_bam_stream_device(ctx, path, threads, st, times);
-    BamDeviceClock clock{ctx, times != nullptr};
+    StageClock clock{ctx, times != nullptr};
     out.ctx = ctx;
-    out.target_name.swap(st.target_name);
-    out.target_len.swap(st.target_len);
-    out.n_records = st.n_records; out.stop = st.stop; out.total = st.total; out.first = st.first; out.host_inflated = st.host_inflated;
-    std::copy(st.walk_stats, st.walk_stats + 4, out.walk_stats);
-    DeviceOwner own(ctx);
+    static_cast<BamStreamInfo &>(out) = std::move(static_cast<BamStreamInfo &>(st));      // (the names move; st's numbers stay readable)
+    DeviceScope own(ctx, bam_gpu_no_room);
     ck(palace_bam_match_segments(ctx, st.d_stream, st.total, st.d_starts, st.n_records, st.n_ref, nullptr, nullptr, nullptr, 0, &out.n_segs),
        "palace_bam_match_segments");
     int32_t **seg[3] = {&out.d_tid, &out.d_pos, &out.d_len};

@@ -39,13 +39,49 @@
 
 using namespace palace_host;
 
+// the awk number on stdout, or awk's complaint (exit code 2)
+static int print_mean(uint64_t sum, uint64_t lines)
+{
+    if (lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; return 2; }
+    std::cout << awk_number(static_cast<double>(sum) / static_cast<double>(lines)) << "\n";
+    return 0;
+}
+
+// `contig <TAB> depth sum <TAB> covered positions` for every contig with coverage
+static int print_per_contig(const std::vector<std::string> &name, const std::vector<uint64_t> &sum, const std::vector<uint64_t> &covered)
+{
+    std::string out;
+    for (size_t t = 0; t < sum.size(); t++)
+        if (covered[t]) out += name[t] + "\t" + std::to_string(sum[t]) + "\t" + std::to_string(covered[t]) + "\n";
+    std::cout << out;
+    return 0;
+}
+
+// --depth-gz-gpu: what the writer reports (traced runs), then the mean
+static int report_depth_gz_gpu(const DepthGzResult &r, const DepthGzDeviceTimes &tm, bool trace)
+{
+    if (trace)
+        std::fprintf(stderr, "[bamdepth] depth-gz-gpu ms: upload %.1f create %.1f emit %.1f crc %.1f deflate+compact %.1f d2h+write %.1f windows %.1f tbi %.1f; "
+                     "text %llu B, file %llu B\n", tm.upload, tm.create, tm.members.emit, tm.members.crc, tm.members.deflate, tm.members.copy_write, tm.windows, tm.tbi,
+                     static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.file_bytes));
+    return print_mean(r.sum, r.lines);
+}
+
+// the mean or the per-contig table from first_depth's answer
+static int print_first_depth(int rc, bool per_contig, const std::string &text, const std::vector<std::string> &name, const std::vector<uint64_t> &cs,
+                             const std::vector<uint64_t> &cc)
+{
+    if (rc < 0) throw std::runtime_error(palace_last_error());
+    if (per_contig) return print_per_contig(name, cs, cc);
+    if (rc > 0) return print_mean(0, 0);
+    std::cout << text << "\n";
+    return 0;
+}
+
 // `bamdepth --bam-gpu ...`: argv[1 ..] are the arguments behind --bam-gpu, parsed as main() parses them
 static int main_bam_gpu(bool per_contig, bool depth_gz_gpu, const char *gz_path, const char *bam, int threads)
 {
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
-    int code = 0;
-    try {
+    return with_device("bamdepth", [&](palace_ctx *ctx) {
         DeviceBam b;
         BamDeviceTimes bt;
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
@@ -62,38 +98,20 @@ static int main_bam_gpu(bool per_contig, bool depth_gz_gpu, const char *gz_path,
         if (depth_gz_gpu) {
             DepthGzDeviceTimes tm;
             const DepthGzResult r = write_depth_gz_device(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_name, b.target_len, gz_path, trace ? &tm : nullptr);
-            if (trace)
-                std::fprintf(stderr, "[bamdepth] depth-gz-gpu ms: upload %.1f create %.1f emit %.1f crc %.1f deflate+compact %.1f d2h+write %.1f windows %.1f tbi %.1f; "
-                             "text %llu B, file %llu B\n", tm.upload, tm.create, tm.emit, tm.crc, tm.deflate, tm.copy_write, tm.windows, tm.tbi,
-                             static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.file_bytes));
-            if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
-            else std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
-        } else {
-            std::string text;
-            std::vector<uint64_t> cs, cc;
-            const int rc = per_contig ? first_depth(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_len, text, nullptr, nullptr, &cs, &cc)
-                                      : first_depth(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_len, text);
-            if (rc < 0) throw std::runtime_error(palace_last_error());
-            if (per_contig) {
-                std::string out;
-                for (size_t t = 0; t < cs.size(); t++)
-                    if (cc[t]) out += b.target_name[t] + "\t" + std::to_string(cs[t]) + "\t" + std::to_string(cc[t]) + "\n";
-                std::cout << out;
-            } else if (rc > 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
-            else std::cout << text << "\n";
+            return report_depth_gz_gpu(r, tm, trace);
         }
-    } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; code = 1; }
-    palace_ctx_destroy(ctx);
-    return code;
+        std::string text;
+        std::vector<uint64_t> cs, cc;
+        const int rc = per_contig ? first_depth(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_len, text, nullptr, nullptr, &cs, &cc)
+                                  : first_depth(ctx, b.n_segs, b.d_tid, b.d_pos, b.d_len, b.target_len, text);
+        return print_first_depth(rc, per_contig, text, b.target_name, cs, cc);
+    });
 }
 
 // `bamdepth --from-depth [--per-contig] <depth file>`
 static int main_from_depth(bool per_contig, const char *file)
 {
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
-    int code = 0;
-    try {
+    return with_device("bamdepth", [&](palace_ctx *ctx) {
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
         DepthReadTimes tm;
         const DepthReadResult r = read_depth_file(ctx, file, trace ? &tm : nullptr);
@@ -102,15 +120,12 @@ static int main_from_depth(bool per_contig, const char *file)
                          "runs %llu, members inflated on the host %llu\n", tm.index, tm.upload, tm.inflate, tm.crc, tm.parse, tm.merge,
                          static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.lines), static_cast<unsigned long long>(r.runs),
                          static_cast<unsigned long long>(r.host_inflated));
-        if (per_contig) {
-            std::string out;
-            for (size_t t = 0; t < r.name.size(); t++) out += r.name[t] + "\t" + std::to_string(r.contig_sum[t]) + "\t" + std::to_string(r.contig_lines[t]) + "\n";
-            std::cout << out;
-        } else if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
-        else std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
-    } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; code = 1; }
-    palace_ctx_destroy(ctx);
-    return code;
+        if (!per_contig) return print_mean(r.sum, r.lines);
+        std::string out;                                                     // (every contig of the file has lines)
+        for (size_t t = 0; t < r.name.size(); t++) out += r.name[t] + "\t" + std::to_string(r.contig_sum[t]) + "\t" + std::to_string(r.contig_lines[t]) + "\n";
+        std::cout << out;
+        return 0;
+    });
 }
 
 static int usage(const char *prog)
@@ -145,47 +160,22 @@ int main(int argc, char **argv)
     try {
         load_bam(bam, threads, 1, c);
     } catch (const std::exception &e) { std::cerr << e.what() << "\n"; return 1; }
-    if (depth_gz_gpu) {                              // text, CRC-32, DEFLATE and the index's offsets on the device
-        palace_ctx *gctx = nullptr;
-        if (palace_ctx_create(pick_device(), &gctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
-        int code = 0;
-        try {
+    if (depth_gz_gpu)                                // text, CRC-32, DEFLATE and the index's offsets on the device
+        return with_device("bamdepth", [&](palace_ctx *ctx) {
             DepthGzDeviceTimes tm;
             const bool trace = std::getenv("PALACE_TRACE") != nullptr;
-            const DepthGzResult r = write_depth_gz_device(gctx, c, argv[2], trace ? &tm : nullptr);
-            if (trace)
-                std::fprintf(stderr, "[bamdepth] depth-gz-gpu ms: upload %.1f create %.1f emit %.1f crc %.1f deflate+compact %.1f d2h+write %.1f windows %.1f tbi %.1f; "
-                             "text %llu B, file %llu B\n", tm.upload, tm.create, tm.emit, tm.crc, tm.deflate, tm.copy_write, tm.windows, tm.tbi,
-                             static_cast<unsigned long long>(r.text_bytes), static_cast<unsigned long long>(r.file_bytes));
-            if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; code = 2; }
-            else std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
-        } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; code = 1; }
-        palace_ctx_destroy(gctx);
-        return code;
-    }
+            return report_depth_gz_gpu(write_depth_gz_device(ctx, c, argv[2], trace ? &tm : nullptr), tm, trace);
+        });
     if (depth_gz) {                                  // no GPU in this mode: text and DEFLATE are host work
         try {
             const DepthGzResult r = write_depth_gz(c, argv[2], threads);
-            if (r.lines == 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; return 2; }
-            std::cout << awk_number(static_cast<double>(r.sum) / static_cast<double>(r.lines)) << "\n";
-            return 0;
+            return print_mean(r.sum, r.lines);
         } catch (const std::exception &e) { std::cerr << "bamdepth: " << e.what() << "\n"; return 1; }
     }
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
-    std::string text;
-    std::vector<uint64_t> cs, cc;
-    const int rc = per_contig ? first_depth(ctx, c, text, nullptr, nullptr, &cs, &cc) : first_depth(ctx, c, text);
-    palace_ctx_destroy(ctx);
-    if (rc < 0) { std::cerr << "bamdepth: " << palace_last_error() << "\n"; return 1; }
-    if (per_contig) {
-        std::string out;
-        for (size_t t = 0; t < cs.size(); t++)
-            if (cc[t]) out += c.target_name[t] + "\t" + std::to_string(cs[t]) + "\t" + std::to_string(cc[t]) + "\n";
-        std::cout << out;
-        return 0;
-    }
-    if (rc > 0) { std::cerr << "bamdepth: no position is covered (awk: division by zero)\n"; return 2; }
-    std::cout << text << "\n";
-    return 0;
+    return with_device("bamdepth", [&](palace_ctx *ctx) {
+        std::string text;
+        std::vector<uint64_t> cs, cc;
+        const int rc = per_contig ? first_depth(ctx, c, text, nullptr, nullptr, &cs, &cc) : first_depth(ctx, c, text);
+        return print_first_depth(rc, per_contig, text, c.target_name, cs, cc);
+    });
 }

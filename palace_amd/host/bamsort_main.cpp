@@ -7,18 +7,12 @@
 // The BAM is inflated, CRC-checked and walked on the device (bam_stream_device.hpp), its records are keyed (palace_bam_sort_keys),
 // the keys sorted with a stable radix sort (palace_sort_u64), the records gathered behind the rewritten header
 // (palace_bam_gather_plan / _write), the stream cut into members of 0xff00 bytes that the device coder deflates (palace_crc32_members,
-// palace_bgzf_deflate, palace_bgzf_compact; the batch loop of depthgz_device.hpp), and the .bai computed from the stream that was
+// palace_bgzf_deflate, palace_bgzf_compact; bgzf_members_device.hpp), and the .bai computed from the stream that was
 // written (bai.hpp).  The host rewrites the header and lays out the index, nothing else.  The rules are DESIGN.md 8.
 // Needs a device: there is no host path behind it.  On any failure no output file is left.
 //   -@ <n>                           host threads that inflate the header's members; otherwise ignored
 //   PALACE_DEVICE, PALACE_TRACE      as in the other tools
 //   PALACE_OPT_BAMSORT_BATCH=<n>     members per deflate batch (tests); PALACE_OPT_BAM_BATCH / PALACE_OPT_BAM_CHUNK on the input side
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <chrono>
 #include <iostream>
 
 #include "bai.hpp"
@@ -76,7 +70,17 @@ std::vector<uint8_t> rewrite_header(const std::vector<uint8_t> &in)
     return out;
 }
 
-void ck(int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); }
+// laps of a traced run
+struct Laps { double keys = 0, sort = 0, gather = 0, index = 0; MemberWriteTimes write; };
+
+// the loader's errors name the input; an out-of-room message stands alone
+template <class Load> void load_named(const std::string &in, Load load)
+{
+    try {
+        load();
+    } catch (const DeviceNoRoom &) { throw;
+    } catch (const std::exception &e) { throw std::runtime_error(in + ": " + e.what()); }
+}
 
 void require_whole(const DeviceBamStream &st)
 {
@@ -86,46 +90,40 @@ void require_whole(const DeviceBamStream &st)
 
 int main_sort(const std::string &in, const std::string &out, bool bai, int threads, bool sam, uint32_t mask)
 {
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamsort: " << palace_last_error() << "\n"; return 1; }
-    int code = 0;
-    bool out_made = false, bai_made = false;
-    FILE *f = nullptr;
-    try {
+    return with_device("bamsort", [&](palace_ctx *ctx) {
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
-        Laps laps{ctx, trace};
+        StageClock clock{ctx, trace};
+        Laps laps;
         BamDeviceTimes bt;
         SamTimes sam_tm;
         DeviceBamStream st;
-        try {
+        load_named(in, [&] {
             if (sam) load_sam_stream_device(ctx, in, mask, st, trace ? &sam_tm : nullptr);
             else load_bam_stream_device(ctx, in, threads, st, trace ? &bt : nullptr);
             require_whole(st);
-        } catch (const BamDeviceNoRoom &e) { throw;
-        } catch (const SamDeviceNoRoom &e) { throw;
-        } catch (const std::exception &e) { throw std::runtime_error(in + ": " + e.what()); }
+        });
         const size_t n = static_cast<size_t>(st.n_records);
-        BamsortDevice dev(ctx);
+        DeviceScope dev(ctx, bamsort_no_room);
 
         // the header: the one part the host touches
         std::vector<uint8_t> head(static_cast<size_t>(st.first));
         ck(palace_d2h(ctx, head.data(), st.d_stream, head.size()), "palace_d2h");
         const std::vector<uint8_t> new_head = rewrite_header(head);
 
-        laps.restart();
+        clock.restart();
         uint64_t *d_key = dev.array<uint64_t>(n, "the sort keys");
         int64_t n_bad = 0, first_bad = -1;
         ck(palace_bam_sort_keys(ctx, st.d_stream, st.total, st.d_starts, st.n_records, st.n_ref, d_key, &n_bad, &first_bad), "palace_bam_sort_keys");
         if (n_bad)
             throw std::runtime_error(in + ": record " + std::to_string(first_bad) + ": refID or pos outside what the header's " + std::to_string(st.n_ref) +
                                      " targets allow (" + std::to_string(n_bad) + " such records)");
-        laps.lap(&laps.keys);
+        clock.lap(&laps.keys, true);
         uint32_t *d_perm = dev.array<uint32_t>(n, "the permutation");
         const size_t sort_bytes = palace_sort_u64_scratch_bytes(st.n_records);
         void *d_sort = dev.alloc(sort_bytes, "the sort's scratch");
         ck(palace_sort_u64(ctx, d_key, d_perm, st.n_records, 33 + bits_of(static_cast<uint32_t>(st.n_ref)), d_sort, sort_bytes), "palace_sort_u64");
         ck(palace_sync(ctx), "palace_sync");
-        laps.lap(&laps.sort);
+        clock.lap(&laps.sort, true);
         dev.give_back(d_sort);
         dev.give_back(d_key);
 
@@ -134,11 +132,11 @@ int main_sort(const std::string &in, const std::string &out, bool bai, int threa
         int64_t out_bytes = 0;
         ck(palace_bam_gather_plan(ctx, st.d_stream, st.d_starts, d_perm, st.n_records, static_cast<int64_t>(new_head.size()), d_out_off, d_out_starts, &out_bytes),
            "palace_bam_gather_plan");
-        uint8_t *d_out = static_cast<uint8_t *>(dev.alloc(static_cast<size_t>(out_bytes) + 64, "the sorted stream"));
+        uint8_t *d_out = dev.array<uint8_t>(static_cast<size_t>(out_bytes) + 64, "the sorted stream");
         ck(palace_h2d(ctx, d_out, new_head.data(), new_head.size()), "palace_h2d");
         ck(palace_bam_gather_write(ctx, st.d_stream, st.d_starts, d_perm, d_out_off, st.n_records, out_bytes, d_out), "palace_bam_gather_write");
         ck(palace_sync(ctx), "palace_sync");
-        laps.lap(&laps.gather);
+        clock.lap(&laps.gather, true);
         st.release();                                                        // the input has been copied
         dev.give_back(d_perm);
         dev.give_back(d_out_off);
@@ -146,89 +144,57 @@ int main_sort(const std::string &in, const std::string &out, bool bai, int threa
         // the file: members of 0xff00 bytes, a batch at a time
         std::vector<int64_t> member_u, member_c;
         uint64_t file_bytes = 0;
-        f = std::fopen(out.c_str(), "wb");
-        if (!f) throw std::runtime_error("cannot open " + out + " for writing");
-        out_made = true;
-        write_members_device(ctx, d_out, out_bytes, bamsort_batch_members(), false, f, out, laps, member_u, member_c, &file_bytes);
-        const int rc_close = std::fclose(f);
-        f = nullptr;
+        OutputFiles outputs;
+        outputs.f = std::fopen(out.c_str(), "wb");
+        if (!outputs.f) throw std::runtime_error("cannot open " + out + " for writing");
+        outputs.made.push_back(out);
+        write_bam_file_device(ctx, bamsort_no_room, d_out, out_bytes, bamsort_batch_members(), false, outputs.f, out, clock, laps.write, member_u, member_c, &file_bytes);
+        const int rc_close = std::fclose(outputs.f);
+        outputs.f = nullptr;
         if (rc_close != 0) throw std::runtime_error("write failed: " + out);
-        laps.lap(&laps.copy_write);
+        clock.lap(&laps.write.copy_write, true);
 
         if (bai) {
-            laps.restart();
-            bai_made = true;
+            clock.restart();
+            outputs.made.push_back(out + ".bai");
             write_bai_device(ctx, out, d_out, d_out_starts, st.n_records, st.n_ref, member_u, member_c, out + ".bai");
-            laps.lap(&laps.index);
+            clock.lap(&laps.index, true);
         }
+        outputs.done = true;
         if (trace && sam)
             std::fprintf(stderr, "[bamsort] --sam ms: read %.1f upload %.1f lines %.1f plan %.1f encode %.1f\n", sam_tm.read, sam_tm.upload, sam_tm.lines, sam_tm.plan,
                          sam_tm.encode);
         if (trace)
             std::fprintf(stderr, "[bamsort] ms: member index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f | keys %.1f sort %.1f gather %.1f "
                          "crc+deflate %.1f copy+write %.1f index %.1f; records %lld, stream %lld B -> %lld B, file %llu B, members inflated on the host %lld\n",
-                         bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, laps.keys, laps.sort, laps.gather, laps.deflate, laps.copy_write, laps.index,
-                         static_cast<long long>(st.n_records), static_cast<long long>(st.total), static_cast<long long>(out_bytes),
+                         bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, laps.keys, laps.sort, laps.gather, laps.write.crc + laps.write.deflate,
+                         laps.write.copy_write, laps.index, static_cast<long long>(st.n_records), static_cast<long long>(st.total), static_cast<long long>(out_bytes),
                          static_cast<unsigned long long>(file_bytes), static_cast<long long>(st.host_inflated));
-    } catch (const std::exception &e) {
-        std::cerr << "bamsort: " << e.what() << "\n";
-        code = 1;
-        if (f) std::fclose(f);
-        if (out_made) std::remove(out.c_str());
-        if (bai_made) std::remove((out + ".bai").c_str());
-    }
-    palace_ctx_destroy(ctx);
-    return code;
+        return 0;
+    });
 }
 
 int main_index(const std::string &bam, const std::string &bai_path, int threads)
 {
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "bamsort: " << palace_last_error() << "\n"; return 1; }
-    int code = 0;
-    try {
+    return with_device("bamsort", [&](palace_ctx *ctx) {
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
-        Laps laps{ctx, trace};
+        StageClock clock{ctx, trace};
+        double index_ms = 0;
         BamDeviceTimes bt;
         DeviceBamStream st;
-        std::vector<int64_t> member_u, member_c;
-        try {
-            load_bam_stream_device(ctx, bam, threads, st, trace ? &bt : nullptr);
+        BamMemberTable members;                                              // the file's own member table (the loader has checked it)
+        load_named(bam, [&] {
+            load_bam_stream_device(ctx, bam, threads, st, trace ? &bt : nullptr, {}, &members);
             require_whole(st);
-            // the file's own member table (the loader has checked it)
-            const int fd = ::open(bam.c_str(), O_RDONLY);
-            struct stat sb;
-            if (fd < 0 || ::fstat(fd, &sb) != 0) { if (fd >= 0) ::close(fd); throw std::runtime_error("Failed to open BAM"); }
-            const size_t size = static_cast<size_t>(sb.st_size);
-            void *m = size ? ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE, fd, 0) : nullptr;
-            ::close(fd);
-            if (size && m == MAP_FAILED) throw std::runtime_error("Failed to read BAM");
-            struct Unmap { void *p; size_t n; ~Unmap() { if (p) ::munmap(p, n); } } unmap{m, size};
-            size_t total = 0;
-            BgzfWalkEnd end;
-            const std::vector<BgzfMember> mem = bgzf_members(static_cast<const uint8_t *>(m), size, &total, &end);
-            for (size_t i = 0; i < mem.size(); i++) {
-                member_u.push_back(static_cast<int64_t>(mem[i].out_off));
-                member_c.push_back(static_cast<int64_t>(i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : 0));
-            }
-            if (mem.empty() || mem.back().out_len != 0) {                    // no EOF member: the file's end stands for the stream's
-                member_u.push_back(static_cast<int64_t>(total));
-                member_c.push_back(static_cast<int64_t>(end.offset));
-            }
-        } catch (const BamDeviceNoRoom &e) { throw;
-        } catch (const std::exception &e) { throw std::runtime_error(bam + ": " + e.what()); }
-        laps.restart();
-        write_bai_device(ctx, bam, st.d_stream, st.d_starts, st.n_records, st.n_ref, member_u, member_c, bai_path);
-        laps.lap(&laps.index);
+        });
+        clock.restart();
+        write_bai_device(ctx, bam, st.d_stream, st.d_starts, st.n_records, st.n_ref, members.u, members.c, bai_path);
+        clock.lap(&index_ms, true);
         if (trace)
             std::fprintf(stderr, "[bamsort] index ms: member index %.1f header %.1f upload %.1f inflate %.1f crc %.1f walk %.1f | index %.1f; records %lld, stream %lld B\n",
-                         bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, laps.index, static_cast<long long>(st.n_records), static_cast<long long>(st.total));
-    } catch (const std::exception &e) {
-        std::cerr << "bamsort: " << e.what() << "\n";
-        code = 1;
-    }
-    palace_ctx_destroy(ctx);
-    return code;
+                         bt.index, bt.header, bt.upload, bt.inflate, bt.crc, bt.walk, index_ms, static_cast<long long>(st.n_records), static_cast<long long>(st.total));
+        return 0;
+    });
 }
 
 }  // namespace

@@ -23,6 +23,7 @@
 #include "../../include/palace_hip.h"
 #include "bam_device.hpp"
 #include "bgzf.hpp"
+#include "device_scope.hpp"
 #include "fastx.hpp"
 
 namespace palace_host {
@@ -158,16 +159,11 @@ inline void read_depth_plain(DepthReader &rd, palace_ctx *ctx, const MappedText 
 {
     const int64_t W = depthin_window_bytes(), N = static_cast<int64_t>(t.size);
     rd.init(std::min(W, std::max<int64_t>(N, 16)));
-    void *pin[2] = {nullptr, nullptr}, *d_text[2] = {nullptr, nullptr};
-    struct Free {
-        palace_ctx *c; void **pin, **dev;
-        ~Free() { for (int k = 0; k < 2; k++) { if (pin[k]) palace_host_free(c, pin[k]); if (dev[k]) palace_free(c, dev[k]); } }
-    } free_{ctx, pin, d_text};
     const size_t bytes = static_cast<size_t>(std::min(W, std::max<int64_t>(N, 16)));
-    for (int k = 0; k < 2; k++) {
-        rd.ck(palace_host_alloc(ctx, bytes, &pin[k]), "page-locked staging");
-        rd.ck(palace_malloc(ctx, bytes + 64, &d_text[k]), "text window");
-    }
+    const PinnedBuffer pin0(ctx, bytes, "device error (page-locked staging)"), pin1(ctx, bytes, "device error (page-locked staging)");
+    void *const pin[2] = {pin0.p, pin1.p};
+    DeviceScope dev(ctx, no_room_device_error);
+    void *const d_text[2] = {dev.alloc(bytes + 64, "text window"), dev.alloc(bytes + 64, "text window")};
     int64_t p = 0;
     int b = 0;
     int64_t n = std::min(W, N - p);
@@ -200,11 +196,9 @@ inline void read_depth_bgzf(DepthReader &rd, palace_ctx *ctx, const MappedText &
     }
     cut.push_back(mem.size());
     rd.init(static_cast<int64_t>(batch_out));
-    void *d_in = nullptr, *d_batch = nullptr, *d_meta = nullptr;
-    rd.ck(palace_malloc(ctx, static_cast<size_t>(max_in) + 64, &d_in), "compressed batch");
-    rd.ck(palace_malloc(ctx, static_cast<size_t>(batch_out) + 64, &d_batch), "inflated batch");
-    rd.ck(palace_malloc(ctx, MemberTable::kBytes, &d_meta), "member table");
-    struct Free { palace_ctx *c; void *a, *b, *m; ~Free() { palace_free(c, a); palace_free(c, b); palace_free(c, m); } } free_{ctx, d_in, d_batch, d_meta};
+    DeviceScope dev(ctx, no_room_device_error);
+    void *d_in = dev.alloc(static_cast<size_t>(max_in) + 64, "compressed batch"), *d_batch = dev.alloc(static_cast<size_t>(batch_out) + 64, "inflated batch");
+    void *d_meta = dev.alloc(MemberTable::kBytes, "member table");
     MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
     std::vector<uint8_t> host_out(65536);
     for (size_t k = 0; k + 1 < cut.size(); k++) {

@@ -5,8 +5,11 @@
 // start-up is most of eref's wall time), and the chosen device is ordinal 0 of the process.
 #pragma once
 #include <cstdlib>
+#include <exception>
+#include <iostream>
 #include <string>
 
+#include "../../include/palace_hip.h"
 #include "fast_exit.hpp"
 
 namespace palace_host {
@@ -25,6 +28,20 @@ inline int pick_device()
         return 0;
     }();
     return chosen;
+}
+
+// The frame of an executable that works on one device: the context on the picked device, body(ctx) -> exit code, the context
+// destroyed.  A context that cannot be made, or an exception from the body, is `<prog>: <message>` on stderr and exit code 1.
+template <class Body> int with_device(const char *prog, Body body)
+{
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << prog << ": " << palace_last_error() << "\n"; return 1; }
+    int code = 1;
+    try {
+        code = body(ctx);
+    } catch (const std::exception &e) { std::cerr << prog << ": " << e.what() << "\n"; }
+    palace_ctx_destroy(ctx);
+    return code;
 }
 
 }  // namespace palace_host

@@ -1,0 +1,344 @@
+// device_scope.hpp, mapped_file.hpp and the member writer's arithmetic on their own (tests/test_host_device_scope.py; also built
+// with the host sanitizers).  No device and no libpalace_hip.so: the few palace_* calls the headers make are stubs here that count
+// their calls, remember what is live and can be told to fail.  `device_scope_selftest <scratch directory>` prints one line per
+// failed check and `ok <checks>` at the end; exit code 1 if any check failed.
+#include <zlib.h>
+
+#include <algorithm>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <fstream>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "bai.hpp"
+#include "bam_stream_device.hpp"
+#include "bgzf_members_device.hpp"
+#include "device_scope.hpp"
+#include "mapped_file.hpp"
+#include "sam_device.hpp"
+
+using namespace palace_host;
+
+namespace {
+
+struct Stub {
+    int mallocs = 0, frees = 0, host_allocs = 0, host_frees = 0, copies = 0, syncs = 0, destroys = 0, bad_frees = 0;
+    int fail_malloc = 0;                            // the k-th palace_malloc from now fails (0: none)
+    bool fail_sync = false, fail_host_alloc = false;
+    std::map<void *, size_t> live, live_host;      // pointer -> bytes asked for
+    std::vector<size_t> asked;
+    void reset() { *this = Stub(); }
+} stub;
+const char *kErr = "out of memory (stub)";
+
+int checks = 0, failed = 0;
+#define CHECK(cond)                                                               \
+    do {                                                                          \
+        checks++;                                                                 \
+        if (!(cond)) { failed++; std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond); } \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+const char *palace_last_error(void) { return kErr; }
+int palace_malloc(palace_ctx *, size_t bytes, void **d_out)
+{
+    stub.mallocs++;
+    stub.asked.push_back(bytes);
+    if (stub.fail_malloc && --stub.fail_malloc == 0) return -1;
+    *d_out = std::malloc(bytes);
+    stub.live[*d_out] = bytes;
+    return 0;
+}
+int palace_free(palace_ctx *, void *p)
+{
+    stub.frees++;
+    if (!stub.live.erase(p)) { stub.bad_frees++; return -1; }
+    std::free(p);
+    return 0;
+}
+int palace_host_alloc(palace_ctx *, size_t bytes, void **h_out)
+{
+    stub.host_allocs++;
+    if (stub.fail_host_alloc) return -1;
+    *h_out = std::malloc(bytes ? bytes : 1);
+    stub.live_host[*h_out] = bytes;
+    return 0;
+}
+int palace_host_free(palace_ctx *, void *p)
+{
+    stub.host_frees++;
+    if (!stub.live_host.erase(p)) { stub.bad_frees++; return -1; }
+    std::free(p);
+    return 0;
+}
+int palace_h2d(palace_ctx *, void *d_dst, const void *h_src, size_t bytes)
+{
+    stub.copies++;
+    std::memcpy(d_dst, h_src, bytes);
+    return 0;
+}
+int palace_sync(palace_ctx *) { stub.syncs++; return stub.fail_sync ? -1 : 0; }
+int palace_bam_names_destroy(palace_ctx *, palace_bam_names *) { stub.destroys++; return 0; }
+int palace_fasta_names_destroy(palace_ctx *, palace_fasta_names *) { stub.destroys++; return 0; }
+int palace_depth_text_destroy(palace_ctx *, palace_depth_text *) { stub.destroys++; return 0; }
+}
+
+namespace {
+
+palace_ctx *const ctx = nullptr;                    // (the stubs never look at it)
+
+// the out-of-room texts the executables print, written out in full: --bam-gpu, bamsort, the SAM front end, split_fastg / make_fa_from_path,
+// the depth file writer, and the readers of depth_read.hpp / fastq_gz.hpp
+struct Style { const char *name; NoRoomText text; std::string (*want)(const std::string &bytes, const std::string &what); };
+const Style kStyles[] = {
+    {"bam-gpu", bam_gpu_no_room, [](const std::string &b, const std::string &w) {
+         return "--bam-gpu keeps the whole inflated BAM on the device and cannot allocate " + b + " bytes for " + w +
+                " (out of memory (stub)); run without --bam-gpu to load the BAM on the host";
+     }},
+    {"bamsort", bamsort_no_room, [](const std::string &b, const std::string &w) {
+         return "the inflated BAM, the sorted stream, the per-record arrays and one batch of members are kept on the device, and " + b + " bytes for " + w +
+                " cannot be allocated (out of memory (stub)); there is no host path, a BAM larger than device memory is out of scope";
+     }},
+    {"sam", sam_no_room, [](const std::string &b, const std::string &w) {
+         return "the SAM text, the BAM stream, 24 bytes per line and 8 per record are kept on the device, and " + b + " bytes for " + w +
+                " cannot be allocated (out of memory (stub)); there is no host path, a text larger than device memory is out of scope";
+     }},
+    {"does-not-fit", no_room_does_not_fit, [](const std::string &b, const std::string &w) { return w + " (" + b + " bytes) does not fit the device: out of memory (stub)"; }},
+    {"plain", no_room_plain, [](const std::string &, const std::string &) { return std::string("palace_malloc: out of memory (stub)"); }},
+    {"device-error", no_room_device_error, [](const std::string &, const std::string &w) { return "device error (" + w + "): out of memory (stub)"; }},
+};
+
+int failing_call() { return -1; }
+
+void test_scope()
+{
+    const int N = 6;
+    {   // leaves normally: every pointer freed exactly once
+        stub.reset();
+        {
+            DeviceScope dev(ctx);
+            for (int i = 1; i <= N; i++) dev.alloc(static_cast<size_t>(100 * i), "the thing");
+            CHECK(stub.mallocs == N && stub.frees == 0 && stub.live.size() == static_cast<size_t>(N));
+        }
+        CHECK(stub.frees == N && stub.live.empty() && stub.bad_frees == 0);
+    }
+    for (const Style &s : kStyles)
+        for (int k = 1; k <= N; k++) {   // the k-th allocation fails: the k - 1 before it are freed exactly once, the text is the style's
+            stub.reset();
+            stub.fail_malloc = k;
+            bool no_room = false;
+            std::string text;
+            try {
+                DeviceScope dev(ctx, s.text);
+                for (int i = 1; i <= N; i++) dev.alloc(static_cast<size_t>(100 * i), "the thing");
+            } catch (const DeviceNoRoom &e) { no_room = true; text = e.what(); }
+            CHECK(no_room);
+            CHECK(text == s.want(std::to_string(100 * k), "the thing"));
+            CHECK(stub.mallocs == k && stub.frees == k - 1 && stub.live.empty() && stub.bad_frees == 0);
+        }
+    {   // give_back, keep, keep_all, zero bytes, array, upload
+        stub.reset();
+        void *kept = nullptr, *kept2[2] = {nullptr, nullptr};
+        {
+            DeviceScope dev(ctx);
+            void *a = dev.alloc(10, "a");
+            kept = dev.alloc(20, "b");
+            void *z = dev.alloc(0, "nothing");
+            CHECK(stub.asked.back() == 1 && z != nullptr);
+            int32_t *arr = dev.array<int32_t>(7, "seven");
+            CHECK(stub.asked.back() == 28 && arr != nullptr);
+            const int64_t src[3] = {5, -6, 7};
+            const int64_t *up = dev.upload(src, 3, "three");
+            CHECK(stub.asked.back() == 24 && stub.copies == 1 && std::memcmp(up, src, 24) == 0);
+            dev.upload(src, 0, "none");
+            CHECK(stub.asked.back() == 1 && stub.copies == 1);
+            dev.give_back(a);
+            CHECK(stub.frees == 1 && !stub.live.count(a));
+            dev.keep(kept);
+            CHECK(stub.frees == 1 && stub.live.count(kept));
+        }
+        CHECK(stub.mallocs == 6 && stub.frees == 5 && stub.live.size() == 1 && stub.live.count(kept) && stub.bad_frees == 0);
+        {
+            DeviceScope dev(ctx);
+            kept2[0] = dev.alloc(1, "x");
+            kept2[1] = dev.alloc(2, "y");
+            dev.keep_all();
+        }
+        CHECK(stub.frees == 5 && stub.live.size() == 3);
+        for (void *p : {kept, kept2[0], kept2[1]}) palace_free(ctx, p);
+        CHECK(stub.live.empty() && stub.bad_frees == 0);
+    }
+    {   // names: one blob, n + 1 offsets
+        stub.reset();
+        {
+            DeviceScope dev(ctx);
+            const DeviceNames d = upload_names(dev, {"a", "", "chr2"}, "the names", "names");
+            const int64_t want[4] = {0, 1, 1, 5};
+            CHECK(std::memcmp(d.blob, "achr2", 5) == 0 && std::memcmp(d.off, want, 32) == 0 && stub.asked == (std::vector<size_t>{5, 32}));
+            const DeviceNames e = upload_names(dev, {}, "the names", "names");
+            CHECK(e.off[0] == 0 && e.blob != nullptr && stub.asked == (std::vector<size_t>{5, 32, 1, 8}));
+        }
+        CHECK(stub.live.empty() && stub.frees == 4 && stub.bad_frees == 0);
+    }
+    {   // ck: today's text
+        std::string text;
+        try { ck(-1, "palace_whatever"); } catch (const std::runtime_error &e) { text = e.what(); }
+        CHECK(text == "palace_whatever: out of memory (stub)");
+        ck(0, "fine");
+        text.clear();
+        try { HIP_OK(failing_call()); } catch (const Failure &e) { text = e.what(); }
+        CHECK(text == "failing_call() failed: out of memory (stub)");
+    }
+}
+
+void test_guards()
+{
+    stub.reset();
+    {
+        PinnedBuffer pin(ctx, 4096);
+        CHECK(pin.p != nullptr && stub.host_allocs == 1 && stub.host_frees == 0 && stub.live_host.size() == 1);
+    }
+    CHECK(stub.host_frees == 1 && stub.live_host.empty() && stub.bad_frees == 0);
+    stub.fail_host_alloc = true;
+    std::string text;
+    try { PinnedBuffer pin(ctx, 4096, "no pinned memory for an output window"); } catch (const std::runtime_error &e) { text = e.what(); }
+    CHECK(text == "no pinned memory for an output window: out of memory (stub)" && stub.host_frees == 1);
+
+    stub.reset();
+    int thing = 0;
+    { BamNamesHandle h(ctx); }
+    { FastaNamesHandle h(ctx); }
+    { DepthTextHandle h(ctx); }
+    CHECK(stub.destroys == 0);                      // a handle that was never made is not destroyed
+    { BamNamesHandle h(ctx); h.h = reinterpret_cast<palace_bam_names *>(&thing); }
+    CHECK(stub.destroys == 1);
+    { FastaNamesHandle h(ctx); h.h = reinterpret_cast<palace_fasta_names *>(&thing); }
+    CHECK(stub.destroys == 2);
+    { DepthTextHandle h(ctx); h.h = reinterpret_cast<palace_depth_text *>(&thing); }
+    CHECK(stub.destroys == 3);
+}
+
+void test_clock()
+{
+    stub.reset();
+    double acc = 0;
+    StageClock off{ctx, false};
+    off.restart();
+    off.lap(&acc, true);
+    off.lap(&acc, false);
+    CHECK(stub.syncs == 0 && acc == 0);
+    StageClock on{ctx, true};
+    on.restart();
+    for (int i = 0; i < 3; i++) on.lap(&acc, true);
+    CHECK(stub.syncs == 3 && acc >= 0);
+    on.lap(&acc, false);
+    CHECK(stub.syncs == 3);
+    stub.fail_sync = true;
+    std::string text;
+    try { on.lap(&acc, true); } catch (const std::runtime_error &e) { text = e.what(); }
+    CHECK(text == "palace_sync: out of memory (stub)");
+    stub.syncs = 0;
+    off.lap(&acc, true);                            // (off: not even asked)
+    CHECK(stub.syncs == 0);
+}
+
+void test_mapped_file(const std::string &dir)
+{
+    const std::string missing = dir + "/missing", empty = dir + "/empty", big = dir + "/big";
+    for (int bam = 0; bam < 2; bam++) {
+        std::string text;
+        try {
+            if (bam) { MappedFile f(missing, MapHint::sequential, "Failed to open BAM ", "Failed to read BAM "); }
+            else { MappedText f(missing); }
+        } catch (const std::runtime_error &e) { text = e.what(); }
+        CHECK(text == (bam ? "Failed to open BAM " : "cannot open ") + missing);
+    }
+    { std::ofstream f(empty, std::ios::binary); }
+    for (MapHint hint : {MapHint::none, MapHint::populate, MapHint::sequential}) {
+        MappedFile f(empty, hint);
+        CHECK(f.size == 0 && f.data == nullptr && f.bytes() == nullptr);
+    }
+    std::string content(70000, '\0');
+    for (size_t i = 0; i < content.size(); i++) content[i] = static_cast<char>((i * 2654435761u) >> 13);
+    { std::ofstream f(big, std::ios::binary); f.write(content.data(), static_cast<std::streamsize>(content.size())); }
+    for (MapHint hint : {MapHint::none, MapHint::populate, MapHint::sequential}) {
+        MappedFile f;
+        f.open(big, hint);
+        CHECK(f.size == content.size() && std::memcmp(f.data, content.data(), content.size()) == 0);
+    }
+}
+
+void test_member_arithmetic()
+{
+    const uint64_t T = 0xff00;
+    for (uint64_t size : {uint64_t{0}, uint64_t{1}, T - 1, T, T + 1, 2 * T})
+        for (size_t cap : {size_t{1}, size_t{3}, size_t{8192}}) {
+            const size_t n = bgzf_member_count(size), batch = bgzf_batch_members(n, cap);
+            CHECK(n == (size + T - 1) / T);
+            CHECK(batch >= 1 && batch <= cap && (n == 0 || batch <= n));
+            std::vector<int32_t> lens(batch);
+            uint64_t sum = 0, at = 0;
+            size_t members = 0;
+            for (size_t m0 = 0; m0 < n; m0 += batch) {
+                const MemberBatch b = bgzf_batch(size, n, batch, m0, lens.data());
+                CHECK(b.nm == (n - m0 < batch ? n - m0 : batch));
+                CHECK(b.t_beg == at && b.t_beg == m0 * T);
+                CHECK(b.t_end == (size < (m0 + b.nm) * T ? size : (m0 + b.nm) * T));
+                for (size_t k = 0; k < b.nm; k++) {
+                    const bool last = m0 + k + 1 == n;
+                    CHECK(lens[k] > 0 && static_cast<uint64_t>(lens[k]) <= T);
+                    CHECK(last ? static_cast<uint64_t>(lens[k]) == size - (n - 1) * T : static_cast<uint64_t>(lens[k]) == T);
+                    sum += static_cast<uint64_t>(lens[k]);
+                }
+                at = b.t_end;
+                members += b.nm;
+            }
+            CHECK(members == n && sum == size && at == size);
+        }
+}
+
+void test_stored_member()
+{
+    for (uint32_t len : {0u, 1u, 0xff00u}) {
+        std::vector<uint8_t> data(len);
+        for (uint32_t i = 0; i < len; i++) data[i] = static_cast<uint8_t>((i * 40503u) >> 7);
+        const uint32_t crc = static_cast<uint32_t>(::crc32(::crc32(0L, Z_NULL, 0), data.data(), len));
+        std::vector<uint8_t> m{0xaa};                // (appended: what is there stays)
+        append_stored_member(m, data.data(), len, crc);
+        CHECK(m[0] == 0xaa && m.size() == 1 + 18 + 5 + len + 8);
+        const size_t total = m.size() - 1;
+        CHECK((m[17] | (m[18] << 8)) == static_cast<int>(total - 1));            // BSIZE
+        uint32_t got_crc, got_len;
+        std::memcpy(&got_crc, m.data() + m.size() - 8, 4);
+        std::memcpy(&got_len, m.data() + m.size() - 4, 4);
+        CHECK(got_crc == crc && got_len == len);
+        z_stream zs{};
+        CHECK(inflateInit2(&zs, 15 + 16) == Z_OK);                               // a gzip member: zlib checks CRC-32 and ISIZE itself
+        std::vector<uint8_t> out(len + 1);
+        zs.next_in = m.data() + 1; zs.avail_in = static_cast<uInt>(total);
+        zs.next_out = out.data(); zs.avail_out = static_cast<uInt>(out.size());
+        CHECK(inflate(&zs, Z_FINISH) == Z_STREAM_END);
+        CHECK(zs.total_out == len && zs.avail_in == 0 && std::equal(data.begin(), data.end(), out.begin()));
+        inflateEnd(&zs);
+    }
+}
+
+}  // namespace
+
+int main(int argc, char **argv)
+{
+    if (argc != 2) { std::fprintf(stderr, "usage: device_scope_selftest <scratch directory>\n"); return 2; }
+    test_scope();
+    test_guards();
+    test_clock();
+    test_mapped_file(argv[1]);
+    test_member_arithmetic();
+    test_stored_member();
+    std::printf("%s %d\n", failed ? "failed" : "ok", checks);
+    return failed ? 1 : 0;
+}

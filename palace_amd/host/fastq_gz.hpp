@@ -29,6 +29,7 @@
 
 #include "../../include/palace_hip.h"
 #include "bam_device.hpp"
+#include "device_scope.hpp"
 #include "fastx.hpp"
 
 namespace palace_host {
@@ -184,11 +185,9 @@ inline void ingest_bgzf(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t,
         max_in = std::max<uint64_t>(max_in, mem[i].in_off + mem[i].in_len + 8 - member_start(cut.back()));
     }
     cut.push_back(mem.size());
-    void *d_in = nullptr, *d_batch = nullptr, *d_meta = nullptr;
-    rs.ck(palace_malloc(ctx, static_cast<size_t>(max_in) + 64, &d_in), "compressed window");
-    rs.ck(palace_malloc(ctx, static_cast<size_t>(batch_out) + 64, &d_batch), "inflated window");
-    rs.ck(palace_malloc(ctx, MemberTable::kBytes, &d_meta), "member table");
-    struct Free { palace_ctx *c; void *a, *b, *m; ~Free() { palace_free(c, a); palace_free(c, b); palace_free(c, m); } } free_{ctx, d_in, d_batch, d_meta};
+    DeviceScope dev(ctx, no_room_device_error);
+    void *d_in = dev.alloc(static_cast<size_t>(max_in) + 64, "compressed window"), *d_batch = dev.alloc(static_cast<size_t>(batch_out) + 64, "inflated window");
+    void *d_meta = dev.alloc(MemberTable::kBytes, "member table");
     MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
     std::vector<uint8_t> host_out(65536);
     uint64_t file_pos = 0;

@@ -13,7 +13,22 @@
 #include <thread>
 #include <vector>
 
+#include "../../include/palace_hip.h"
+
 namespace palace_host {
+
+// what the device's FASTA index found wrong with a text (PALACE_FASTA_E*, csrc/path_fasta.hip)
+inline const char *fasta_fault_text(int code)
+{
+    switch (code) {
+    case PALACE_FASTA_ETEXT: return "text before the first '>'";
+    case PALACE_FASTA_ENAME: return "a header line without a name";
+    case PALACE_FASTA_ERAGGED: return "a sequence line behind a line of another length than the record's first (only a record's last line may be shorter)";
+    case PALACE_FASTA_EBLANK: return "a sequence line behind a blank line of its record";
+    case PALACE_FASTA_EBYTE: return "a sequence byte outside 0x21-0x7E";
+    }
+    return "malformed";
+}
 
 struct SeqSet {
     std::vector<uint8_t> bases;
@@ -198,39 +213,13 @@ inline void parse_fasta_mt(const char *txt, size_t N, SeqSet &out, int threads)
 // sequence lines to their final place in a staging buffer.  Same getline semantics as parse_fastq above.
 // ------------------------------------------------------------------------------------------------
 #include <emmintrin.h>
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <atomic>
 #include <functional>
 
-namespace palace_host {
+#include "mapped_file.hpp"
 
-struct MappedText {
-    const char *data = nullptr;
-    size_t size = 0;
-    MappedText() = default;
-    explicit MappedText(const std::string &path) { open(path); }
-    void open(const std::string &path)
-    {
-        int fd = ::open(path.c_str(), O_RDONLY);
-        if (fd < 0) throw std::runtime_error("cannot open " + path);
-        struct stat st;
-        if (::fstat(fd, &st) != 0) { ::close(fd); throw std::runtime_error("cannot open " + path); }
-        size = static_cast<size_t>(st.st_size);
-        if (size) {
-            void *m = ::mmap(nullptr, size, PROT_READ, MAP_PRIVATE | MAP_POPULATE, fd, 0);
-            if (m == MAP_FAILED) { ::close(fd); throw std::runtime_error("cannot read " + path); }
-            data = static_cast<const char *>(m);
-        }
-        ::close(fd);
-    }
-    ~MappedText() { if (data) ::munmap(const_cast<char *>(data), size); }
-    MappedText(const MappedText &) = delete;
-    MappedText &operator=(const MappedText &) = delete;
-};
+namespace palace_host {
 
 // run f(i) for i in [0, n) on `threads` threads (dynamic hand-out, small n per call is fine)
 inline void pool_for(size_t n, int threads, const std::function<void(size_t)> &f)

@@ -250,11 +250,10 @@ struct DeviceColumns {
 void decode_on_device(palace_ctx *ctx, const DeviceBamStream &st, const std::vector<std::string> &names, uint64_t seed, DeviceColumns &out,
                       BamDeviceTimes *times)
 {
-    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
     BamDeviceTimes unused;
     BamDeviceTimes &tm = times ? *times : unused;
-    BamDeviceClock clock{ctx, times != nullptr};
-    DeviceOwner own(ctx);
+    StageClock clock{ctx, times != nullptr};
+    DeviceScope own(ctx, bam_gpu_no_room);
     const size_t n = static_cast<size_t>(st.n_records);
     auto col32 = [&] { return static_cast<int32_t *>(own.alloc(n * 4, "the record columns")); };
     palace_bam_cols &c = out.cols;
@@ -269,18 +268,10 @@ void decode_on_device(palace_ctx *ctx, const DeviceBamStream &st, const std::vec
     ck(palace_bam_columns(ctx, st.d_stream, st.total, st.d_starts, st.n_records, seed, &c), "palace_bam_columns");
     clock.lap(&tm.columns, true);
     // the header's names for the SA items' look-up: one blob, offsets, the table built from them on the device
-    std::vector<int64_t> off(names.size() + 1, 0);
-    for (size_t t = 0; t < names.size(); t++) off[t + 1] = off[t] + static_cast<int64_t>(names[t].size());
-    std::string blob;
-    blob.reserve(static_cast<size_t>(off.back()));
-    for (const std::string &nm : names) blob += nm;
-    uint8_t *d_blob = static_cast<uint8_t *>(own.alloc(blob.size(), "the contig names"));
-    int64_t *d_off = static_cast<int64_t *>(own.alloc(off.size() * 8, "the contig names"));
-    ck(palace_h2d(ctx, d_blob, blob.data(), blob.size()), "contig names");
-    ck(palace_h2d(ctx, d_off, off.data(), off.size() * 8), "contig names");
-    palace_bam_names *table = nullptr;
-    ck(palace_bam_names_create(ctx, d_blob, d_off, static_cast<int32_t>(names.size()), &table), "palace_bam_names_create");
-    struct Table { palace_ctx *ctx; palace_bam_names *t; ~Table() { palace_bam_names_destroy(ctx, t); } } table_guard{ctx, table};
+    const DeviceNames d_names = upload_names(own, names, "the contig names", "contig names");
+    BamNamesHandle table_guard(ctx);
+    ck(palace_bam_names_create(ctx, d_names.blob, d_names.off, static_cast<int32_t>(names.size()), &table_guard.h), "palace_bam_names_create");
+    palace_bam_names *const table = table_guard.h;
     ck(palace_bam_sa_items(ctx, st.d_stream, st.total, st.d_starts, st.n_records, table, nullptr, nullptr, 0, &out.n_sa), "palace_bam_sa_items");
     out.d_sa = static_cast<palace_sa_item *>(own.alloc(static_cast<size_t>(out.n_sa) * sizeof(palace_sa_item), "the SA items"));
     int64_t again = 0;
@@ -288,8 +279,8 @@ void decode_on_device(palace_ctx *ctx, const DeviceBamStream &st, const std::vec
     if (again != out.n_sa) throw std::runtime_error("palace_bam_sa_items: two counts of one stream differ");
     ck(palace_sync(ctx), "palace_sync");
     clock.lap(&tm.sa, true);
-    own.give_back(d_blob);                                                   // (the table goes with table_guard, behind the sync)
-    own.give_back(d_off);
+    own.give_back(d_names.blob);                                             // (the table goes with table_guard, behind the sync)
+    own.give_back(d_names.off);
     own.keep_all();
 }
 

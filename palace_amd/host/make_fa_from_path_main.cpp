@@ -16,6 +16,7 @@
 
 #include "../../include/palace_hip.h"
 #include "device_pick.hpp"
+#include "device_scope.hpp"
 #include "fast_exit.hpp"
 #include "fastx.hpp"
 #include "path_tokens.hpp"
@@ -24,90 +25,56 @@
 
 namespace {
 
-struct Failure : std::runtime_error { using std::runtime_error::runtime_error; };
-
-#define HIP_OK(call)                                                                     \
-    do {                                                                                 \
-        if ((call) != PALACE_OK) throw Failure(std::string(#call " failed: ") + palace_last_error()); \
-    } while (0)
-
-// device memory that goes with its scope
-struct Dev {
-    palace_ctx *ctx;
-    void *p = nullptr;
-    Dev(palace_ctx *c, size_t bytes, const char *what) : ctx(c)
-    {
-        if (palace_malloc(ctx, bytes ? bytes : 1, &p) != PALACE_OK)
-            throw Failure(std::string(what) + " (" + std::to_string(bytes) + " bytes) does not fit the device: " + palace_last_error());
-    }
-    ~Dev() { if (p) palace_free(ctx, p); }
-    Dev(const Dev &) = delete;
-    Dev &operator=(const Dev &) = delete;
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-template <class T>
-std::unique_ptr<Dev> uploaded(palace_ctx *ctx, const T *src, size_t count, const char *what)
-{
-    auto d = std::make_unique<Dev>(ctx, count * sizeof(T), what);
-    if (count) HIP_OK(palace_h2d(ctx, d->p, src, count * sizeof(T)));
-    return d;
-}
-
-const char *fault_text(int code)
-{
-    switch (code) {
-    case PALACE_FASTA_ETEXT: return "text before the first '>'";
-    case PALACE_FASTA_ENAME: return "a header line without a name";
-    case PALACE_FASTA_ERAGGED: return "a sequence line behind a line of another length than the record's first (only a record's last line may be shorter)";
-    case PALACE_FASTA_EBLANK: return "a sequence line behind a blank line of its record";
-    case PALACE_FASTA_EBYTE: return "a sequence byte outside 0x21-0x7E";
-    }
-    return "malformed";
-}
+using palace_host::Failure;
+using palace_host::DeviceScope;
+using palace_host::fasta_fault_text;
 
 // the assembly on the device: text, index, names
 struct Assembly {
     palace_ctx *ctx;
     std::string path;
     palace_host::MappedText text;
-    std::unique_ptr<Dev> d_text, d_recs;
-    palace_fasta_names *names = nullptr;
+    DeviceScope dev;
+    palace_host::FastaNamesHandle names;
+    const uint8_t *d_text = nullptr;
+    palace_fasta_rec *d_recs = nullptr;
     int64_t n_records = 0;
 
-    Assembly(palace_ctx *c, const std::string &fasta, palace_host::Trace &tr) : ctx(c), path(fasta)
+    Assembly(palace_ctx *c, const std::string &fasta, palace_host::Trace &tr) : ctx(c), path(fasta), dev(c, palace_host::no_room_does_not_fit), names(c)
     {
         try { text.open(fasta); }
         catch (const std::exception &) { throw Failure("cannot open " + fasta); }
         tr.lap("FASTA read");
         const int64_t n = static_cast<int64_t>(text.size);
-        d_text = uploaded(ctx, reinterpret_cast<const uint8_t *>(text.data), text.size, "the FASTA is read on the device and has no other path: it");
+        d_text = dev.upload(text.bytes(), text.size, "the FASTA is read on the device and has no other path: it");
         tr.lap("FASTA uploaded");
-        Dev scratch(ctx, palace_fasta_index_scratch_bytes(n), "the index's scratch");
+        const size_t sb = palace_fasta_index_scratch_bytes(n);
+        void *d_scratch = dev.alloc(sb, "the index's scratch");
         palace_fasta_status st{};
-        HIP_OK(palace_fasta_index(ctx, d_text->as<uint8_t>(), n, nullptr, 0, scratch.p, palace_fasta_index_scratch_bytes(n), &st));      // how many records
-        d_recs = std::make_unique<Dev>(ctx, static_cast<size_t>(st.n_records) * sizeof(palace_fasta_rec), "the FASTA's index");
-        HIP_OK(palace_fasta_index(ctx, d_text->as<uint8_t>(), n, d_recs->as<palace_fasta_rec>(), st.n_records, scratch.p, palace_fasta_index_scratch_bytes(n), &st));
-        if (st.error) throw Failure(fasta + ": line " + std::to_string(st.bad_line) + ": " + fault_text(st.error));
+        HIP_OK(palace_fasta_index(ctx, d_text, n, nullptr, 0, d_scratch, sb, &st));                                  // how many records
+        d_recs = dev.array<palace_fasta_rec>(static_cast<size_t>(st.n_records), "the FASTA's index");
+        HIP_OK(palace_fasta_index(ctx, d_text, n, d_recs, st.n_records, d_scratch, sb, &st));
+        if (st.error) throw Failure(fasta + ": line " + std::to_string(st.bad_line) + ": " + fasta_fault_text(st.error));
         n_records = st.n_records;
         tr.lap("FASTA indexed");
-        Dev dup(ctx, static_cast<size_t>(n_records), "the duplicate flags");
-        HIP_OK(palace_fasta_names_create(ctx, d_text->as<uint8_t>(), d_recs->as<palace_fasta_rec>(), n_records, dup.as<uint8_t>(), &names));
+        uint8_t *d_dup = dev.array<uint8_t>(static_cast<size_t>(n_records), "the duplicate flags");
+        HIP_OK(palace_fasta_names_create(ctx, d_text, d_recs, n_records, d_dup, &names.h));
         std::vector<uint8_t> h_dup(static_cast<size_t>(n_records));
-        if (n_records) HIP_OK(palace_d2h(ctx, h_dup.data(), dup.p, h_dup.size()));
+        if (n_records) HIP_OK(palace_d2h(ctx, h_dup.data(), d_dup, h_dup.size()));
         size_t k = 0;
         for (; k < h_dup.size() && !h_dup[k]; k++) {}
         if (k < h_dup.size()) {                                             // (rare: the records come to the host only to name them)
             std::vector<palace_fasta_rec> recs(h_dup.size());
-            HIP_OK(palace_d2h(ctx, recs.data(), d_recs->p, recs.size() * sizeof(palace_fasta_rec)));
+            HIP_OK(palace_d2h(ctx, recs.data(), d_recs, recs.size() * sizeof(palace_fasta_rec)));
             for (; k < h_dup.size(); k++)
                 if (h_dup[k])
                     std::fprintf(stderr, "make_fa_from_path: warning: %s: sequence name '%.*s' appears again in record %zu: the first one is used\n", fasta.c_str(),
                                  static_cast<int>(recs[k].name_len), text.data + recs[k].name_off, k + 1);
         }
+        dev.give_back(d_scratch);
+        dev.give_back(d_dup);
         tr.lap("names hashed");
     }
-    ~Assembly() { if (names) palace_fasta_names_destroy(ctx, names); }
 };
 
 int64_t window_bytes()
@@ -135,12 +102,13 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
     const int64_t n_tok = static_cast<int64_t>(tk.tokens()), n_paths = static_cast<int64_t>(tk.lines());
     tr.lap("paths split");
 
-    auto d_tok = uploaded(ctx, reinterpret_cast<const uint8_t *>(tk.clean.data()), tk.clean.size(), "the tokens");
-    auto d_tok_off = uploaded(ctx, tk.clean_off.data(), tk.clean_off.size(), "the tokens' offsets");
-    Dev d_code(ctx, static_cast<size_t>(n_tok) * sizeof(int32_t), "the tokens' records");
-    HIP_OK(palace_path_resolve(ctx, as.names, d_tok->as<uint8_t>(), d_tok_off->as<int64_t>(), n_tok, d_code.as<int32_t>()));
+    DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
+    const uint8_t *d_tok = dev.upload(reinterpret_cast<const uint8_t *>(tk.clean.data()), tk.clean.size(), "the tokens");
+    const int64_t *d_tok_off = dev.upload(tk.clean_off.data(), tk.clean_off.size(), "the tokens' offsets");
+    int32_t *d_code = dev.array<int32_t>(static_cast<size_t>(n_tok), "the tokens' records");
+    HIP_OK(palace_path_resolve(ctx, as.names.h, d_tok, d_tok_off, n_tok, d_code));
     std::vector<int32_t> code(static_cast<size_t>(n_tok));
-    if (n_tok) HIP_OK(palace_d2h(ctx, code.data(), d_code.p, code.size() * sizeof(int32_t)));
+    if (n_tok) HIP_OK(palace_d2h(ctx, code.data(), d_code, code.size() * sizeof(int32_t)));
     for (int64_t l = 0; l < n_paths; l++)
         for (int64_t t = tk.line_tok[static_cast<size_t>(l)]; t < tk.line_tok[static_cast<size_t>(l) + 1]; t++) {
             const int32_t c = code[static_cast<size_t>(t)];
@@ -160,13 +128,12 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
         }
     tr.lap("tokens resolved");
 
-    auto d_path_off = uploaded(ctx, tk.line_tok.data(), tk.line_tok.size(), "the paths' tokens");
-    Dev d_cum(ctx, static_cast<size_t>(n_tok + 1) * sizeof(int64_t), "the tokens' places");
-    Dev d_len(ctx, static_cast<size_t>(n_paths) * sizeof(int64_t), "the paths' lengths");
-    HIP_OK(palace_path_fasta_lengths(ctx, as.d_recs->as<palace_fasta_rec>(), d_code.as<int32_t>(), n_tok, d_path_off->as<int64_t>(), n_paths, d_cum.as<int64_t>(),
-                                     d_len.as<int64_t>()));
+    const int64_t *d_path_off = dev.upload(tk.line_tok.data(), tk.line_tok.size(), "the paths' tokens");
+    int64_t *d_cum = dev.array<int64_t>(static_cast<size_t>(n_tok + 1), "the tokens' places");
+    int64_t *d_len = dev.array<int64_t>(static_cast<size_t>(n_paths), "the paths' lengths");
+    HIP_OK(palace_path_fasta_lengths(ctx, as.d_recs, d_code, n_tok, d_path_off, n_paths, d_cum, d_len));
     std::vector<int64_t> len(static_cast<size_t>(n_paths));
-    if (n_paths) HIP_OK(palace_d2h(ctx, len.data(), d_len.p, len.size() * sizeof(int64_t)));
+    if (n_paths) HIP_OK(palace_d2h(ctx, len.data(), d_len, len.size() * sizeof(int64_t)));
     std::string hdr;
     std::vector<int64_t> hdr_off{0}, path_out{0};
     for (int64_t l = 0; l < n_paths; l++) {
@@ -177,20 +144,18 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
         hdr_off.push_back(static_cast<int64_t>(hdr.size()));
     }
     const int64_t total = path_out.back();
-    auto d_hdr = uploaded(ctx, reinterpret_cast<const uint8_t *>(hdr.data()), hdr.size(), "the headers");
-    auto d_hdr_off = uploaded(ctx, hdr_off.data(), hdr_off.size(), "the headers' offsets");
-    auto d_path_out = uploaded(ctx, path_out.data(), path_out.size(), "the paths' places");
+    const uint8_t *d_hdr = dev.upload(reinterpret_cast<const uint8_t *>(hdr.data()), hdr.size(), "the headers");
+    const int64_t *d_hdr_off = dev.upload(hdr_off.data(), hdr_off.size(), "the headers' offsets");
+    const int64_t *d_path_out = dev.upload(path_out.data(), path_out.size(), "the paths' places");
     tr.lap("lengths and headers");
 
     // windows of the output text: window w is computed and copied back while window w - 1 goes to the file
     const int64_t win = total < window_bytes() ? total : window_bytes();
     if (total) {
-        Dev d_win0(ctx, static_cast<size_t>(win), "an output window"), d_win1(ctx, static_cast<size_t>(win), "an output window");
-        void *pin[2] = {nullptr, nullptr};
-        struct Pinned { palace_ctx *c; void **p; ~Pinned() { for (int i = 0; i < 2; i++) if (p[i]) palace_host_free(c, p[i]); } } pinned{ctx, pin};
-        for (int i = 0; i < 2; i++)
-            if (palace_host_alloc(ctx, static_cast<size_t>(win), &pin[i]) != PALACE_OK) throw Failure(std::string("no pinned memory for an output window: ") + palace_last_error());
-        uint8_t *d_win[2] = {d_win0.as<uint8_t>(), d_win1.as<uint8_t>()};
+        uint8_t *d_win[2] = {dev.array<uint8_t>(static_cast<size_t>(win), "an output window"), dev.array<uint8_t>(static_cast<size_t>(win), "an output window")};
+        const palace_host::PinnedBuffer pin0(ctx, static_cast<size_t>(win), "no pinned memory for an output window"),
+            pin1(ctx, static_cast<size_t>(win), "no pinned memory for an output window");
+        void *const pin[2] = {pin0.p, pin1.p};
         auto flush = [&](int64_t w) {
             const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
             HIP_OK(palace_mark_wait(ctx, static_cast<int>(w & 1)));
@@ -199,9 +164,7 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
         const int64_t n_win = (total + win - 1) / win;
         for (int64_t w = 0; w < n_win; w++) {
             const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
-            HIP_OK(palace_path_fasta_write(ctx, as.d_text->as<uint8_t>(), as.d_recs->as<palace_fasta_rec>(), d_code.as<int32_t>(), d_cum.as<int64_t>(),
-                                           d_path_off->as<int64_t>(), n_paths, d_hdr->as<uint8_t>(), d_hdr_off->as<int64_t>(), d_path_out->as<int64_t>(), lo, hi,
-                                           d_win[w & 1]));
+            HIP_OK(palace_path_fasta_write(ctx, as.d_text, as.d_recs, d_code, d_cum, d_path_off, n_paths, d_hdr, d_hdr_off, d_path_out, lo, hi, d_win[w & 1]));
             HIP_OK(palace_d2h_async(ctx, pin[w & 1], d_win[w & 1], static_cast<size_t>(hi - lo)));
             HIP_OK(palace_mark(ctx, static_cast<int>(w & 1)));
             if (w) flush(w - 1);

@@ -18,7 +18,12 @@ struct SamTimes { double read = 0, upload = 0, lines = 0, plan = 0, encode = 0; 
 struct SamError : std::runtime_error {
     SamError(int64_t line, int code) : std::runtime_error("line " + std::to_string(line) + ": " + sam_error_text(code)) {}
 };
-struct SamDeviceNoRoom : std::runtime_error { using std::runtime_error::runtime_error; };
+// the out-of-room text of the SAM front end
+inline std::string sam_no_room(size_t bytes, const char *what, const char *err)
+{
+    return "the SAM text, the BAM stream, 24 bytes per line and 8 per record are kept on the device, and " + std::to_string(bytes) + " bytes for " + what +
+           " cannot be allocated (" + err + "); there is no host path, a text larger than device memory is out of scope";
+}
 
 // `-F`'s value: decimal or 0x hex, nothing else
 inline bool parse_flag_mask(const std::string &v, uint32_t *mask)
@@ -48,26 +53,10 @@ inline std::vector<uint8_t> read_whole(const std::string &path)
 inline void load_sam_stream_device(palace_ctx *ctx, const std::string &path, uint32_t mask, DeviceBamStream &out, SamTimes *times = nullptr,
                                    int64_t *n_dropped_out = nullptr)
 {
-    auto ck = [](int rc, const char *what) { if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error()); };
     SamTimes unused;
     SamTimes &tm = times ? *times : unused;
-    BamDeviceClock clock{ctx, times != nullptr};
-    struct Owner {
-        palace_ctx *ctx;
-        std::vector<void *> owned;
-        ~Owner() { for (void *p : owned) palace_free(ctx, p); }
-        void *alloc(size_t bytes, const char *what)
-        {
-            void *p = nullptr;
-            if (palace_malloc(ctx, bytes ? bytes : 1, &p))
-                throw SamDeviceNoRoom("the SAM text, the BAM stream, 24 bytes per line and 8 per record are kept on the device, and " + std::to_string(bytes) +
-                                      " bytes for " + what + " cannot be allocated (" + palace_last_error() +
-                                      "); there is no host path, a text larger than device memory is out of scope");
-            owned.push_back(p);
-            return p;
-        }
-        void keep(void *p) { owned.erase(std::find(owned.begin(), owned.end(), p)); }
-    } own{ctx, {}};
+    StageClock clock{ctx, times != nullptr};
+    DeviceScope own(ctx, sam_no_room);
 
     const std::vector<uint8_t> text = read_whole(path);
     const int64_t n = static_cast<int64_t>(text.size());
@@ -98,16 +87,10 @@ inline void load_sam_stream_device(palace_ctx *ctx, const std::string &path, uin
     clock.lap(&tm.lines, true);
 
     // the header's names for RNAME / RNEXT: one blob, offsets, the table built from them on the device
-    std::vector<int64_t> off(hdr.name.size() + 1, 0);
-    std::string blob;
-    for (size_t t = 0; t < hdr.name.size(); t++) { off[t + 1] = off[t] + static_cast<int64_t>(hdr.name[t].size()); blob += hdr.name[t]; }
-    uint8_t *d_blob = static_cast<uint8_t *>(own.alloc(blob.size(), "the target names"));
-    int64_t *d_name_off = static_cast<int64_t *>(own.alloc(off.size() * 8, "the target names"));
-    if (!blob.empty()) ck(palace_h2d(ctx, d_blob, blob.data(), blob.size()), "target names");
-    ck(palace_h2d(ctx, d_name_off, off.data(), off.size() * 8), "target names");
-    palace_bam_names *table = nullptr;
-    ck(palace_bam_names_create(ctx, d_blob, d_name_off, static_cast<int32_t>(hdr.name.size()), &table), "palace_bam_names_create");
-    struct Table { palace_ctx *ctx; palace_bam_names *t; ~Table() { palace_bam_names_destroy(ctx, t); } } table_guard{ctx, table};
+    const DeviceNames names = upload_names(own, hdr.name, "the target names", "target names");
+    BamNamesHandle table_guard(ctx);
+    ck(palace_bam_names_create(ctx, names.blob, names.off, static_cast<int32_t>(hdr.name.size()), &table_guard.h), "palace_bam_names_create");
+    palace_bam_names *const table = table_guard.h;
 
     const size_t na = static_cast<size_t>(n_align);
     int32_t *d_size = static_cast<int32_t *>(own.alloc(na * 4, "the record sizes"));

@@ -9,6 +9,7 @@
 //   PALACE_DEVICE, PALACE_TRACE      as in the other tools
 #include <iostream>
 
+#include "bai.hpp"
 #include "bgzf_members_device.hpp"
 #include "device_pick.hpp"
 #include "sam_device.hpp"
@@ -62,38 +63,31 @@ int main(int argc, char **argv)
     if (!have_in || in.empty()) return usage();
     if (!bam) { std::cerr << "samview: only BAM is written: -b is required\n"; return 1; }
 
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(pick_device(), &ctx)) { std::cerr << "samview: " << palace_last_error() << "\n"; return 1; }
-    int code = 0;
-    bool out_made = false;
-    FILE *f = nullptr;
-    try {
+    return with_device("samview", [&](palace_ctx *ctx) {
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
-        Laps laps{ctx, trace};
+        StageClock clock{ctx, trace};
+        MemberWriteTimes wt;
         SamTimes tm;
         DeviceBamStream st;
         int64_t dropped = 0;
         load_sam_stream_device(ctx, in, mask, st, trace ? &tm : nullptr, &dropped);      // (the whole conversion: nothing is written before it is done)
-        f = out.empty() ? stdout : std::fopen(out.c_str(), "wb");
+        const std::string out_name = out.empty() ? "stdout" : out;
+        OutputFiles outputs;                                                 // (stdout is not its to close or remove)
+        FILE *f = out.empty() ? stdout : (outputs.f = std::fopen(out.c_str(), "wb"));
         if (!f) throw std::runtime_error("cannot open " + out + " for writing");
-        out_made = !out.empty();
+        if (!out.empty()) outputs.made.push_back(out);
         std::vector<int64_t> member_u, member_c;
         uint64_t file_bytes = 0;
-        write_members_device(ctx, st.d_stream, st.total, 8192, stored, f, out.empty() ? "stdout" : out, laps, member_u, member_c, &file_bytes);
+        write_bam_file_device(ctx, bamsort_no_room, st.d_stream, st.total, 8192, stored, f, out_name, clock, wt, member_u, member_c, &file_bytes);
         const int rc_close = out.empty() ? std::fflush(f) : std::fclose(f);
-        f = nullptr;
-        if (rc_close != 0) throw std::runtime_error("write failed: " + (out.empty() ? std::string("stdout") : out));
+        outputs.f = nullptr;
+        if (rc_close != 0) throw std::runtime_error("write failed: " + out_name);
+        outputs.done = true;
         if (trace)
             std::fprintf(stderr, "[samview] ms: read %.1f upload %.1f lines %.1f plan %.1f encode %.1f | crc%s %.1f copy+write %.1f; records %lld, dropped %lld, "
-                         "stream %lld B, file %llu B\n", tm.read, tm.upload, tm.lines, tm.plan, tm.encode, stored ? "" : "+deflate", laps.deflate, laps.copy_write,
+                         "stream %lld B, file %llu B\n", tm.read, tm.upload, tm.lines, tm.plan, tm.encode, stored ? "" : "+deflate", wt.crc + wt.deflate, wt.copy_write,
                          static_cast<long long>(st.n_records), static_cast<long long>(dropped), static_cast<long long>(st.total),
                          static_cast<unsigned long long>(file_bytes));
-    } catch (const std::exception &e) {
-        std::cerr << "samview: " << e.what() << "\n";
-        code = 1;
-        if (f && f != stdout) std::fclose(f);
-        if (out_made) std::remove(out.c_str());
-    }
-    palace_ctx_destroy(ctx);
-    return code;
+        return 0;
+    });
 }

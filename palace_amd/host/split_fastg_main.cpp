@@ -10,55 +10,26 @@
 // failure; 2 for a usage error.
 #include <cstdio>
 #include <cstdlib>
-#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "../../include/palace_hip.h"
 #include "device_pick.hpp"
+#include "device_scope.hpp"
 #include "fast_exit.hpp"
 #include "fastx.hpp"
 #include "trace.hpp"
 
 namespace {
 
-struct Failure : std::runtime_error { using std::runtime_error::runtime_error; };
+using palace_host::Failure;
+using palace_host::DeviceScope;
 
-#define HIP_OK(call)                                                                     \
-    do {                                                                                 \
-        if ((call) != PALACE_OK) throw Failure(std::string(#call " failed: ") + palace_last_error()); \
-    } while (0)
-
-// device memory that goes with its scope
-struct Dev {
-    palace_ctx *ctx;
-    void *p = nullptr;
-    Dev(palace_ctx *c, size_t bytes, const char *what) : ctx(c)
-    {
-        if (palace_malloc(ctx, bytes ? bytes : 1, &p) != PALACE_OK)
-            throw Failure(std::string(what) + " (" + std::to_string(bytes) + " bytes) does not fit the device: " + palace_last_error());
-    }
-    ~Dev() { if (p) palace_free(ctx, p); }
-    Dev(const Dev &) = delete;
-    Dev &operator=(const Dev &) = delete;
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
-struct Names {
-    palace_ctx *ctx;
-    palace_fasta_names *t = nullptr;
-    ~Names() { if (t) palace_fasta_names_destroy(ctx, t); }
-};
-
+// the FASTG's own faults on top of the FASTA index's
 const char *fault_text(int code)
 {
     switch (code) {
-    case PALACE_FASTA_ETEXT: return "text before the first '>'";
-    case PALACE_FASTA_ENAME: return "a header line without a name";
-    case PALACE_FASTA_ERAGGED: return "a sequence line behind a line of another length than the record's first (only a record's last line may be shorter)";
-    case PALACE_FASTA_EBLANK: return "a sequence line behind a blank line of its record";
-    case PALACE_FASTA_EBYTE: return "a sequence byte outside 0x21-0x7E";
     case PALACE_FASTG_EPLUS: return "a sequence line that begins with '+' or '@'";
     case PALACE_FASTG_EHIGH: return "a byte of 0x80 or above in a header line";
     case PALACE_FASTG_ECR: return "a CR in a header line that is not directly before the LF";
@@ -67,7 +38,7 @@ const char *fault_text(int code)
     case PALACE_FASTG_ENONAME: return "a header without a name in front of its last byte, its first ':' or ','";
     case PALACE_FASTG_EBASE: return "a base other than A, C, G, T in a primed record";
     }
-    return "malformed";
+    return palace_host::fasta_fault_text(code);
 }
 
 // a device buffer of `bytes` bytes to the file, in pieces
@@ -85,15 +56,16 @@ void to_file(palace_ctx *ctx, const uint8_t *d, int64_t bytes, std::FILE *f, con
 // the `.fai` rows of d_recs (none where d_skip is set) to `path`
 void write_fai(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records, const std::string &path)
 {
-    Dev d_off(ctx, static_cast<size_t>(n_records + 1) * sizeof(int64_t), "the rows' places");
+    DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
+    int64_t *d_off = dev.array<int64_t>(static_cast<size_t>(n_records + 1), "the rows' places");
     int64_t bytes = 0;
-    HIP_OK(palace_fai_rows_plan(ctx, d_recs, d_skip, n_records, d_off.as<int64_t>(), &bytes));
-    Dev d_rows(ctx, static_cast<size_t>(bytes), "the index rows");
-    HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off.as<int64_t>(), d_rows.as<uint8_t>()));
+    HIP_OK(palace_fai_rows_plan(ctx, d_recs, d_skip, n_records, d_off, &bytes));
+    uint8_t *d_rows = dev.array<uint8_t>(static_cast<size_t>(bytes), "the index rows");
+    HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off, d_rows));
     std::FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) throw Failure("cannot write " + path);
     struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{f};
-    to_file(ctx, d_rows.as<uint8_t>(), bytes, f, path);
+    to_file(ctx, d_rows, bytes, f, path);
     closer.f = nullptr;
     if (std::fclose(f) != 0) throw Failure("cannot write " + path);
 }
@@ -108,64 +80,58 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{out};
     tr.lap("FASTG read");
     const int64_t n = static_cast<int64_t>(text.size);
-    Dev d_text(ctx, text.size, "the FASTG is read on the device and has no other path: it");
-    if (n) HIP_OK(palace_h2d(ctx, d_text.p, text.data, text.size));
+    DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
+    const uint8_t *d_text = dev.upload(text.bytes(), text.size, "the FASTG is read on the device and has no other path: it");
     tr.lap("FASTG uploaded");
 
     palace_fasta_status st{}, fg{};
-    int64_t n_records = 0;
-    std::unique_ptr<Dev> d_recs;
-    {
-        const size_t sb = palace_fasta_index_scratch_bytes(n);
-        Dev scratch(ctx, sb, "the index's scratch");
-        HIP_OK(palace_fasta_index(ctx, d_text.as<uint8_t>(), n, nullptr, 0, scratch.p, sb, &st));                     // how many records
-        n_records = st.n_records;
-        d_recs = std::make_unique<Dev>(ctx, static_cast<size_t>(n_records) * sizeof(palace_fasta_rec), "the FASTG's index");
-        HIP_OK(palace_fasta_index(ctx, d_text.as<uint8_t>(), n, d_recs->as<palace_fasta_rec>(), n_records, scratch.p, sb, &st));
-    }
+    const size_t sb = palace_fasta_index_scratch_bytes(n);
+    void *d_scratch = dev.alloc(sb, "the index's scratch");
+    HIP_OK(palace_fasta_index(ctx, d_text, n, nullptr, 0, d_scratch, sb, &st));                                      // how many records
+    const int64_t n_records = st.n_records;
+    const size_t nr = static_cast<size_t>(n_records);
+    palace_fasta_rec *d_recs = dev.array<palace_fasta_rec>(nr, "the FASTG's index");
+    HIP_OK(palace_fasta_index(ctx, d_text, n, d_recs, n_records, d_scratch, sb, &st));
+    dev.give_back(d_scratch);
     tr.lap("FASTG indexed");
-    Dev d_name_recs(ctx, static_cast<size_t>(n_records) * sizeof(palace_fasta_rec), "the records' names");
-    Dev d_primed(ctx, static_cast<size_t>(n_records), "the primed bits");
-    HIP_OK(palace_fastg_derive(ctx, d_text.as<uint8_t>(), n, d_recs->as<palace_fasta_rec>(), n_records, d_name_recs.as<palace_fasta_rec>(), d_primed.as<uint8_t>(),
-                               &fg));
+    palace_fasta_rec *d_name_recs = dev.array<palace_fasta_rec>(nr, "the records' names");
+    uint8_t *d_primed = dev.array<uint8_t>(nr, "the primed bits");
+    HIP_OK(palace_fastg_derive(ctx, d_text, n, d_recs, n_records, d_name_recs, d_primed, &fg));
     tr.lap("names derived, text checked");
     if (fg.error && (!st.error || fg.bad_line < st.bad_line || (fg.bad_line == st.bad_line && fg.error < st.error))) st = fg;
     if (st.error) throw Failure(graph + ": line " + std::to_string(st.bad_line) + ": " + fault_text(st.error));
 
-    Names names{ctx};
-    Dev d_dup(ctx, static_cast<size_t>(n_records), "the duplicate flags");
-    HIP_OK(palace_fasta_names_create(ctx, d_text.as<uint8_t>(), d_name_recs.as<palace_fasta_rec>(), n_records, d_dup.as<uint8_t>(), &names.t));
-    Dev d_out_off(ctx, static_cast<size_t>(n_records + 1) * sizeof(int64_t), "the records' places");
-    Dev d_out_recs(ctx, fai ? static_cast<size_t>(n_records) * sizeof(palace_fasta_rec) : 0, "the output's index");
+    palace_host::FastaNamesHandle names(ctx);
+    uint8_t *d_dup = dev.array<uint8_t>(nr, "the duplicate flags");
+    HIP_OK(palace_fasta_names_create(ctx, d_text, d_name_recs, n_records, d_dup, &names.h));
+    int64_t *d_out_off = dev.array<int64_t>(nr + 1, "the records' places");
+    palace_fasta_rec *d_out_recs = dev.array<palace_fasta_rec>(fai ? nr : 0, "the output's index");
     int64_t n_kept = 0, total = 0;
-    HIP_OK(palace_fastg_plan(ctx, d_name_recs.as<palace_fasta_rec>(), d_dup.as<uint8_t>(), n_records, d_out_off.as<int64_t>(),
-                             fai ? d_out_recs.as<palace_fasta_rec>() : nullptr, &n_kept, &total));
+    HIP_OK(palace_fastg_plan(ctx, d_name_recs, d_dup, n_records, d_out_off, fai ? d_out_recs : nullptr, &n_kept, &total));
     tr.lap("names hashed, output planned");
-    {
-        Dev d_out(ctx, static_cast<size_t>(total), "the output is gathered on the device and has no other path: it");
-        HIP_OK(palace_fastg_write(ctx, d_text.as<uint8_t>(), d_name_recs.as<palace_fasta_rec>(), d_primed.as<uint8_t>(), d_out_off.as<int64_t>(), n_records, 0, total,
-                                  d_out.as<uint8_t>()));
-        HIP_OK(palace_sync(ctx));
-        tr.lap("output gathered");
-        to_file(ctx, d_out.as<uint8_t>(), total, out, output);
-    }
+    uint8_t *d_out = dev.array<uint8_t>(static_cast<size_t>(total), "the output is gathered on the device and has no other path: it");
+    HIP_OK(palace_fastg_write(ctx, d_text, d_name_recs, d_primed, d_out_off, n_records, 0, total, d_out));
+    HIP_OK(palace_sync(ctx));
+    tr.lap("output gathered");
+    to_file(ctx, d_out, total, out, output);
+    dev.give_back(d_out);
     closer.f = nullptr;
     if (std::fclose(out) != 0) throw Failure("cannot write " + output);
     tr.lap("output written");
     if (!fai) return;
 
-    write_fai(ctx, d_text.as<uint8_t>(), d_out_recs.as<palace_fasta_rec>(), d_dup.as<uint8_t>(), n_records, output + ".fai");
-    Names whole{ctx};
-    Dev d_skip(ctx, static_cast<size_t>(n_records), "the duplicate flags");
-    HIP_OK(palace_fasta_names_create(ctx, d_text.as<uint8_t>(), d_recs->as<palace_fasta_rec>(), n_records, d_skip.as<uint8_t>(), &whole.t));
-    write_fai(ctx, d_text.as<uint8_t>(), d_recs->as<palace_fasta_rec>(), d_skip.as<uint8_t>(), n_records, graph + ".fai");
-    std::vector<uint8_t> skip(static_cast<size_t>(n_records));
-    if (n_records) HIP_OK(palace_d2h(ctx, skip.data(), d_skip.p, skip.size()));
+    write_fai(ctx, d_text, d_out_recs, d_dup, n_records, output + ".fai");
+    palace_host::FastaNamesHandle whole(ctx);
+    uint8_t *d_skip = dev.array<uint8_t>(nr, "the duplicate flags");
+    HIP_OK(palace_fasta_names_create(ctx, d_text, d_recs, n_records, d_skip, &whole.h));
+    write_fai(ctx, d_text, d_recs, d_skip, n_records, graph + ".fai");
+    std::vector<uint8_t> skip(nr);
+    if (n_records) HIP_OK(palace_d2h(ctx, skip.data(), d_skip, skip.size()));
     size_t k = 0;
     for (; k < skip.size() && !skip[k]; k++) {}
     if (k < skip.size()) {                                                   // (rare: the records come to the host only to name them)
         std::vector<palace_fasta_rec> recs(skip.size());
-        HIP_OK(palace_d2h(ctx, recs.data(), d_recs->p, recs.size() * sizeof(palace_fasta_rec)));
+        HIP_OK(palace_d2h(ctx, recs.data(), d_recs, recs.size() * sizeof(palace_fasta_rec)));
         for (; k < skip.size(); k++)
             if (skip[k])
                 std::fprintf(stderr, "split_fastg: warning: %s: sequence name '%.*s' appears again in record %zu: left out of %s.fai\n", graph.c_str(),
