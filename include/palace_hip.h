@@ -1044,6 +1044,68 @@ int palace_sam_encode(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_l
                       const palace_bam_names *names, const int32_t *d_size, const int64_t *d_off, const int32_t *d_ord,
                       uint8_t *d_out, int64_t *d_starts);
 
+/* ---- readqc: fastp's paired-read trimming and filtering where the two FASTQ texts lie (the rules: DESIGN.md 8, csrc/fastq_rules.hpp) -- */
+
+/* What is wrong with a FASTQ text.  Parity with fastp is UNPINNED: fastp is not at hand, these rules are the behaviour. */
+#define PALACE_FASTQ_ELINES 1     /* the text ends inside a record: fewer than 4 lines behind the last complete one (at its first line) */
+#define PALACE_FASTQ_EAT 2        /* a record's line 0 does not begin with '@' */
+#define PALACE_FASTQ_EPLUS 3      /* a record's line 2 does not begin with '+' */
+#define PALACE_FASTQ_ELONG 4      /* SEQ of more than PALACE_FASTQ_MAX_SEQ bases */
+#define PALACE_FASTQ_EBASE 5      /* SEQ: a byte that is none of A C G T N (CR included) */
+#define PALACE_FASTQ_EQLEN 6      /* QUAL has not SEQ's length */
+#define PALACE_FASTQ_EQUAL 7      /* QUAL: a byte outside 33 .. 126 (CR included) */
+#define PALACE_FASTQ_ECOUNT 8     /* (host) the two files hold different numbers of records */
+
+#define PALACE_FASTQ_MAX_SEQ 4096 /* the bases of a read: a wavefront of the plan holds both reads of a pair in 2 x 4096 bytes of LDS */
+
+/* The option values of readqc (fastp's names in brackets) and the four constants of its overlap search.  The defaults:
+ * {15, 40, 5, 15, 0, 0, 0, 30, 5, 20, 50, 0}. */
+typedef struct {
+    int32_t qualified_quality;     /* -q: a QUAL byte below 33 + this is a low one */
+    int32_t unqualified_percent;   /* -u: a read fails when low * 100 > this * L */
+    int32_t n_limit;               /* -n: ... or when it has more N than this */
+    int32_t min_length;            /* -l: ... or when L is below this */
+    int32_t no_trim;               /* -A */
+    int32_t no_quality_filter;     /* -Q: neither the quality nor the N filter */
+    int32_t no_length_filter;      /* -L */
+    int32_t overlap_require;       /* 30: offsets o < L1 - 30 and k < L2 - 30 are searched */
+    int32_t diff_limit;            /* 5 and */
+    int32_t diff_pct;              /* 20: a candidate of n bases may have min(5, n * 20 / 100) mismatches */
+    int32_t diff_window;           /* 50: ... among its first min(n, 50) positions; later ones are not looked at */
+    int32_t reserved;
+} palace_readqc_params;
+
+/* the numbers palace_readqc_plan leaves in out[]: counts in reads (two per pair) and bases */
+enum {
+    PALACE_READQC_READS_BEFORE = 0, PALACE_READQC_BASES_BEFORE = 1, PALACE_READQC_READS_AFTER = 2, PALACE_READQC_BASES_AFTER = 3,
+    PALACE_READQC_LOW_QUALITY = 4, PALACE_READQC_TOO_MANY_N = 5, PALACE_READQC_TOO_SHORT = 6,
+    PALACE_READQC_TRIMMED_READS = 7,   /* reads that lost bases to the overlap rule (dropped pairs included) */
+    PALACE_READQC_TRIMMED_BASES = 8,   /* ... and the bases they lost */
+    PALACE_READQC_BYTES_1 = 9, PALACE_READQC_BYTES_2 = 10,    /* d_off1[n_pairs], d_off2[n_pairs] */
+    PALACE_READQC_N_OUT = 11
+};
+
+/* The records of a FASTQ text whose lines palace_sam_lines has cut (d_line_start[0 .. n_lines], n_lines / 4 < 2^31): record r is the lines
+ * 4r .. 4r + 3.  A wavefront owns a record and its lanes stride the bytes of SEQ and QUAL, so a record may lie across any number of
+ * tiles.  d_seq_len[r] = SEQ's length.  out[0] = the complete records, out[1] / out[2] = the smallest 1-based number of a faulty line
+ * and its PALACE_FASTQ_E* code, 0 / 0 for none.  Waits for the stream. */
+int palace_fastq_records(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, int64_t n_lines, int32_t *d_seq_len,
+                         int64_t *out);
+
+/* Pair i of two texts palace_fastq_records found no fault in (their line starts; n_pairs records each): the overlap search, the trim
+ * and the filter of csrc/fastq_rules.hpp, a wavefront per pair.  d_len1[i] / d_len2[i] = the bases read 1 / read 2 keeps, -1 / -1 for a
+ * dropped pair; d_off1 / d_off2 [0 .. n_pairs] = the exclusive sums of the records' bytes in the two output texts;
+ * out[PALACE_READQC_N_OUT] as the enum above.  Waits for the stream. */
+int palace_readqc_plan(palace_ctx *ctx, const uint8_t *d_text1, const int64_t *d_line_start1, const uint8_t *d_text2,
+                       const int64_t *d_line_start2, int64_t n_pairs, const palace_readqc_params *prm, int32_t *d_len1, int32_t *d_len2,
+                       int64_t *d_off1, int64_t *d_off2, int64_t *out);
+
+/* Bytes [lo, hi) of one output text to d_out[0 .. hi - lo) (16-byte aligned), 0 <= lo <= hi <= d_off[n_pairs]: every kept record is its
+ * name line, SEQ[0 : len], line 2 and QUAL[0 : len], each with an LF.  A lane writes 16 bytes with one store; a tile of 4096 bytes
+ * searches the record of its first byte once.  Nothing outside the range is written.  Enqueues only. */
+int palace_readqc_write(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, const int32_t *d_len, const int64_t *d_off,
+                        int64_t n_pairs, int64_t lo, int64_t hi, uint8_t *d_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,7 +97,24 @@ class FastaStatus(C.Structure):
     _fields_ = [("n_records", C.c_int64), ("bad_line", C.c_int64), ("error", C.c_int32), ("reserved", C.c_int32)]
 
 
-assert CAND_DTYPE.itemsize == 64 and EDGE_DTYPE.itemsize == 32 and SA_ITEM_DTYPE.itemsize == 32
+class ReadqcParams(C.Structure):
+    """palace_readqc_params (defaults = fastp's for paired input)."""
+    _fields_ = [(k, C.c_int32) for k in ("qualified_quality", "unqualified_percent", "n_limit", "min_length", "no_trim", "no_quality_filter",
+                                         "no_length_filter", "overlap_require", "diff_limit", "diff_pct", "diff_window", "reserved")]
+
+    @classmethod
+    def default(cls, **kw):
+        p = cls(15, 40, 5, 15, 0, 0, 0, 30, 5, 20, 50, 0)
+        for k, v in kw.items():
+            assert hasattr(p, k), k
+            setattr(p, k, int(v))
+        return p
+
+
+READQC_OUT = ("reads_before", "bases_before", "reads_after", "bases_after", "low_quality", "too_many_n", "too_short", "trimmed_reads", "trimmed_bases",
+              "bytes_1", "bytes_2")                # PALACE_READQC_* of include/palace_hip.h
+
+assert CAND_DTYPE.itemsize == 64 and EDGE_DTYPE.itemsize == 32 and SA_ITEM_DTYPE.itemsize == 32 and C.sizeof(ReadqcParams) == 48
 
 _SIGS = {
     "palace_ctx_create": [C.c_int, C.POINTER(C.c_void_p)],
@@ -250,6 +267,10 @@ _SIGS = {
     "palace_sam_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_uint32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
                         C.POINTER(C.c_int64)],
     "palace_sam_encode": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_fastq_records": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_readqc_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ReadqcParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                           C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_readqc_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p],
 }
 
 
@@ -991,6 +1012,72 @@ def sam_encode(ctx: Ctx, text: bytes, starts, n_header: int, names, mask: int, h
     """palace_sam_plan and palace_sam_encode -> the plan's dict and, for a text without error, stream: `head`, the records, and `guard`
     bytes of 0xAA where nothing may be written; starts: the kept records' starts int64"""
     return _sam_run(ctx, text, starts, n_header, names, mask, head, True, guard)
+
+
+class Readqc:
+    """Two FASTQ texts on the device with their line starts (palace_sam_lines), and the three calls of readqc over them:
+    records() -> per text (records, bad line, code, seq_len int32); plan(prm) -> dict of len1, len2 int32, off1, off2 int64 (pairs + 1) and
+    the READQC_OUT numbers; write(which, lo, hi, guard) -> guard bytes of 0xAA, the window's bytes, guard bytes of 0xAA."""
+
+    def __init__(self, ctx: Ctx, text1: bytes, text2: bytes):
+        self.ctx, self.bufs, self.text, self.starts, self.n_lines = ctx, [], [], [], []
+        self.d_len = self.d_off = None
+        for text in (bytes(text1), bytes(text2)):
+            n = len(text)
+            nscr = int(lib().palace_sam_scratch_bytes(n))
+            d_text, d_scr = ctx.upload(np.frombuffer(text, dtype=np.uint8) if n else np.zeros(16, np.uint8)), ctx.empty(max(nscr, 1), np.uint8)
+            self.bufs += [d_text, d_scr]
+            out = (C.c_int64 * 5)()
+            _check(lib().palace_sam_lines(ctx.h, d_text.ptr, n, d_scr.ptr, nscr, None, 0, out), "palace_sam_lines")
+            n_lines = int(out[0])
+            d_st = ctx.empty(n_lines + 1, np.int64)
+            self.bufs.append(d_st)
+            _check(lib().palace_sam_lines(ctx.h, d_text.ptr, n, d_scr.ptr, nscr, d_st.ptr, n_lines + 1, out), "palace_sam_lines")
+            self.text.append(d_text); self.starts.append(d_st); self.n_lines.append(n_lines)
+
+    def records(self):
+        res = []
+        for d_text, d_st, n_lines in zip(self.text, self.starts, self.n_lines):
+            d_len = self.ctx.empty(max(1, n_lines // 4), np.int32)
+            out = (C.c_int64 * 3)()
+            try:
+                _check(lib().palace_fastq_records(self.ctx.h, d_text.ptr, d_st.ptr, n_lines, d_len.ptr, out), "palace_fastq_records")
+                res.append((int(out[0]), int(out[1]), int(out[2]), d_len.to_host()[:n_lines // 4].copy()))
+            finally:
+                d_len.free()
+        return res
+
+    def plan(self, prm: "ReadqcParams | None" = None):
+        n = self.n_lines[0] // 4
+        assert self.n_lines[1] // 4 == n
+        prm = prm or ReadqcParams.default()
+        if self.d_len is None:
+            self.d_len = [self.ctx.empty(max(1, n), np.int32) for _ in range(2)]
+            self.d_off = [self.ctx.empty(n + 1, np.int64) for _ in range(2)]
+            self.bufs += self.d_len + self.d_off
+        out = (C.c_int64 * len(READQC_OUT))()
+        _check(lib().palace_readqc_plan(self.ctx.h, self.text[0].ptr, self.starts[0].ptr, self.text[1].ptr, self.starts[1].ptr, n, C.byref(prm),
+                                        self.d_len[0].ptr, self.d_len[1].ptr, self.d_off[0].ptr, self.d_off[1].ptr, out), "palace_readqc_plan")
+        res = {k: int(v) for k, v in zip(READQC_OUT, out)}
+        res.update(len1=self.d_len[0].to_host()[:n].copy(), len2=self.d_len[1].to_host()[:n].copy(), off1=self.d_off[0].to_host()[:n + 1].copy(),
+                   off2=self.d_off[1].to_host()[:n + 1].copy())
+        return res
+
+    def write(self, which: int, lo: int, hi: int, guard: int = 32) -> bytes:
+        assert guard % 16 == 0 and self.d_len is not None
+        image = self.ctx.upload(np.full(2 * guard + max(hi - lo, 0), 0xAA, np.uint8))
+        try:
+            _check(lib().palace_readqc_write(self.ctx.h, self.text[which].ptr, self.starts[which].ptr, self.d_len[which].ptr, self.d_off[which].ptr,
+                                             self.n_lines[which] // 4, lo, hi, image.ptr + guard), "palace_readqc_write")
+            self.ctx.sync()
+            return image.to_host().tobytes()
+        finally:
+            image.free()
+
+    def close(self):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
 
 
 BAM_COLUMNS = (("tid", np.int32), ("pos", np.int32), ("mtid", np.int32), ("mpos", np.int32), ("nm", np.int32), ("ref_len", np.int32),
