@@ -943,13 +943,15 @@ int palace_bam_gather_plan(palace_ctx *ctx, const uint8_t *d_stream, const int64
 int palace_bam_gather_write(palace_ctx *ctx, const uint8_t *d_stream, const int64_t *d_starts, const uint32_t *d_perm,
                             const int64_t *d_out_off, int64_t n_records, int64_t out_bytes, uint8_t *d_out);
 
-/* What a .bai (SAM specification 5.2) files each record of a coordinate-sorted stream under.  refID < 0: d_ref = -1, the record is
- * not indexed and counted into n_no_coor.  Else beg = pos, end = pos + the reference bases of the CIGAR the record really has (M, D,
+/* What a .bai (SAM specification 5.2) files each record of a coordinate-sorted stream under.  refID = -1: d_ref = -1 and d_bin =
+ * d_win_beg = d_win_end = 0 (so the unplaced tail of a sorted stream is ONE run of palace_bai_chunks), the record is not indexed
+ * and counted into n_no_coor.  Else beg = pos, end = pos + the reference bases of the CIGAR the record really has (M, D,
  * N, =, X; the CG tag's behind a placeholder), pos + 1 for flag 0x4, no ops or no reference bases; d_bin = reg2bin(beg, end), the
  * record's own bin field is not looked at; d_win_beg / d_win_end = beg >> 14, (end - 1) >> 14; d_unmapped = flag 0x4.  n_bad /
  * first_bad: the records a .bai cannot hold (refID >= n_ref or < -1, pos < 0 with a refID, end > 2^29) and the first one's
- * ordinal (-1: none); first_unsorted: the first ordinal whose sort key is smaller than its predecessor's (-1: the stream is
- * coordinate-sorted).  Waits for the stream. */
+ * ordinal (-1: none); of a record counted in n_bad only d_unmapped is specified, its other four columns may hold anything.
+ * first_unsorted: the first ordinal whose sort key is smaller than its predecessor's, a record without a key (palace_bam_sort_keys)
+ * being out of order with neither neighbour (-1: the stream is coordinate-sorted).  Waits for the stream. */
 typedef struct {
     int64_t n_bad, first_bad, first_unsorted, n_no_coor;
 } palace_bai_status;

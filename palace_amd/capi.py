@@ -940,6 +940,123 @@ def bam_gather(ctx: Ctx, stream: bytes, starts, perm, head: bytes):
             b.free()
 
 
+GUARD = b"\xaa" * 16     # behind the last entry of every output the index wrappers allocate; the fill of entries nothing may write
+
+
+def untouched(arr) -> np.ndarray:
+    """per entry of an array a wrapper below returned: every byte still holds the fill"""
+    a = np.ascontiguousarray(arr)
+    return (a.view(np.uint8).reshape(len(a), a.dtype.itemsize) == GUARD[0]).all(axis=1)
+
+
+def _guarded(ctx: Ctx, n: int, dtype) -> DevBuf:
+    """n entries of the fill and GUARD behind them, on the device"""
+    return ctx.upload(np.full(n * np.dtype(dtype).itemsize + len(GUARD), GUARD[0], np.uint8))
+
+
+def _unguard(buf: DevBuf, n: int, dtype, what: str) -> np.ndarray:
+    """the n entries back on the host; the guard behind them must be intact"""
+    raw = buf.to_host()
+    size = n * np.dtype(dtype).itemsize
+    assert raw[size:].tobytes() == GUARD, f"{what}: written behind its {n} entries"
+    return raw[:size].view(dtype).copy()
+
+
+def _stream_and_starts(ctx: Ctx, stream: bytes, starts):
+    stream = bytes(stream)
+    st = np.ascontiguousarray(starts, dtype=np.int64)
+    return [ctx.upload(np.frombuffer(stream, dtype=np.uint8) if stream else np.zeros(1, np.uint8)), ctx.upload(st if len(st) else np.zeros(1, np.int64))], len(st)
+
+
+def _column(ctx: Ctx, arr, dtype, n: int) -> DevBuf:
+    a = np.ascontiguousarray(arr, dtype=dtype)
+    assert a.shape == (n,), (a.shape, n)
+    return ctx.upload(a if n else np.zeros(1, dtype))
+
+
+def bai_records(ctx: Ctx, stream: bytes, starts, n_ref: int):
+    """palace_bai_records -> (ref, bin, win_beg, win_end int32, unmapped uint8, (n_bad, first_bad, first_unsorted, n_no_coor))"""
+    bufs, n = _stream_and_starts(ctx, stream, starts)
+    kinds = (np.int32, np.int32, np.int32, np.int32, np.uint8)
+    status = BaiStatus()
+    try:
+        out = [_guarded(ctx, n, t) for t in kinds]
+        bufs += out
+        _check(lib().palace_bai_records(ctx.h, bufs[0].ptr, bufs[1].ptr, n, n_ref, *(b.ptr for b in out), C.byref(status)), "palace_bai_records")
+        cols = tuple(_unguard(b, n, t, "palace_bai_records") for b, t in zip(out, kinds))
+        return cols + ((int(status.n_bad), int(status.first_bad), int(status.first_unsorted), int(status.n_no_coor)),)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bai_chunks(ctx: Ctx, stream: bytes, starts, ref, bin, n_ref: int, cap: int | None = None):
+    """palace_bai_chunks on columns of the caller's -> (n_runs, chunk_ref, chunk_bin int32, chunk_beg, chunk_end int64).  cap=None: the
+    two calls of host/bai.hpp, the count and then the runs into arrays of exactly that size.  cap=0: the count alone, empty arrays.
+    Any other cap goes through as it is: the arrays come back with all their cap entries, unwritten ones as untouched() knows them."""
+    bufs, n = _stream_and_starts(ctx, stream, starts)
+    kinds = (np.int32, np.int32, np.int64, np.int64)
+    n_runs = C.c_int64(-1)
+    try:
+        bufs += [_column(ctx, ref, np.int32, n), _column(ctx, bin, np.int32, n)]
+        ins = [b.ptr for b in bufs]
+        if cap is None or cap == 0:
+            _check(lib().palace_bai_chunks(ctx.h, *ins, n, n_ref, None, None, None, None, 0, C.byref(n_runs)), "palace_bai_chunks")
+            if cap == 0:
+                return (int(n_runs.value),) + tuple(np.zeros(0, t) for t in kinds)
+            cap = int(n_runs.value)
+        out = [_guarded(ctx, cap, t) for t in kinds]
+        bufs += out
+        again = C.c_int64(-1)
+        _check(lib().palace_bai_chunks(ctx.h, *ins, n, n_ref, *(b.ptr for b in out), cap, C.byref(again)), "palace_bai_chunks")
+        assert n_runs.value in (-1, again.value), "palace_bai_chunks: two counts of one stream differ"
+        return (int(again.value),) + tuple(_unguard(b, cap, t, "palace_bai_chunks") for b, t in zip(out, kinds))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bai_linear(ctx: Ctx, stream: bytes, starts, ref, win_beg, win_end, unmapped, n_ref: int):
+    """palace_bai_linear, the two calls of host/bai.hpp -> (n_intv int32 (n_ref), ref_stat int64 (4, n_ref), lin_off int64 (n_ref + 1):
+    the exclusive sums of n_intv made here, lin int64 (lin_off[-1]))"""
+    bufs, n = _stream_and_starts(ctx, stream, starts)
+    try:
+        bufs += [_column(ctx, ref, np.int32, n), _column(ctx, win_beg, np.int32, n), _column(ctx, win_end, np.int32, n), _column(ctx, unmapped, np.uint8, n)]
+        ins = [b.ptr for b in bufs]
+        d_n_intv, d_stat = _guarded(ctx, n_ref, np.int32), _guarded(ctx, 4 * n_ref, np.int64)
+        bufs += [d_n_intv, d_stat]
+        _check(lib().palace_bai_linear(ctx.h, *ins, n, n_ref, d_n_intv.ptr, d_stat.ptr, None, 0, None), "palace_bai_linear")
+        n_intv = _unguard(d_n_intv, n_ref, np.int32, "palace_bai_linear: n_intv")
+        stat = _unguard(d_stat, 4 * n_ref, np.int64, "palace_bai_linear: ref_stat")
+        lin_off = np.concatenate(([0], np.cumsum(n_intv, dtype=np.int64))).astype(np.int64)
+        n_lin = int(lin_off[-1])
+        d_lin_off, d_lin = ctx.upload(lin_off), _guarded(ctx, n_lin, np.int64)
+        bufs += [d_lin_off, d_lin]
+        _check(lib().palace_bai_linear(ctx.h, *ins, n, n_ref, d_n_intv.ptr, d_stat.ptr, d_lin_off.ptr, n_lin, d_lin.ptr), "palace_bai_linear")
+        lin = _unguard(d_lin, n_lin, np.int64, "palace_bai_linear: lin")
+        assert np.array_equal(_unguard(d_n_intv, n_ref, np.int32, "palace_bai_linear: n_intv"), n_intv), "the second call changed n_intv"
+        assert np.array_equal(_unguard(d_stat, 4 * n_ref, np.int64, "palace_bai_linear: ref_stat"), stat), "the second call changed ref_stat"
+        return n_intv, stat.reshape(4, n_ref), lin_off, lin
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bgzf_voffsets(ctx: Ctx, u, member_u, member_c) -> np.ndarray:
+    """palace_bgzf_voffsets -> uint64 virtual offsets, one per entry of u"""
+    u, mu, mc = (np.ascontiguousarray(a, dtype=np.int64) for a in (u, member_u, member_c))
+    assert len(mu) == len(mc)
+    bufs = [ctx.upload(a if len(a) else np.zeros(1, np.int64)) for a in (u, mu, mc)]
+    try:
+        d_v = _guarded(ctx, len(u), np.uint64)
+        bufs.append(d_v)
+        _check(lib().palace_bgzf_voffsets(ctx.h, bufs[0].ptr, len(u), bufs[1].ptr, bufs[2].ptr, len(mu), d_v.ptr), "palace_bgzf_voffsets")
+        return _unguard(d_v, len(u), np.uint64, "palace_bgzf_voffsets")
+    finally:
+        for b in bufs:
+            b.free()
+
+
 SAM_TILE = 4096          # PALACE_SAM_TILE of include/palace_hip.h
 
 

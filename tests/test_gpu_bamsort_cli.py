@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+from tests import bai_cases as bai
 from tests import bam_sort_cases as bc
 from tests import gz_util
 from tests.bai_reader import PSEUDO_BIN, IndexedBam, read_bai
@@ -296,3 +297,40 @@ def test_index_refuses_an_unsorted_file_and_records_a_bai_cannot_hold(tmp_path):
         p = run(["--index", bam])
         assert p.returncode == 1 and p.stdout == b"" and p.stderr.startswith(b"bamsort: ") and message in p.stderr and p.stderr.count(b"\n") == 1, p.stderr
         assert not os.path.exists(str(bam) + ".bai")
+
+
+# ---- more targets than 16 bits count: the index's per-reference kernels and run keys in the executable ------------------------------
+def test_seventy_thousand_targets(tmp_path):
+    """records on the references around 256 and 65 536 and on 900 others of 70 000, most references without any: the run key's reference
+    bits above 16 and several workgroups of the per-reference kernels, through the executable"""
+    n_ref, tlen = 70000, 100000
+    targets = [(f"t{k}", tlen) for k in range(n_ref)]
+    recs, used = bai.many_reference_records(random.Random(70), n_ref, 900, tlen, 25)
+    assert 3000 < len(recs) < 5500 and {65535, 65536, 65537} <= set(used)
+    text = "@HD\tVN:1.6\tSO:unsorted\n"
+
+    def head(t):                                                            # (header() appends target by target: too slow for 70 000)
+        return b"BAM\1" + struct.pack("<i", len(t)) + t.encode() + struct.pack("<i", n_ref) + b"".join(
+            struct.pack("<i", len(n) + 1) + n.encode() + b"\0" + struct.pack("<i", l) for n, l in targets)
+
+    src, out = tmp_path / "in.bam", tmp_path / "out.bam"
+    src.write_bytes(gz_util.bgzf(head(text) + b"".join(recs), level=1))
+    sort_ok(["-o", out, "--bai", src])
+    read_sorted(out, head(bc.rewrite_text(text)) + b"".join(bc.sorted_records(recs, n_ref)))
+    ib = IndexedBam(out)
+    assert ib.targets == targets and len(ib.bai["refs"]) == n_ref and ib.bai["n_no_coor"] == 25
+    rng = random.Random(71)
+    empty = [t for t in (2, 254, 2000, 2999, 65534, 65538, 66000, 66999, 69998) + tuple(rng.sample(range(n_ref), 12)) if t not in used]
+    assert len(empty) >= 8
+    for tid in empty:
+        assert ib.bai["refs"][tid] == dict(bins={}, order=[], ioff=[]) and ib.fetch(tid, 0, tlen) == ib.brute(tid, 0, tlen) == []
+    hits = 0
+    for tid in list(bai.FORCED_REFS) + rng.sample(used, 10):
+        for beg, end in ((0, tlen), (16383, 16385), (40000, 60000), (rng.randrange(tlen), tlen)):
+            want = ib.brute(tid, beg, end)
+            assert ib.fetch(tid, beg, end) == want and ib.fetch(tid, beg, end, use_linear=False) == want, (tid, beg, end)
+            hits += len(want)
+    assert hits > 150
+    other = tmp_path / "other.bai"
+    sort_ok(["--index", out, other])
+    assert other.read_bytes() == (tmp_path / "out.bam.bai").read_bytes()
