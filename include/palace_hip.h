@@ -908,6 +908,29 @@ int palace_fai_rows_plan(palace_ctx *ctx, const palace_fasta_rec *d_recs, const 
 int palace_fai_rows_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records,
                           const int64_t *d_row_off, uint8_t *d_out);
 
+/* ---- the phage scorer's input: k-mer pair features of every record of an indexed FASTA (phage_scoring; the rules: DESIGN.md 8) */
+
+#define PALACE_CONTIG_FEATURES 12288       /* 3 distances x 64 x 64 pairs of 3-mers */
+#define PALACE_CONTIG_FSUMS    64          /* row sums of the first distance's matrix */
+#define PALACE_CONTIG_CHUNK_BASES 4096     /* positions of a record's sequence (kept or dropped) that one workgroup looks at; a
+                                            * record with more of them is counted by several workgroups into one row */
+
+typedef struct { int64_t length, bases; } palace_contig_info;      /* |S| and m: sequence bytes, and those that are A C G T a c g t */
+
+/* The features of records [r0, r1) of the text d_text[0 .. n) under the index d_recs (palace_fasta_index without a fault).  Of a
+ * record's sequence bytes S those that are A C G T in either case are kept and coded 0 1 2 3: v[0 .. m); loc[i] = 16 v[i] +
+ * 4 v[i+1] + v[i+2]; C[d][loc[i]][loc[i+3+d]] counts 0 <= i < m - 5 - d for d = 0, 1, 2.  Row r - r0 of d_feat (PALACE_CONTIG_FEATURES
+ * floats a row, 16-byte aligned) gets float(double(C[d][a][b]) / double(length) * 100.0) at (a * 64 + b) * 3 + d, row r - r0 of
+ * d_fsum (PALACE_CONTIG_FSUMS floats) the same of the exact integer sum over b of C[0][a][b]; length 0 gives NaN in both.  d_info,
+ * when not null, gets a record's length and m.  *d_bad: the smallest text offset of a byte '0'..'9' in a sequence of [r0, r1),
+ * else -1; digits are dropped like every other byte, the caller decides what they mean.  Writes rows [0, r1 - r0) and nothing
+ * else; r0 == r1 writes *d_bad alone.  Eleven launches whatever the text holds; the counts are integers added with integer
+ * atomics, so the same call gives the same bytes.  d_scratch (16-byte aligned): palace_contig_features_scratch_bytes(n, r1 - r0)
+ * bytes.  Enqueues only. */
+size_t palace_contig_features_scratch_bytes(int64_t n_text, int64_t n_records);
+int palace_contig_features(palace_ctx *ctx, const uint8_t *d_text, int64_t n, const palace_fasta_rec *d_recs, int64_t r0, int64_t r1,
+                           float *d_feat, float *d_fsum, palace_contig_info *d_info, int64_t *d_bad, void *d_scratch, size_t scratch_bytes);
+
 /* ---- bamsort: a BAM coordinate-sorted and indexed where its inflated stream lies (the rules: DESIGN.md 8) --------------------- */
 
 /* One sort key per record of the stream (d_starts as palace_bam_walk leaves them): t << 33 | uint32(pos + 1) << 1 | reverse bit,

@@ -81,6 +81,8 @@ DEPTH_RUN_DTYPE = np.dtype([("sum", np.uint64), ("lines", np.uint64), ("name_off
 assert DEPTH_CURSOR_DTYPE.itemsize == 64 + 8192 and DEPTH_RUN_DTYPE.itemsize == 24
 FASTA_REC_DTYPE = np.dtype([(k, np.int64) for k in ("name_off", "name_len", "seq_off", "length", "line_bases", "line_width")])
 FASTA_TILE_BYTES = 4096                 # PALACE_FASTA_TILE_BYTES
+CONTIG_FEATURES, CONTIG_FSUMS, CONTIG_CHUNK_BASES = 12288, 64, 4096     # PALACE_CONTIG_FEATURES, _FSUMS, _CHUNK_BASES
+CONTIG_INFO_DTYPE = np.dtype([("length", np.int64), ("bases", np.int64)])
 PATH_NOTHING, PATH_NOT_FOUND, PATH_REVERSE, PATH_SECOND_TRY = -1, -2, 1, 2
 
 
@@ -271,6 +273,9 @@ _SIGS = {
     "palace_readqc_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ReadqcParams), C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(C.c_int64)],
     "palace_readqc_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_contig_features_scratch_bytes": [C.c_int64, C.c_int64],    # (returns size_t: restype set below)
+    "palace_contig_features": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                               C.c_void_p, C.c_size_t],
 }
 
 
@@ -312,6 +317,7 @@ def lib() -> C.CDLL:
         _LIB.palace_fasta_index_scratch_bytes.restype = C.c_size_t
         _LIB.palace_sort_u64_scratch_bytes.restype = C.c_size_t
         _LIB.palace_sam_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_contig_features_scratch_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -1416,6 +1422,53 @@ def fasta_index(ctx: Ctx, text: bytes, recs_cap: int | None = None):
     d_scratch.free()
     recs = d_recs.to_host()[:int(st.n_records)] if int(st.n_records) <= recs_cap else None
     return st, recs, d_text, d_recs
+
+
+def fasta_index_at(ctx: Ctx, text_ptr: int, n: int, recs_ptr, recs_cap: int, scratch_ptr: int, scratch_bytes: int) -> FastaStatus:
+    """palace_fasta_index on device pointers of the caller's; recs_ptr None with recs_cap 0 asks for the number of records"""
+    st = FastaStatus()
+    _check(lib().palace_fasta_index(ctx.h, text_ptr, n, recs_ptr, recs_cap, scratch_ptr, scratch_bytes, C.byref(st)), "palace_fasta_index")
+    return st
+
+
+def contig_features_enqueue(ctx: Ctx, text_ptr: int, n: int, recs_ptr: int, r0: int, r1: int, feat_ptr: int, fsum_ptr: int, info_ptr, bad_ptr: int,
+                            scratch_ptr: int, scratch_bytes: int):
+    """palace_contig_features on device pointers of the caller's (a torch tensor's data_ptr() is one); enqueues only"""
+    _check(lib().palace_contig_features(ctx.h, text_ptr, n, recs_ptr, r0, r1, feat_ptr, fsum_ptr, info_ptr, bad_ptr, scratch_ptr, scratch_bytes),
+           "palace_contig_features")
+
+
+def contig_features(ctx: Ctx, text: bytes, r0: int = 0, r1: int | None = None, guard_rows: int = 1, repeat: int = 1):
+    """FASTA text through palace_fasta_index and palace_contig_features for records [r0, r1): (index status, records, feat
+    [r1 - r0, 12288] float32, fsum [r1 - r0, 64] float32, info as CONTIG_INFO_DTYPE, bad).  The rows lie between guard_rows rows of
+    0xA5 bytes on either side, which must come back as they went in.  repeat: the call is made that often into the same buffers."""
+    st, recs, d_text, d_recs = fasta_index(ctx, text)
+    if st.error:
+        return st, recs, None, None, None, None
+    n_rec = int(st.n_records)
+    r1 = n_rec if r1 is None else r1
+    rows = r1 - r0
+    outs = []
+    for width, dtype in ((CONTIG_FEATURES, np.float32), (CONTIG_FSUMS, np.float32), (1, CONTIG_INFO_DTYPE)):
+        outs.append(ctx.upload(np.full((rows + 2 * guard_rows) * width * np.dtype(dtype).itemsize, 0xA5, np.uint8)))
+    d_bad = ctx.upload(np.array([12345], np.int64))
+    need = int(lib().palace_contig_features_scratch_bytes(len(text), rows))
+    d_scratch = DevBuf(ctx, max(need, 1))
+    at = [b.ptr + guard_rows * w * isz for b, w, isz in zip(outs, (CONTIG_FEATURES, CONTIG_FSUMS, 1), (4, 4, 16))]
+    for _ in range(repeat):
+        contig_features_enqueue(ctx, d_text.ptr, len(text), d_recs.ptr, r0, r1, at[0], at[1], at[2], d_bad.ptr, d_scratch.ptr, need)
+    ctx.sync()
+    got = []
+    for b, width, dtype in zip(outs, (CONTIG_FEATURES, CONTIG_FSUMS, 1), (np.float32, np.float32, CONTIG_INFO_DTYPE)):
+        raw = b.to_host()
+        g = guard_rows * width * np.dtype(dtype).itemsize
+        if not ((raw[:g] == 0xA5).all() and (raw[len(raw) - g:] == 0xA5).all()):
+            raise PalaceError("palace_contig_features wrote outside its rows")
+        got.append(raw[g:len(raw) - g].view(dtype).reshape(rows, width) if width > 1 else raw[g:len(raw) - g].view(dtype))
+    bad = int(d_bad.to_host()[0])
+    for b in outs + [d_bad, d_scratch, d_text, d_recs]:
+        b.free()
+    return st, recs, got[0], got[1], got[2], bad
 
 
 class PathFasta:
