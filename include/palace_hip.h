@@ -704,6 +704,14 @@ typedef struct palace_match_result palace_match_result;
  * the same order -- weight | path-backed | class of (tail, head) -- whenever the sample's arcs fit it, which saves the second
  * proposal pass of every matching iteration: half of the atomics and a third of the look-ups). */
 int palace_match_set_option(palace_ctx *ctx, const char *name, int64_t value);
+/* Which way the last decomposition whose result this context handed out (palace_match_decompose[_ex], palace_stage04_result)
+ * went: info[0] = how it ranked its arcs (0: by the arc's position alone, palace_match_decompose; 1: by the two-word key;
+ * 2: by the one-word key), info[1] = 1 when a round did not settle and the run with the host checking every fixed point
+ * took over (info[0], [2] and [3] then describe that run; it never uses one-word keys), info[2] = rounds enqueued (fewer than
+ * asked for when no segment kept a copy), info[3] = matching iterations enqueued, the ones behind a fixed point included.
+ * All zero after a graph without arcs.  Reads what the decomposition brought back anyway: no launch, no wait.  An error
+ * before the first decomposition. */
+int palace_match_last_run(palace_ctx *ctx, int64_t info[4]);
 int palace_match_decompose(palace_ctx *ctx, int32_t n_segs, const int64_t *copies, int64_t n_arcs,
                            const int32_t *src, const int32_t *dst, int32_t iterations, int32_t aggressive,
                            palace_match_result **out);

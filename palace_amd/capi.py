@@ -186,7 +186,8 @@ _SIGS = {
     "palace_match_arcs_from_edges": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
     "palace_match_set_option": [C.c_void_p, C.c_char_p, C.c_int64],
-    "palace_match_decompose": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
+    "palace_match_last_run": [C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_match_decompose":[C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                C.c_int32, C.POINTER(C.c_void_p)],
     "palace_match_decompose_ex": [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32,
                                   C.c_int32, C.c_int32, C.POINTER(C.c_void_p)],
@@ -1347,6 +1348,44 @@ def match_decompose(ctx: "Ctx", copies: np.ndarray, src: np.ndarray, dst: np.nda
     """palace_match_decompose -> (offsets, verts, kind, iter, open_at) as numpy copies."""
     with match_decompose_views(ctx, copies, src, dst, iterations, aggressive) as r:
         return r.off.copy(), r.verts.copy(), r.kind.copy(), r.iter.copy(), r.open_at.copy()
+
+
+MATCH_KEYS_POSITION, MATCH_KEYS_TWO_WORDS, MATCH_KEYS_ONE_WORD = 0, 1, 2      # palace_match_last_run, info[0]
+
+
+def match_last_run(ctx: "Ctx") -> dict:
+    """palace_match_last_run -> {key_mode, checked_rerun, rounds, iterations} of the last decomposition of this context"""
+    info = (C.c_int64 * 4)()
+    _check(lib().palace_match_last_run(ctx.h, info), "palace_match_last_run")
+    return dict(key_mode=int(info[0]), checked_rerun=bool(info[1]), rounds=int(info[2]), iterations=int(info[3]))
+
+
+def match_greedy(ctx: "Ctx", n_vertices: int, src, dst, alive=None):
+    """palace_match_greedy for arcs given in rank order (arc id = position) -> (next, prev, next_arc, rounds); the two CSR
+    lists of arc ids per tail and per head are built here (a stable sort keeps each list ascending in arc id)."""
+    s = np.ascontiguousarray(src, dtype=np.int32)
+    d = np.ascontiguousarray(dst, dtype=np.int32)
+    al = np.ones(n_vertices, np.uint8) if alive is None else np.ascontiguousarray(alive, dtype=np.uint8)
+    assert len(s) == len(d) and len(al) == n_vertices
+    assert not len(s) or (0 <= min(s.min(), d.min()) and max(s.max(), d.max()) < n_vertices)
+
+    def csr(ends):
+        off = np.zeros(n_vertices + 1, np.int64)
+        np.cumsum(np.bincount(ends, minlength=n_vertices), out=off[1:])
+        return off, np.argsort(ends, kind="stable").astype(np.int32)
+
+    (out_off, out_arcs), (in_off, in_arcs) = csr(s), csr(d)
+    bufs = [ctx.upload(a) for a in (s, d, out_off, out_arcs, in_off, in_arcs, al)]
+    outs = [ctx.empty(max(1, n_vertices), np.int32) for _ in range(3)]
+    rounds = C.c_int32()
+    try:
+        _check(lib().palace_match_greedy(ctx.h, n_vertices, len(s), *(b.ptr for b in bufs), *(o.ptr for o in outs), C.byref(rounds)),
+               "palace_match_greedy")
+        nxt, prv, arc = (o.to_host()[:n_vertices] for o in outs)
+    finally:
+        for b in bufs + outs:
+            b.free()
+    return nxt, prv, arc, rounds.value
 
 
 class Stage04:

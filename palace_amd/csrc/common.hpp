@@ -95,6 +95,7 @@ struct palace_ctx {
     int match_grid = 0;             // workgroups of the decomposition's arc- and vertex-sized phases (0 = default; decomp.hip)
     bool match_two_word_keys = false; // option: the decomposition never uses the one-word form of the arc keys (A/B runs, tests)
     int match_iters = 0;            // matching iterations enqueued per round (0 = defaults; tests lower it to force the checked path)
+    int64_t match_last[4] = {-1, 0, 0, 0};    // palace_match_last_run: key mode, checked rerun, rounds, iterations of the last decomposition
     uint64_t *d_small = nullptr;   // 64 x u64 scratch for reductions
 };
 

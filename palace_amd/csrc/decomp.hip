@@ -496,7 +496,7 @@ int decomp_rounds(palace_ctx *ctx, const DecompBufs &b, int t0, int t1, int roun
 // takes (a chain of ascending weights needs as many iterations as it has arcs).  Only used when decomp_enqueue's fixed
 // number of iterations did not suffice (`unsettled`); needs rounds * 2^21 / ... never more than 2^21 iterations in all.
 int decomp_run_checked(palace_ctx *ctx, const DecompBufs &b, int rounds, int aggressive, bool unique_hi, int64_t comp_cap,
-                       int64_t vert_cap, int64_t max_iterations)
+                       int64_t vert_cap, int64_t max_iterations, uint64_t *iterations_out)
 {
     PALACE_REQUIRE(rounds >= 1 && rounds <= kMaxRounds, "round count out of range");
     constexpr int kBatch = 16;                                              // even: the klo parity carries over
@@ -520,6 +520,7 @@ int decomp_run_checked(palace_ctx *ctx, const DecompBufs &b, int rounds, int agg
         int rc = enqueue_read_off(ctx, b, t, kBatch - 1);
         if (rc) return rc;
     }
+    if (iterations_out) *iterations_out = count;
     return PALACE_OK;
 }
 
@@ -531,6 +532,7 @@ int decomp_group(palace_ctx *ctx, const DecompBufs &b, DecompRun &run, int round
         const int iters = ctx->match_iters > 0 ? std::min(ctx->match_iters, kMaxIters) : (t == 0 ? kFirstRoundIters : kLaterRoundIters);
         int rc = decomp_rounds(ctx, b, t, t + 1, rounds, aggressive, iters, unique_hi, &run.count);
         if (rc) return rc;
+        run.rounds++;
     }
     run.next_round = t1;
     return PALACE_OK;
@@ -547,7 +549,8 @@ int decomp_finish(palace_ctx *ctx, const DecompBufs &b, DecompRun &run, int roun
             // decomposition once more, with the host watching every round's fixed point
             int rc = reset_left();
             if (rc) return rc;
-            rc = decomp_run_checked(ctx, b, rounds, aggressive, unique_hi, comp_cap, vert_cap, max_iterations);
+            run.checked = true; run.rounds = rounds; run.count = 0;
+            rc = decomp_run_checked(ctx, b, rounds, aggressive, unique_hi, comp_cap, vert_cap, max_iterations, &run.count);
             if (rc) return rc;
             PALACE_HIP_TRY(hipMemcpyAsync(h_state, b.st, sizeof *h_state, hipMemcpyDeviceToHost, ctx->stream));
             PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));

@@ -91,14 +91,25 @@ int decomp_rounds(palace_ctx *ctx, const DecompBufs &b, int t0, int t1, int roun
 // The usual way through: decomp_begin, decomp_group (the next kRoundsPerGroup rounds; only enqueues), then decomp_finish, which
 // reads the state back after every group, enqueues further groups while segments keep copies, and redoes the decomposition
 // with decomp_run_checked (after `reset_left` has put the copy numbers back) should a round not have settled.  h_state: pinned.
-struct DecompRun { int next_round = 0; uint64_t count = 0; };
+// (rounds / count: rounds and matching iterations enqueued so far; checked: decomp_run_checked took over and the two count its run)
+struct DecompRun { int next_round = 0; uint64_t count = 0; int rounds = 0; bool checked = false; };
 int decomp_group(palace_ctx *ctx, const DecompBufs &b, DecompRun &run, int rounds, int aggressive, bool unique_hi);
 int decomp_finish(palace_ctx *ctx, const DecompBufs &b, DecompRun &run, int rounds, int aggressive, bool unique_hi, int64_t comp_cap,
                   int64_t vert_cap, int64_t max_iterations, DecompState *h_state, const std::function<int()> &reset_left);
 
 // The same with the host checking for each round's fixed point (any number of iterations); synchronises the stream.
 int decomp_run_checked(palace_ctx *ctx, const DecompBufs &b, int rounds, int aggressive, bool unique_hi, int64_t comp_cap,
-                       int64_t vert_cap, int64_t max_iterations);
+                       int64_t vert_cap, int64_t max_iterations, uint64_t *iterations_out = nullptr);
+
+// what palace_match_last_run reports: key mode (0 khi alone, 1 two words, 2 one word) from the state decomp_finish read back,
+// the rest from `run`
+inline void decomp_note_run(palace_ctx *ctx, const DecompRun &run, const DecompState &h_state, bool unique_hi)
+{
+    ctx->match_last[0] = unique_hi ? 0 : (h_state.packed ? 2 : 1);
+    ctx->match_last[1] = run.checked ? 1 : 0;
+    ctx->match_last[2] = run.rounds;
+    ctx->match_last[3] = static_cast<int64_t>(run.count);
+}
 
 // exclusive scan of u64 values whose count *n_dev lives on the device: 3 launches on the stream; total -> *total_dev
 int scan_u64(palace_ctx *ctx, const uint64_t *in, uint64_t *out, const int32_t *n_dev, uint64_t *partials, uint64_t *total_dev);

@@ -753,6 +753,7 @@ int palace_stage04_result(palace_ctx *ctx, palace_stage04 *s, palace_match_resul
     };
     int rc = decomp_finish(ctx, s->b, s->run, rounds, s->aggressive, false, s->comp_cap, s->vert_cap, 2 * s->e_cap + 64, s->h_ds, reset_left);
     if (rc) return rc;
+    decomp_note_run(ctx, s->run, *s->h_ds, false);
     rc = check_filter_state(*s->h_fs);                          // (in since the first wait of decomp_finish)
     if (rc) return rc;
     const DecompState &ds = *s->h_ds;

@@ -282,6 +282,7 @@ static int decompose_core(palace_ctx *ctx, int32_t n_segs, const int64_t *copies
         return PALACE_OK;
     };
     if ((rc = decomp_finish(ctx, b, run, rounds, aggressive, true, comp_cap, vert_cap, 2 * E + 64, p_back, reset_left))) return fail(rc);
+    decomp_note_run(ctx, run, *p_back, true);
     if (p_back->overflow || p_back->n_comp > comp_cap || p_back->n_vert > vert_cap) {
         set_error("decompose: component arrays too small (%lld components, %lld vertices)", (long long)p_back->n_comp, (long long)p_back->n_vert);
         return PALACE_ESTATE;
@@ -400,6 +401,14 @@ int palace_match_set_option(palace_ctx *ctx, const char *name, int64_t value)
     return PALACE_OK;
 }
 
+int palace_match_last_run(palace_ctx *ctx, int64_t info[4])
+{
+    PALACE_REQUIRE(ctx && info, "null argument");
+    PALACE_REQUIRE(ctx->match_last[0] >= 0, "no decomposition has run on the device through this context");
+    std::copy(ctx->match_last, ctx->match_last + 4, info);
+    return PALACE_OK;
+}
+
 int palace_match_decompose(palace_ctx *ctx, int32_t n_segs, const int64_t *copies, int64_t n_arcs,
                            const int32_t *src, const int32_t *dst, int32_t iterations, int32_t aggressive,
                            palace_match_result **out)
@@ -465,6 +474,7 @@ int palace_match_decompose_ex(palace_ctx *ctx, int32_t n_segs, const int64_t *co
     int rc = n_sub ? decompose_core(ctx, n_sub, sub_copies.data(), old_id.data(), n_arcs, ssrc.data(), sdst.data(), iterations, aggressive, &sub)
                    : PALACE_OK;                            // (vertices come back as ids of the caller's graph)
     if (rc) return rc;
+    if (!n_sub) { const int64_t none[4] = {0, 0, 0, 0}; std::copy(none, none + 4, ctx->match_last); }     // no arc: nothing was enqueued
     const int64_t n_sub_comp = static_cast<int64_t>(sub.kind.size());
     const int last_round = iterations + (aggressive ? 1 : 0) - 1;
     const int64_t n_bare = static_cast<int64_t>(n_segs) - n_sub;

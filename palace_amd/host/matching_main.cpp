@@ -6,8 +6,9 @@
 // (filter_result.py:125-134, make_fa_from_path.py:94-137, remove_cycle_dup.py:9-13): the linear
 // file holds one path per line, tokens `<seg><+|->` separated by tabs, no marker lines; the cycle
 // file holds two-line records, a marker line (`iter <n>` or `self`) followed by the cycle's tokens.
-// The decomposition itself is this repository's algorithm (DESIGN.md "matching"); the greedy
-// matching of every iteration runs on the GPU (palace_match_greedy), the rest is bookkeeping.
+// The decomposition itself is this repository's algorithm (DESIGN.md "matching"); all of it -- the
+// greedy matching of every round, the read-off, the copy numbers -- runs on the GPU
+// (palace_match_decompose); this file reads, ranks the arcs and formats.
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>

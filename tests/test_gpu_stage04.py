@@ -99,10 +99,24 @@ def _file_chain(tmp_path, files, avg, flags):
     return open(P("lin.txt")).read(), open(P("cyc.txt")).read(), open(P("filt.txt")).read()
 
 
-@pytest.mark.parametrize("seed,n_contigs,n_events,flags,iters", [(5, 60, 4000, ["-s"], 0), (6, 400, 30000, ["-s"], 0), (6, 400, 30000, ["-s"], 1),
-                                                                   (7, 400, 30000, ["-b", "--aggressive"], 0), (7, 400, 30000, ["-b", "--aggressive"], 2),
-                                                                   (8, 2500, 120000, ["-s"], 0)])
-def test_in_memory_stage04_equals_the_file_chain(tmp_path, seed, n_contigs, n_events, flags, iters):
+def _cpu_oracle_on_the_chain_s_files(tmp_path, flags):
+    """oracle/match_oracle.cpp on the filtered graph and the paths _file_chain left in tmp_path: the chain ends in bin/matching,
+    which runs the kernels the in-memory stage 04 runs -- this is the side of the comparison that no kernel computes"""
+    from oracle import binding as orc
+    lin, cyc = orc.match_run(str(tmp_path / "filt.txt"), str(tmp_path / "contigs_paths"), 10, self_loops="-s" in flags, break_cycles="-b" in flags,
+                             aggressive="--aggressive" in flags)
+    return lin.decode(), cyc.decode()
+
+
+# (one_word 0: the two-word rank key although the arcs fit one word; the ids of the rows that were here before it are unchanged)
+_CHAIN_ROWS = [(5, 60, 4000, ["-s"], 0, 1), (6, 400, 30000, ["-s"], 0, 1), (6, 400, 30000, ["-s"], 1, 1), (7, 400, 30000, ["-b", "--aggressive"], 0, 1),
+               (7, 400, 30000, ["-b", "--aggressive"], 2, 1), (8, 2500, 120000, ["-s"], 0, 1),
+               (6, 400, 30000, ["-s"], 0, 0), (7, 400, 30000, ["-b", "--aggressive"], 0, 0), (7, 400, 30000, ["-b", "--aggressive"], 2, 0)]
+
+
+@pytest.mark.parametrize("seed,n_contigs,n_events,flags,iters,one_word", _CHAIN_ROWS,
+                         ids=["%d-%d-%d-flags%d-%d%s" % (r[0], r[1], r[2], i, r[4], "" if r[5] else "-two_word_keys") for i, r in enumerate(_CHAIN_ROWS)])
+def test_in_memory_stage04_equals_the_file_chain(tmp_path, seed, n_contigs, n_events, flags, iters, one_word):
     from oracle import binding as orc
     rng = synth.rng_for(seed)
     targets, fai_text, recs, avg = synth.random_graph_case(rng, n_contigs, n_events)
@@ -113,9 +127,11 @@ def test_in_memory_stage04_equals_the_file_chain(tmp_path, seed, n_contigs, n_ev
     graph = orc.graph_run(recs, targets, str(tmp_path / "g.fastg.fai"), avg, o).decode()      # a `_graph.txt` (the checker's; any would do)
     files = dict(graph=graph, fastg_fai=fai_text, **synth.filter_side_files(rng, names, lens))
     lin, cyc, filt = _file_chain(tmp_path, files, avg, flags)
+    assert (lin, cyc) == _cpu_oracle_on_the_chain_s_files(tmp_path, flags)
     case = _load_case(files, tmp_path)
     with capi.Ctx(0) as ctx:
         ctx.match_set_option("iters_per_round", iters)         # 0: the defaults; 1 or 2: rounds do not settle, the host-checked run takes over
+        ctx.match_set_option("one_word_keys", one_word)        # 0: the two-word rank key although the arcs fit one word
         st, d_e, d_n = _run_filter(ctx, case, min_count=0)
         d_cn = ctx.upload(case["cn"])
         st.match(d_e.ptr, d_cn.ptr, 10, "--aggressive" in flags, True)
@@ -123,7 +139,10 @@ def test_in_memory_stage04_equals_the_file_chain(tmp_path, seed, n_contigs, n_ev
         got_lin, got_cyc = stage04_io.matching_text(res, contig_of, names, self_loops="-s" in flags, break_cycles="-b" in flags)
         seg_order = [names[c] for c in contig_of]              # (views into the object's pinned memory: read before close)
         counts = st.counts()
+        how = capi.match_last_run(ctx)
         st.close()
+    assert how["key_mode"] == (capi.MATCH_KEYS_ONE_WORD if one_word and not how["checked_rerun"] else capi.MATCH_KEYS_TWO_WORDS)
+    assert how["checked_rerun"] or iters != 1                  # (one iteration takes an arc, so its round has not settled)
     assert seg_order == [l.split(" ")[1] for l in filt.splitlines() if l.startswith("SEG")]     # the file's SEG order
     assert got_lin == lin
     assert got_cyc == cyc
@@ -278,6 +297,7 @@ def test_device_stage04_equals_the_file_chain_on_adversarial_graphs(case, flags)
     with tempfile.TemporaryDirectory(prefix="palace_s4fuzz_") as d:
         tmp = Path(d)
         lin, cyc, filt = _file_chain(tmp, files, 5.0, flags)
+        assert (lin, cyc) == _cpu_oracle_on_the_chain_s_files(tmp, flags)
         case_arrays = _load_case(files, tmp)
     with capi.Ctx(0) as ctx:
         st, d_e, d_n = _run_filter(ctx, case_arrays, min_count=0)

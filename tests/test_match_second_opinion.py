@@ -1,6 +1,7 @@
 """oracle/match_oracle.cpp against tests/match_bruteforce.py (an independent Python statement of the same prose) on every
 kind of tiny graph hypothesis finds: <= 12 segments, self loops, self-conjugate junctions, parallel junctions, equal weights.
-CPU only; tests/test_gpu_cli.py::test_matching_second_opinion_on_the_gpu repeats it against the executable."""
+CPU only; tests/test_host_match_model.py adds a third statement (tests/match_cases.py: every field of every component) on the
+same strategy, and tests/test_gpu_match_abi.py holds the device to it at the C ABI."""
 import os
 
 import pytest
