@@ -517,7 +517,9 @@ enum {
     PALACE_GZ_ISIZE = 8,
     PALACE_GZ_TRAILING = 9,    /* bytes that are no gzip member behind the last one */
     PALACE_GZ_SINK = 10,       /* the sink returned non-zero */
-    PALACE_GZ_MARKER = 11      /* a reference to before the start of a member */
+    PALACE_GZ_MARKER = 11      /* a match that reaches before the start of its member (zlib: "invalid distance too far back"),
+                                * in whichever chunk of the member: the chain compares every chunk's reach before its own start
+                                * with the member's text so far */
 };
 
 /* chunks_found: block starts the finder reported; chunks_accepted: chunks on the chain (decoded to text); false_hits: reported

@@ -52,10 +52,10 @@ __device__ __forceinline__ GzResult inflate_chunk(const uint32_t *in, int64_t n_
     BitReader br;
     br.base = in;
     br.last = n_bytes > 0 ? (n_bytes - 1) >> 2 : -1;
-    int64_t opos = 0;
+    int64_t opos = 0, reach = 0;
     int32_t err = kInfOk;
     bool fin = false;
-    if (c.start < 0 || c.start >= end_bit) return GzResult{0, c.start, 0, kInfInput};
+    if (c.start < 0 || c.start >= end_bit) return GzResult{0, c.start, 0, kInfInput, 0};
     const int64_t far = c.stop < end_bit - kGzFarBits ? c.stop + kGzFarBits : end_bit + 128;
     br.seek(c.start);
     auto written = [] { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); };
@@ -114,7 +114,10 @@ __device__ __forceinline__ GzResult inflate_chunk(const uint32_t *in, int64_t n_
             br.refill();
             dist_code(ds, dbase, dextra);
             const int32_t d = dbase + static_cast<int32_t>(br.take(dextra));    // <= 32768
-            if (d > opos && c.first) { err = kInfBadDistance; break; }         // before the start of the member
+            if (d > opos) {                                                    // before the chunk: known to the window alone, counted here
+                if (c.first) { err = kInfBadDistance; break; }                 // ... and before the start of the member
+                if (d - opos > reach) reach = d - opos;
+            }
             if (kWrite) {
                 if (len > c.out_len - opos) { err = kInfOverrun; break; }
                 written();
@@ -133,7 +136,7 @@ __device__ __forceinline__ GzResult inflate_chunk(const uint32_t *in, int64_t n_
     // straddles the end of the span fails as a bad code): it says "more input", and the host decides what that means.
     if (err != kInfOk && br.bit_pos() + 64 > end_bit) err = kInfInput;
     if (kWrite && err == kInfOk && opos != c.out_len) err = kInfSize;
-    return GzResult{opos, br.bit_pos(), fin ? 1 : 0, err};
+    return GzResult{opos, br.bit_pos(), fin ? 1 : 0, err, reach};
 }
 
 __global__ __launch_bounds__(64) void gz_size_kernel(const uint32_t *in, int64_t n_bytes, const GzChunk *chunks, GzResult *res, int64_t n)
@@ -339,6 +342,7 @@ extern "C" int palace_gzip_inflate(palace_ctx *ctx, const uint8_t *file, int64_t
     if (hdr < 0) return decline(PALACE_GZ_HEADER);
     int64_t cur_abs = hdr * 8;                                                 // the certain start: a bit of the file
     int32_t first = 1;
+    int64_t member_text = 0;                                                   // of the member cur_abs lies in, before cur_abs
     bool file_done = false;
     palace_host::MemberCheck check;
     std::vector<GzChunk> ch;
@@ -390,18 +394,18 @@ extern "C" int palace_gzip_inflate(palace_ctx *ctx, const uint8_t *file, int64_t
         for (int64_t h : hits)
             if (h > cur && h < end_bits) { ch.back().stop = h; ch.push_back(GzChunk{h, end_bits, 0, 0, 0, 0}); }
         st->chunks_found += static_cast<int64_t>(ch.size()) - 1;
-        res.assign(ch.size() + 1, GzResult{0, 0, 0, 0});
+        res.assign(ch.size() + 1, GzResult{0, 0, 0, 0, 0});
         if (int rc = size_pass(0, ch.size(), n_bytes)) return rc;
 
         // ---- the chain (host/gzip_member.hpp) ----
         const palace_host::GzSpan sp{file, size, a, end_bits, at_eof, cap, kGzMaxRounds};
-        palace_host::GzChainState cs{cur, first, false};
+        palace_host::GzChainState cs{cur, first, false, member_text};
         const std::vector<GzChunk> cand = ch;
         const std::vector<GzResult> cand_res(res.begin(), res.begin() + static_cast<long>(cand.size()));
         int device_rc = 0;
         const int why = palace_host::gz_chain_walk(sp, cand, cand_res, cs, acc, [&](const GzChunk &c, GzResult *r) -> int {
             ch.assign(1, c);
-            res.assign(2, GzResult{0, 0, 0, 0});
+            res.assign(2, GzResult{0, 0, 0, 0, 0});
             if (int rc = size_pass(0, 1, n_bytes)) return rc;
             *r = res[0];
             return 0;
@@ -409,7 +413,7 @@ extern "C" int palace_gzip_inflate(palace_ctx *ctx, const uint8_t *file, int64_t
         st->false_hits += cs.false_hits; st->rounds += cs.rounds; st->members += cs.members;
         if (why < 0) return device_rc;
         if (why) return decline(why);
-        first = cs.first; file_done = cs.file_done;
+        first = cs.first; file_done = cs.file_done; member_text = cs.member_text;
         cur_abs = rel + cs.pos;
         st->chunks_accepted += static_cast<int64_t>(acc.size());
 
@@ -461,7 +465,7 @@ extern "C" int palace_gzip_inflate(palace_ctx *ctx, const uint8_t *file, int64_t
             uint8_t *dm = d_meta.as<uint8_t>();
             GzChunk *dc = reinterpret_cast<GzChunk *>(dm);
             GzResult *dr = reinterpret_cast<GzResult *>(dm + o_res);
-            res.assign(n + 1, GzResult{0, 0, 0, 0});
+            res.assign(n + 1, GzResult{0, 0, 0, 0, 0});
             {
                 Lap lap(st->ms_decode);
                 PALACE_HIP_TRY(hipMemcpyAsync(dm, meta.data(), o_crc, hipMemcpyHostToDevice, s));

@@ -71,6 +71,7 @@ struct GzChunk {
 struct GzResult {
     int64_t out_len, end_bit;
     int32_t fin, status;                         // fin: a final block ended the chunk; status: 0, or the decoder's refusal
+    int64_t reach;                               // how far the chunk's matches reach before its own first byte (the largest distance - position; 0: not at all)
 };
 constexpr int32_t kGzOk = 0, kGzNeedsInput = 6;  // (= kInfOk, kInfInput of the device decoder)
 struct GzAccepted {                              // a chunk on the chain
@@ -90,15 +91,19 @@ struct GzChainState {
     int64_t pos;                                 // the next certain start (bits from the span's first byte)
     int32_t first;                               // ... opens a member
     bool file_done;
+    int64_t member_text = 0;                     // text of the member `pos` lies in, before `pos` (carried from span to span, as `first` is)
     int64_t false_hits = 0, rounds = 0, members = 0;
 };
-enum { kGzWhyHeader = 1, kGzWhyDecode = 2, kGzWhyChainOpen = 3, kGzWhyNoProgress = 4, kGzWhyTooBig = 5, kGzWhyTruncated = 6, kGzWhyTrailing = 9 };
+enum { kGzWhyHeader = 1, kGzWhyDecode = 2, kGzWhyChainOpen = 3, kGzWhyNoProgress = 4, kGzWhyTooBig = 5, kGzWhyTruncated = 6, kGzWhyTrailing = 9, kGzWhyMarker = 11 };
 
 // Walks the chain from st.pos over the sized candidates ch / res (ascending starts): a chunk is accepted when it starts where its
 // predecessor ended; candidates the chain ran across are false hits; a position without a candidate is sized alone through
 // size_one(chunk, &result) (non-zero = a device error, handed back in *device_rc).  Behind a final block the trailer and the next
 // member's header are parsed here.  Ends at the end of the file, or at the chunk whose block ends behind the span (st.pos: where the
-// next span starts).  Returns 0, or why the file is declined (PALACE_GZ_*); -1 with *device_rc set.
+// next span starts).  A chunk whose matches reach further back than its member has text before it (GzResult::reach against the running
+// count st.member_text) refers to bytes before the member's start: zlib's "invalid distance too far back", declined as kGzWhyMarker --
+// the window the chunk would be resolved through holds zeros or the previous member's text there, and only the CRC would stand against it.
+// Returns 0, or why the file is declined (PALACE_GZ_*); -1 with *device_rc set.
 template <class SizeOne>
 int gz_chain_walk(const GzSpan &sp, const std::vector<GzChunk> &ch, const std::vector<GzResult> &res, GzChainState &st,
                   std::vector<GzAccepted> &acc, SizeOne &&size_one, int *device_rc)
@@ -124,6 +129,7 @@ int gz_chain_walk(const GzSpan &sp, const std::vector<GzChunk> &ch, const std::v
         }
         if (r.status != kGzOk || r.end_bit <= c.start) return kGzWhyDecode;
         if (r.out_len > sp.cap) return kGzWhyTooBig;
+        if (r.reach > st.member_text) return kGzWhyMarker;
         GzAccepted ac{c.start, r.end_bit, r.out_len, st.first, -1};
         if (r.fin) {
             const int64_t tb = sp.a + ((r.end_bit + 7) >> 3);
@@ -137,9 +143,11 @@ int gz_chain_walk(const GzSpan &sp, const std::vector<GzChunk> &ch, const std::v
                 st.pos = hdr * 8 - sp.a * 8;
                 st.first = 1;
             }
+            st.member_text = 0;
         } else {
             st.pos = r.end_bit;
             st.first = 0;
+            st.member_text += r.out_len;
         }
         acc.push_back(ac);
     }

@@ -4,7 +4,10 @@
 //   gzip_selftest chain FILE STRIDE SPAN      gz_chain_walk (gzip_member.hpp) over spans of the file without a device: the candidates are
 //                                             the true dynamic block starts a finder would report per stride (every fifth one moved a
 //                                             few bits: a false hit), the size pass is zlib from a bit position; the chunks on the chain
-//                                             must add up to zlib's text, member for member
+//                                             must add up to zlib's text, member for member.  With a fifth argument `reach` the size
+//                                             pass also reports how far a chunk reaches before its own start (the smallest preset
+//                                             dictionary zlib decodes it with), and a file zlib refuses for a distance too far back
+//                                             must be declined by the walk: "declined: 11"
 //   gzip_selftest inflate FILE [STRIDE SPAN]  palace_gzip_inflate on the file, its text against zlib's (CRC-32 and length), the counters
 //                                             and stage times; the driver for `rocprofv3 --kernel-trace --stats` (eref leaves through _exit)
 #include <zlib.h>
@@ -33,14 +36,15 @@ static std::vector<uint8_t> read_file(const char *path)
 }
 
 // raw inflate from bit `bit` of file[0 .. limit) with Z_BLOCK: stops at the first block boundary at or after `stop` or behind a final
-// block; the unknown window is 32 KiB of zeros (lengths and positions do not depend on it)
-static GzResult zlib_size(const uint8_t *file, int64_t limit, int64_t bit, int64_t stop)
+// block; the unknown window is `window` bytes of zeros (lengths and positions do not depend on it; a match that reaches further back
+// than `window` is zlib's "invalid distance too far back")
+static GzResult zlib_size(const uint8_t *file, int64_t limit, int64_t bit, int64_t stop, int window = 32768)
 {
-    GzResult r{0, bit, 0, kGzOk};
+    GzResult r{0, bit, 0, kGzOk, 0};
     z_stream zs{};
     if (inflateInit2(&zs, -15) != Z_OK) { r.status = 2; return r; }
     static const std::vector<uint8_t> zeros(32768, 0);
-    inflateSetDictionary(&zs, zeros.data(), 32768);
+    if (window > 0) inflateSetDictionary(&zs, zeros.data(), static_cast<uInt>(window));
     int64_t byte = bit >> 3;
     const int k = static_cast<int>(bit & 7);
     if (byte >= limit) { inflateEnd(&zs); r.status = kGzNeedsInput; return r; }
@@ -63,6 +67,20 @@ static GzResult zlib_size(const uint8_t *file, int64_t limit, int64_t bit, int64
         if ((zs.data_type & 128) && pos > bit && pos >= stop) { r.end_bit = pos; break; }
     }
     inflateEnd(&zs);
+    return r;
+}
+
+// ... and with the chunk's reach before its own start: the smallest window zlib decodes it with (by bisection)
+static GzResult zlib_size_reach(const uint8_t *file, int64_t limit, int64_t bit, int64_t stop)
+{
+    GzResult r = zlib_size(file, limit, bit, stop);
+    if (r.status != kGzOk) return r;
+    int lo = 0, hi = 32768;                                                     // decodes with hi, not with any window below lo
+    while (lo < hi) {
+        const int mid = (lo + hi) / 2;
+        if (zlib_size(file, limit, bit, stop, mid).status == kGzOk) hi = mid; else lo = mid + 1;
+    }
+    r.reach = lo;
     return r;
 }
 
@@ -89,13 +107,14 @@ static std::vector<Block> block_starts(const std::vector<uint8_t> &f)
     return blocks;
 }
 
-static int run_chain(const std::vector<uint8_t> &f, int64_t stride, int64_t span)
+static int run_chain(const std::vector<uint8_t> &f, int64_t stride, int64_t span, bool with_reach)
 {
     const int64_t size = static_cast<int64_t>(f.size());
     const std::vector<Block> blocks = block_starts(f);
     // zlib's text length per member
     std::vector<uint64_t> want_len;
-    for (size_t pos = 0; pos < f.size();) {
+    bool too_far_back = false;
+    for (size_t pos = 0; pos < f.size() && !too_far_back;) {
         z_stream zs{};
         inflateInit2(&zs, 31);
         zs.next_in = const_cast<Bytef *>(f.data() + pos); zs.avail_in = static_cast<uInt>(f.size() - pos);
@@ -103,6 +122,7 @@ static int run_chain(const std::vector<uint8_t> &f, int64_t stride, int64_t span
         int rc;
         uint64_t n = 0;
         do { zs.next_out = out.data(); zs.avail_out = static_cast<uInt>(out.size()); rc = inflate(&zs, Z_NO_FLUSH); n += out.size() - zs.avail_out; } while (rc == Z_OK);
+        if (with_reach && rc == Z_DATA_ERROR && zs.msg && !std::strcmp(zs.msg, "invalid distance too far back")) { inflateEnd(&zs); too_far_back = true; break; }
         if (rc != Z_STREAM_END) { std::fprintf(stderr, "zlib refuses the file\n"); return 1; }
         pos = static_cast<size_t>(zs.next_in - f.data());
         inflateEnd(&zs);
@@ -131,14 +151,17 @@ static int run_chain(const std::vector<uint8_t> &f, int64_t stride, int64_t span
         }
         std::vector<GzResult> res;
         for (const GzChunk &c : ch) {
-            GzResult r = zlib_size(f.data() + a, b - a, c.start, c.stop);
+            GzResult r = with_reach ? zlib_size_reach(f.data() + a, b - a, c.start, c.stop) : zlib_size(f.data() + a, b - a, c.start, c.stop);
             res.push_back(r);
         }
         std::vector<GzAccepted> acc;
         const GzSpan sp{f.data(), size, a, end_bits, b == size, int64_t{1} << 30, 1 << 20};
         cs.pos = cur_abs - rel;
         int device_rc = 0;
-        const int why = gz_chain_walk(sp, ch, res, cs, acc, [&](const GzChunk &c, GzResult *r) { *r = zlib_size(f.data() + a, b - a, c.start, c.stop); return 0; }, &device_rc);
+        const int why = gz_chain_walk(sp, ch, res, cs, acc, [&](const GzChunk &c, GzResult *r) {
+            *r = with_reach ? zlib_size_reach(f.data() + a, b - a, c.start, c.stop) : zlib_size(f.data() + a, b - a, c.start, c.stop);
+            return 0;
+        }, &device_rc);
         if (why) { std::printf("declined: %d (span %lld)\n", why, static_cast<long long>(spans)); return 1; }
         for (const GzAccepted &x : acc) {
             member += static_cast<uint64_t>(x.out_len);
@@ -150,6 +173,7 @@ static int run_chain(const std::vector<uint8_t> &f, int64_t stride, int64_t span
     std::printf("spans %lld candidates %lld false_made %lld accepted %lld false_hits %lld rounds %lld members %lld\n", static_cast<long long>(spans),
                 static_cast<long long>(found), static_cast<long long>(false_made), static_cast<long long>(accepted), static_cast<long long>(cs.false_hits),
                 static_cast<long long>(cs.rounds), static_cast<long long>(cs.members));
+    if (too_far_back) { std::printf("the chain accepted a file zlib refuses: invalid distance too far back\n"); return 1; }
     if (got_len != want_len) { std::printf("member lengths differ from zlib's\n"); return 1; }
     if (cs.false_hits != false_made) { std::printf("false hits: %lld made, %lld dropped\n", static_cast<long long>(false_made), static_cast<long long>(cs.false_hits)); return 1; }
     std::printf("chain ok\n");
@@ -220,7 +244,7 @@ static int run_inflate(const std::vector<uint8_t> &f, int64_t stride, int64_t sp
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: gzip_selftest blocks|chain|inflate FILE [STRIDE SPAN]\n"); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: gzip_selftest blocks|chain|inflate FILE [STRIDE SPAN [reach]]\n"); return 2; }
     const std::string mode = argv[1];
     const std::vector<uint8_t> f = read_file(argv[2]);
     const int64_t stride = argc > 3 ? std::atoll(argv[3]) : 0, span = argc > 4 ? std::atoll(argv[4]) : 0;
@@ -231,7 +255,7 @@ int main(int argc, char **argv)
         std::printf("blocks %zu dynamic_nonfinal %ld\n", b.size(), dyn);
         return 0;
     }
-    if (mode == "chain") return run_chain(f, stride > 0 ? stride : 16384, span > 0 ? span : int64_t{64} << 20);
+    if (mode == "chain") return run_chain(f, stride > 0 ? stride : 16384, span > 0 ? span : int64_t{64} << 20, argc > 5 && !std::strcmp(argv[5], "reach"));
     if (mode == "inflate") return run_inflate(f, stride, span);
     return 2;
 }

@@ -198,7 +198,7 @@ static inline __attribute__((always_inline)) bool inflate_body(const uint8_t *in
             if ((len ^ 0xffffu) != nlen) return false;
             p += 4;
             if (len > in_len - p || len > out_len - opos) return false;
-            std::memcpy(out + opos, in + p, len);
+            if (len) std::memcpy(out + opos, in + p, len);                  // (an empty block of an empty member: `out` may be null)
             opos += len;
             ipos = p + len;
             bitbuf = 0;

@@ -2,6 +2,11 @@
 //   inflate_selftest            many generated inputs x every zlib strategy / level / window, truncations and bit flips:
 //                               for every stream, inflate_fast either fails or gives exactly zlib's bytes; prints "ok <n>"
 //   inflate_selftest time <bam> decodes every BGZF member of a file with both and prints MB/s (single thread)
+//   inflate_selftest streams FILE [SLACK]
+//                               FILE: records of <in_len u32> <out_len u32> <in_len bytes of raw DEFLATE> (little endian), streams
+//                               written by hand (tests/deflate_streams.py) that zlib's encoder never makes.  One line per stream:
+//                               "<index> fast <0|1> plain <0|1> crc <CRC-32 of inflate_fast's output, 0 when refused>"; the test
+//                               holds the verdicts to its catalogue.  SLACK (default 0) readable bytes lie behind every stream.
 #include <zlib.h>
 
 #include <chrono>
@@ -169,8 +174,39 @@ static int time_file(const char *path)
     return 0;
 }
 
+static int run_streams(const char *path, size_t slack)
+{
+    const std::vector<char> f = palace_host::read_file(path);
+    size_t p = 0, index = 0;
+    while (p < f.size()) {
+        uint32_t in_len, out_len;
+        if (f.size() - p < 8) { std::fprintf(stderr, "a record is cut short\n"); return 2; }
+        std::memcpy(&in_len, f.data() + p, 4);
+        std::memcpy(&out_len, f.data() + p + 4, 4);
+        p += 8;
+        if (f.size() - p < in_len) { std::fprintf(stderr, "a record is cut short\n"); return 2; }
+        // exactly in_len + slack readable bytes and out_len writable ones, each in an allocation of its own: a read or write past
+        // either is the sanitizer build's to report; the guard bytes around the output are for the plain build
+        std::vector<uint8_t> in(in_len + slack, 0xA7), guard(static_cast<size_t>(out_len) + 64, 0x5C), other(std::max<size_t>(out_len, 1), 0x5C);
+        std::memcpy(in.data(), f.data() + p, in_len);
+        p += in_len;
+        const bool fast = inflate_fast(in.data(), in_len, slack, guard.data() + 32, out_len);
+        for (size_t i = 0; i < 32; i++)
+            if (guard[i] != 0x5C || guard[32 + out_len + i] != 0x5C) { std::fprintf(stderr, "stream %zu: write outside the output buffer\n", index); return 1; }
+        const bool plain = palace_host::inflate_detail::inflate_plain(in.data(), in_len, slack, other.data(), out_len);
+        if (fast && plain && std::memcmp(other.data(), guard.data() + 32, out_len) != 0) { std::fprintf(stderr, "stream %zu: plain and BMI2 builds give different bytes\n", index); return 1; }
+        const unsigned long crc = fast ? crc32(0, guard.data() + 32, out_len) : 0;
+        std::printf("%zu fast %d plain %d crc %08lx\n", index, fast ? 1 : 0, plain ? 1 : 0, crc);
+        index++;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc >= 3 && !std::strcmp(argv[1], "streams")) {
+        try { return run_streams(argv[2], argc > 3 ? static_cast<size_t>(std::atol(argv[3])) : 0); } catch (const std::exception &e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
+    }
     if (argc >= 3 && !std::strcmp(argv[1], "time")) {
         try { return time_file(argv[2]); } catch (const std::exception &e) { std::fprintf(stderr, "%s\n", e.what()); return 1; }
     }

@@ -44,6 +44,12 @@ def gzip_member(data: bytes, level: int = 6, fname: bytes | None = None, comment
     return head + deflate_raw(data, level) + struct.pack("<II", zlib.crc32(data), len(data) & 0xFFFFFFFF)
 
 
+def gzip_wrap(raw: bytes, text: bytes, fname: bytes | None = None) -> bytes:
+    """One gzip member around raw DEFLATE data made elsewhere (tests/deflate_streams.py): header, `raw`, CRC-32 and ISIZE of `text`."""
+    head = struct.pack("<BBBBIBB", 0x1F, 0x8B, 8, 8 if fname is not None else 0, 0, 0, 3) + (fname + b"\0" if fname is not None else b"")
+    return head + raw + struct.pack("<II", zlib.crc32(text), len(text) & 0xFFFFFFFF)
+
+
 def gzip_members(data: bytes, cuts, level: int = 6) -> bytes:
     """`data` as several gzip members, cut at the ascending positions `cuts` (anywhere: mid-record, mid-line)."""
     bounds = [0] + [c for c in cuts if 0 < c < len(data)] + [len(data)]

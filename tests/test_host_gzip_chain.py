@@ -40,3 +40,32 @@ def test_block_starts_and_chain_walk_against_zlib(tmp_path):
                 span = 1 << 30
             out = subprocess.run([TOOL, "chain", p, str(stride), str(span)], capture_output=True, text=True)
             assert out.returncode == 0 and out.stdout.endswith("chain ok\n"), (name, stride, span, out.stdout, out.stderr)
+
+
+def test_chain_walk_declines_a_chunk_that_reaches_before_its_member(tmp_path):
+    """`chain ... reach`: the size pass also reports how far a chunk's matches reach before its own start, and the walk holds that against
+    the member's text so far.  Hand-written streams (tests/deflate_streams.py): the sound ones stay on the chain at every stride and across
+    spans, the files whose later chunk reaches before the member's start are declined as PALACE_GZ_MARKER (11) where zlib says
+    "invalid distance too far back"."""
+    from tests import deflate_streams as ds
+    for g in ds.long_streams():
+        p = str(tmp_path / (g.name + ".gz"))
+        blob = gz.gzip_wrap(g.raw, g.text)
+        open(p, "wb").write(blob)
+        for stride, span in ((16384, 1 << 30), (512, len(blob) // 4 + 1), (1024, len(blob) // 4 + 1)):
+            out = subprocess.run([TOOL, "chain", p, str(stride), str(span), "reach"], capture_output=True, text=True)
+            assert out.returncode == 0 and out.stdout.endswith("chain ok\n"), (g.name, stride, span, out.stdout, out.stderr)
+            accepted = int(out.stdout.split("accepted ")[1].split()[0])
+            assert accepted >= (8 if stride == 16384 else 30), out.stdout
+    for name, (blob, _, _) in ds.reach_before_files().items():
+        p = str(tmp_path / (name + ".gz"))
+        open(p, "wb").write(blob)
+        # (the last span ends inside the offending block of the one-member file: the member's text so far is carried into the next span)
+        for stride, span in ((16384, 1 << 30), (512, 1 << 30), (512, 17500 if name == "one_member" else 40000)):
+            out = subprocess.run([TOOL, "chain", p, str(stride), str(span), "reach"], capture_output=True, text=True)
+            assert out.returncode == 1 and out.stdout.startswith("declined: 11 "), (name, stride, span, out.stdout, out.stderr)
+            if span == 17500:
+                assert out.stdout == "declined: 11 (span 2)\n"
+            # without the reach the same walk has nothing to hold against the file: only the CRC would
+            out = subprocess.run([TOOL, "chain", p, str(stride), str(span)], capture_output=True, text=True)
+            assert out.returncode == 1 and "zlib refuses the file" in out.stderr, (name, stride, out.stdout, out.stderr)
