@@ -786,6 +786,72 @@ def bgzf_deflate(ctx: Ctx, pieces, lead: int = 0):
             b.free()
 
 
+BGZF_SLOT = 65536
+
+
+def bgzf_deflate_slots(ctx: Ctx, blob: bytes, offs, lens, crcs, before: int = 1, after: int = 1, fill: int = 0xa5):
+    """palace_bgzf_deflate alone, on ranges and CRCs exactly as the caller states them (d_len as it is: nothing is clamped here), into
+    slots pre-filled with `fill` with `before` / `after` spare slots around them.  blob: the text, 4 bytes of room behind it are added (the kernel reads whole dwords).
+    -> (member_len int32[n], every slot as uint8[before + n + after, 65536]); the guard behind member_len must be intact."""
+    lens, offs, crcs = np.ascontiguousarray(lens, np.int32), np.ascontiguousarray(offs, np.int64), np.ascontiguousarray(crcs, np.uint32)
+    n = len(lens)
+    assert n >= 1 and offs.shape == (n,) and crcs.shape == (n,)
+    bufs = [ctx.upload(np.frombuffer(bytes(blob) + bytes(4), np.uint8)), ctx.upload(offs), ctx.upload(lens), ctx.upload(crcs),
+            ctx.upload(np.full((before + n + after) * BGZF_SLOT, fill, np.uint8)), _guarded(ctx, n, np.int32)]
+    d_text, d_off, d_len, d_crc, d_slots, d_mlen = bufs
+    try:
+        _check(lib().palace_bgzf_deflate(ctx.h, d_text.ptr, n, d_off.ptr, d_len.ptr, d_crc.ptr, d_slots.ptr + before * BGZF_SLOT, d_mlen.ptr),
+               "palace_bgzf_deflate")
+        ctx.sync()
+        return _unguard(d_mlen, n, np.int32, "member lengths"), d_slots.to_host().reshape(before + n + after, BGZF_SLOT)
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bgzf_compact_slots(ctx: Ctx, d_slots: DevBuf, member_len, base: int = 0, fill: int = 0x5a, room: int = 64):
+    """palace_bgzf_compact alone on slots the caller filled (d_slots: at least len(member_len) slots, raw bytes): d_file lies `base` bytes
+    into a buffer of `fill` with `room` bytes behind the sum of the lengths.
+    -> (member_off int64[n + 1], the whole buffer as uint8); the guard behind member_off must be intact."""
+    member_len = np.ascontiguousarray(member_len, np.int32)
+    n = len(member_len)
+    total = int(member_len.astype(np.int64).sum())
+    bufs = [ctx.upload(member_len if n else np.zeros(1, np.int32)), ctx.upload(np.full(base + total + room, fill, np.uint8)),
+            _guarded(ctx, n + 1, np.int64)]
+    d_mlen, d_file, d_moff = bufs
+    try:
+        _check(lib().palace_bgzf_compact(ctx.h, d_slots.ptr, n, d_mlen.ptr, d_file.ptr + base, d_moff.ptr), "palace_bgzf_compact")
+        ctx.sync()
+        return _unguard(d_moff, n + 1, np.int64, "member offsets"), d_file.to_host()
+    finally:
+        for b in bufs:
+            b.free()
+
+
+def bgzf_inflate_members(ctx: Ctx, members, sizes):
+    """whole BGZF members (18-byte header, DEFLATE, 8-byte trailer) through palace_bgzf_inflate, member k stated as sizes[k] bytes of text
+    -> (status int32[n], [bytes])"""
+    blob, in_off, out_off, o = bytearray(), [], [], 0
+    for m, k in zip(members, sizes):
+        in_off.append(len(blob) + 18)
+        blob += m
+        out_off.append(o)
+        o += k
+    blob += bytes(8)
+    n = len(members)
+    bufs = [ctx.upload(np.frombuffer(bytes(blob), np.uint8)), ctx.upload(np.array(in_off, np.int64)),
+            ctx.upload(np.array([len(m) - 26 for m in members], np.int32)), ctx.upload(np.array(out_off, np.int64)),
+            ctx.upload(np.array(sizes, np.int32)), ctx.upload(np.zeros(o + 8, np.uint8)), ctx.upload(np.full(n, -1, np.int32))]
+    try:
+        _check(lib().palace_bgzf_inflate(ctx.h, bufs[0].ptr, n, *(b.ptr for b in bufs[1:])), "palace_bgzf_inflate")
+        ctx.sync()
+        st, out = bufs[6].to_host(), bufs[5].to_host().tobytes()
+        return st, [out[a:a + k] for a, k in zip(out_off, sizes)]
+    finally:
+        for b in bufs:
+            b.free()
+
+
 def gzip_inflate(ctx: Ctx, blob: bytes, stride: int = 0, span: int = 0, text_cap: int = 0, check_guards: bool = False):
     """The text of the gzip file `blob` as palace_gzip_inflate hands it over, and the call's counters as a dict.  The text is None
     when the device path declined the file (counters["fallback"] != 0) or the sink did not see the file's last bytes."""

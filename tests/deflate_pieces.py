@@ -11,7 +11,8 @@ def depth_lines(name, positions, depths):
 
 def fibonacci_piece():
     """22 distinct byte values with frequencies 1, 1, 2, 3, ... 17 711 (46 367 bytes, no newline): an unrestricted Huffman tree
-    of it is 21 levels deep"""
+    of the bytes alone is 21 levels deep.  (With the end-of-block code as a third 1, ties let an optimal tree be 12 levels deep:
+    tests/deflate_enc_cases.py has the piece that forces the length limit.)"""
     fib = [1, 1]
     while len(fib) < 22:
         fib.append(fib[-1] + fib[-2])
