@@ -98,7 +98,19 @@ int palace_eref_index_refs(palace_ctx *ctx, const uint8_t *d_bases, const int64_
  * d_keep (optional, 1 B/read) carries the E3 subsampling decision (extract_ref.cpp:955-960).
  * total_bases = d_offsets[n_reads] - d_offsets[0] when the caller knows it (keeps the call
  * asynchronous), or -1 to have it read back.
- * The table is held as three 2^32-bit planes "count >= 1 / >= 2 / >= 3". */
+ * The table is held as three 2^32-bit planes "count >= 1 / >= 2 / >= 3".  What it holds, and what it then accepts
+ * (options: palace_eref_set_option; every other call in a state fails and changes nothing; reset, invalidate and attach always work):
+ *   the table holds   after                                                   accepted
+ *   zero planes       reset; a count of no reads under "probe_all_sets" 2     everything
+ *   three planes      count, merge, plane_unpack into zero planes,            everything
+ *                     table_attach, table_invalidate
+ *   its top plane     a final count ("final_count")                           table_planes, plane_pack / _unpack, popcounts (0, 0, n),
+ *                                                                             both scans
+ *   nothing           a final count that tested every entry set of the        scan_refs_indexed with that index -- under
+ *                     attached index ("probe_all_sets" 1 or 2)                "probe_all_sets" 2 only after entry_hits_complete
+ * A count call with no reads or positions returns OK without looking at the table (under "probe_all_sets" 2 it is the rank's one
+ * count per reset and zeroes the count block).  Hit bits a count launch left in an attached index (palace_eref_attach_probe_index, entry_hits_complete) are used by the
+ * next indexed scan only while nothing has written the planes since: any count, merge, unpack, attach or reset drops them. */
 int palace_eref_table_reset(palace_ctx *ctx);
 /* Optional: allocate the table and the scratch memory a count_reads call over `total_bases` bases will need now (tens of
  * GB at a gigabase; the allocation alone can take from a millisecond to a second), e.g. while the caller is still parsing. */

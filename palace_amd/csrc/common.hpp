@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../../include/palace_hip.h"
+#include "eref_table_state.hpp"
 
 namespace palace {
 
@@ -23,13 +24,14 @@ void set_error(const char *fmt, ...);
         }                                                                                       \
     } while (0)
 
-#define PALACE_REQUIRE(cond, msg)                                  \
+#define PALACE_REQUIRE_AS(name, cond, msg)                         \
     do {                                                           \
         if (!(cond)) {                                             \
-            palace::set_error("%s: %s", __func__, msg);            \
+            palace::set_error("%s: %s", name, msg);                \
             return PALACE_EINVAL;                                  \
         }                                                          \
     } while (0)
+#define PALACE_REQUIRE(cond, msg) PALACE_REQUIRE_AS(__func__, cond, msg)      // (_AS: a helper that speaks for the entry point it serves)
 
 constexpr int kWave = 64;               // CDNA wavefront
 constexpr int kCUs = 256;               // MI355X
@@ -66,22 +68,12 @@ struct palace_ctx {
     palace::CoderMasks masks{};
     uint32_t *plane[3] = {nullptr, nullptr, nullptr};
     bool planes_external = false;
+    palace::TableState table;       // what the planes hold, the fused-hits record, the partial counts' block (eref_table_state.hpp)
     bool want_final = false;        // option final_count: a count into a clean table may keep only the ">= 3" plane
-    bool final_only = false;        // ... and did: planes ">= 1" and ">= 2" are all zero, the table cannot take further counts
-    bool table_clean = false;       // every plane bit is zero (set by reset, cleared by whatever writes the planes)
-    int64_t keys_counted = 0;       // key instances counted into the table since the last reset (an upper bound; -1: unknown -- planes merged or written from outside)
-    // Phase B's channel-0 probe fused into the count launch (palace_eref_attach_probe_index): the attached per-DB index, and the
-    // index whose hit bytes the last count launch left complete (cleared by whatever changes the planes afterwards)
+    // Phase B's channel-0 probe fused into the count launch (palace_eref_attach_probe_index): the attached per-DB index
     const struct palace_eref_probe_index *probe_ix = nullptr;
-    const struct palace_eref_probe_index *c0_hits_ix = nullptr;
-    uint32_t hits_mask = 0;         // ... which of its entry sets' hit bits that launch left (bit 0: channel 0; 0xf: all four, option probe_all_sets)
     int probe_all_sets = 0;         // option: a final count with an attached index tests every entry set and writes no plane (2: leaves partial counts)
-    bool sent_scattered = false;    // ... and that launch carried the sentinels' hits to position order itself
     int64_t scan_ref_lo = 0, scan_ref_hi = 0;   // options scan_ref_lo / _hi: the indexed scan works on refs [lo, hi) (hi = 0: all)
-    const void *counts_ptr = nullptr;   // probe_all_sets 2: the count block (an index's, or the caller's) that holds this context's partial counts of
-                                    // the sample counted since the last reset -- a fused count wrote them, or a call without reads zeroed them
-    bool planeless = false;         // ... and did: the table holds NOTHING (all three planes are zero, as after a reset); Phase B is the attached
-                                    // index's hit bits alone, and whatever else reads the table is refused until the next reset
     int count_mode = 0;             // 0 auto, 1 direct atomics, 2 binned
     int64_t bin_cap_override = 0;
     int64_t slab_override = 0;

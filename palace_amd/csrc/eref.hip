@@ -558,7 +558,7 @@ constexpr int kCountThreads = 256;
 // and the sentinels) are tested here, so nothing reads the ">= 3" plane afterwards -- and the slice is not written: the plane never
 // exists in HBM (0.54 GB of write-back, the 0.5 GB reset of the next step and the probe kernel's 0.5 GB read of it fall away).  Where
 // the overflow path of the partition kernels put bits into the global planes (touched buckets) all three slices are zeroed again:
-// after the launch the table is all zero, as after a reset, and holds nothing (palace_ctx::planeless).
+// after the launch the table is all zero, as after a reset, and holds nothing (TableState::Planes::Nothing).
 constexpr int kProbeSetsMax = 4;
 struct ProbeArgs {
     const unsigned long long *first[kProbeSetsMax];         // [65537] start of every fine bucket's entries of the set (multiples of 8)
@@ -923,6 +923,13 @@ int plan_count(palace_ctx *ctx, int64_t total_bases, CountPlan *pl)
     PALACE_REQUIRE(3ull * static_cast<uint64_t>(slab_bases) / kL1Replicas + (1ull << 20) < (1ull << 32), "slab too large for 32-bit region cursors");
     return PALACE_OK;
 }
+
+// Binned or direct: the positions bound the number of keys; tiny inputs keep the direct path (a 16 Ki-workgroup launch per call
+// would dominate them), everything else is binned -- as is every partial count (option probe_all_sets 2 has no other form of result).
+bool count_is_binned(const palace_ctx *ctx, int64_t positions)
+{
+    return ctx->probe_all_sets == 2 || ctx->count_mode == 2 || (ctx->count_mode == 0 && positions >= (1ll << 22));
+}
 }  // namespace
 
 extern "C" {
@@ -933,8 +940,7 @@ int palace_eref_reserve(palace_ctx *ctx, int64_t total_bases)
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
-    const bool binned = ctx->probe_all_sets == 2 || ctx->count_mode == 2 || (ctx->count_mode == 0 && total_bases >= (1ll << 22));
-    if (!binned) return PALACE_OK;
+    if (!count_is_binned(ctx, total_bases)) return PALACE_OK;
     CountPlan pl;
     rc = plan_count(ctx, total_bases, &pl);
     if (rc) return rc;
@@ -980,14 +986,13 @@ static void carve_count(const CountPlan &pl, char *ws, bool with_words, CountBuf
     b->buf2 = reinterpret_cast<uint16_t *>(ws);
 }
 
-// the final count kernel of a launch with Phase B's channel-0 probe riding along (eref_lds_count_kernel<true, true, true>)
-// (all_sets: eref_lds_count_kernel<true, true, 2> -- every entry set is tested and the ">= 3" plane is not written at all)
-static int probe_index_launch_fused(palace_ctx *ctx, const palace_eref_probe_index *ix, const CountBufs &b, const CountPlan &pl, const KeyBuckets &keys,
-                                    int mode)                  // 0: channel 0; 1: every entry set, hit bits; 2: every entry set, partial counts
+// What the final count kernel needs to have Phase B's probes of `ix` ride along (probe = the kernel's PROBE: 1 channel 0; 2 every
+// entry set, hit bits -- the ">= 3" plane is not written at all; 3 every entry set, partial counts); what the launch will write
+// into is zeroed here (buckets without keys leave their bytes alone)
+static int fused_probe_args(palace_ctx *ctx, const palace_eref_probe_index *ix, int probe, ProbeArgs *out)
 {
-    const bool all_sets = mode >= 1;
-    // (buckets without keys leave their bytes alone)
-    if (mode == 2) {
+    const bool all_sets = probe >= 2, counts = probe == 3;
+    if (counts) {
         PALACE_REQUIRE(ix->ecnt_own[0], "the probe index has no count block (palace_eref_entry_layout / _buffers_attach)");
         PALACE_REQUIRE(ix->canonical, "the probe index's entries are not in position order (a bucket of more than 8192 entries, or no room for the ordering pass): "
                                       "ranks could not add their partial counts entry by entry");
@@ -998,23 +1003,32 @@ static int probe_index_launch_fused(palace_ctx *ctx, const palace_eref_probe_ind
         PALACE_HIP_TRY(hipMemsetAsync(ix->ehits_own[0], 0, all_sets ? ix->entry_hits_bytes : ix->ehits_bytes[0], ctx->stream));
         if (all_sets) PALACE_HIP_TRY(hipMemsetAsync(ix->sent_bytes_own, 0, ix->hit_bytes_size / kSentinelStride, ctx->stream));
     }
-    ProbeArgs pr{};
+    ProbeArgs &pr = *out;
     for (int k = 0; k < kSets; k++) {
         pr.first[k] = ix->first + static_cast<size_t>(k) * (kIndexGroups + 1);
         pr.keys16[k] = ix->keys16[k];
-        pr.ehits[k] = mode == 2 ? ix->ecnt_own[k] : ix->ehits_own[k];
+        pr.ehits[k] = counts ? ix->ecnt_own[k] : ix->ehits_own[k];
     }
     pr.pos_s = ix->pos_s;
     pr.sent_bytes = ix->sent_bytes_own;
-    if (mode == 2)
-        hipLaunchKernelGGL((eref_lds_count_kernel<true, true, 3>), dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2,
-                           ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, pr);
-    else if (all_sets)
-        hipLaunchKernelGGL((eref_lds_count_kernel<true, true, 2>), dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2,
-                           ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, pr);
-    else
-        hipLaunchKernelGGL((eref_lds_count_kernel<true, true, 1>), dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2,
-                           ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, pr);
+    return PALACE_OK;
+}
+
+// The count kernel, one workgroup per fine bucket, by its template parameters: clean (the planes were all zero when the call began),
+// final (implies clean: only the ">= 3" plane is kept), probe (implies final; see fused_probe_args).
+static int launch_lds_count(palace_ctx *ctx, const CountBufs &b, const CountPlan &pl, const KeyBuckets &keys, bool clean, bool final, int probe,
+                            const ProbeArgs &pr)
+{
+#define PALACE_LDS_COUNT(...)                                                                                                                     \
+    hipLaunchKernelGGL((eref_lds_count_kernel<__VA_ARGS__>), dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2, \
+                       ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, pr)
+    if (final && probe == 3) PALACE_LDS_COUNT(true, true, 3);
+    else if (final && probe == 2) PALACE_LDS_COUNT(true, true, 2);
+    else if (final && probe == 1) PALACE_LDS_COUNT(true, true, 1);
+    else if (final) PALACE_LDS_COUNT(true, true);
+    else if (clean) PALACE_LDS_COUNT(true);
+    else PALACE_LDS_COUNT(false);
+#undef PALACE_LDS_COUNT
     PALACE_HIP_TRY(hipGetLastError());
     return PALACE_OK;
 }
@@ -1029,9 +1043,8 @@ static int partial_counts_ready(palace_ctx *ctx)
     if (!ix || !ctx->want_final) { set_error("option probe_all_sets 2 needs option final_count and an attached probe index"); return PALACE_ESTATE; }
     if (!probe_index_usable(ctx, ix)) { set_error("probe_all_sets 2: the attached probe index was built with another coder or holds no entries"); return PALACE_ESTATE; }
     if (!ix->ecnt_own[0]) { set_error("probe_all_sets 2: the probe index has no count block (palace_eref_entry_buffers_attach)"); return PALACE_ESTATE; }
-    const bool whole = (ctx->key_buckets[0] & ctx->key_buckets[1] & ctx->key_buckets[2] & ctx->key_buckets[3]) == ~0u;
-    if (!whole) { set_error("probe_all_sets 2: a share of the reads is counted over the whole key space (palace_eref_set_key_buckets is set)"); return PALACE_ESTATE; }
-    if (!ctx->table_clean || ctx->counts_ptr) { set_error("probe_all_sets 2: one count call per reset (the table is not clean)"); return PALACE_ESTATE; }
+    if (!ctx_buckets(ctx).all()) { set_error("probe_all_sets 2: a share of the reads is counted over the whole key space (palace_eref_set_key_buckets is set)"); return PALACE_ESTATE; }
+    if (!ctx->table.partial_count_allowed()) { set_error("probe_all_sets 2: one count call per reset (the table is not clean)"); return PALACE_ESTATE; }
     return PALACE_OK;
 }
 // ... a rank without reads: its counts are zero
@@ -1040,9 +1053,7 @@ static int partial_counts_zero(palace_ctx *ctx)
     const palace_eref_probe_index *ix = ctx->probe_ix;
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     PALACE_HIP_TRY(hipMemsetAsync(ix->ecnt_own[0], 0, 2 * ix->entry_hits_bytes, ctx->stream));
-    ctx->counts_ptr = ix->ecnt_own[0];
-    ctx->c0_hits_ix = nullptr;
-    ctx->hits_mask = 0;
+    ctx->table.partial_counts_zeroed(ix->ecnt_own[0]);
     return PALACE_OK;
 }
 
@@ -1074,7 +1085,7 @@ static int launch_bin1(palace_ctx *ctx, hipStream_t stream, int ppl, const uint3
 static int bin_and_count(palace_ctx *ctx, const CountPlan &pl, const CountBufs &b, const uint32_t *w0, const uint32_t *w1,
                          const uint32_t *wu, int64_t total_bases, double keys_per_pos)
 {
-    ctx->c0_hits_ix = nullptr;
+    ctx->table.count_started();
     const int64_t kSlabBases = pl.slab_bases_max, n_slabs = pl.n_slabs;
     // positions per lane of the level-1 kernel.  Its throughput is (key slots the CU's LDS holds) / (latency of a tile,
     // ~11 us whatever the tile size): 6 positions x 3 keys x 512 lanes + pads = 39.8 KiB, the most that still fits four
@@ -1090,47 +1101,106 @@ static int bin_and_count(palace_ctx *ctx, const CountPlan &pl, const CountBufs &
     for (int64_t slab = 0; slab < n_slabs; slab++) {
         PALACE_HIP_TRY(hipMemsetAsync(b.cursor2, 0, pl.cur2_bytes + kTouchedBytes, ctx->stream));
         PALACE_HIP_TRY(hipMemsetAsync(b.cursor1, 0, pl.cur1_bytes, ctx->stream));
-        const bool clean = ctx->table_clean && slab == 0;        // every plane bit is still zero: slices need no reading
+        const bool clean = ctx->table.clean() && slab == 0;      // every plane bit is still zero: slices need no reading
         const int64_t s_lo = slab * kSlabBases, s_hi = std::min(total_bases, (slab + 1) * kSlabBases);
-        int rc1 = launch_bin1(ctx, ctx->stream, ppl, w0, w1, wu, s_lo, s_hi, o1);
-        if (rc1) return rc1;
+        int rc = launch_bin1(ctx, ctx->stream, ppl, w0, w1, wu, s_lo, s_hi, o1);
+        if (rc) return rc;
         hipLaunchKernelGGL(eref_bin2_kernel, dim3(g2.first[kL1Buckets]), dim3(kBin2Threads), 0, ctx->stream, b.cursor1, b.buf1, pl.caps1, g2, o2);
         PALACE_HIP_TRY(hipGetLastError());
-        const ProbeArgs no_probe{};
-        if (clean && n_slabs == 1 && ctx->want_final) {
-            const palace_eref_probe_index *ix = ctx->probe_ix;
-            const bool whole = (ctx->key_buckets[0] & ctx->key_buckets[1] & ctx->key_buckets[2] & ctx->key_buckets[3]) == ~0u;
-            if (ix && whole && probe_index_usable(ctx, ix)) {
-                // the final count of a whole key space with a probe index attached: channel 0 of Phase B rides along -- or (option
-                // probe_all_sets) all of Phase B's look-ups, and the ">= 3" plane is never written
-                int rc = probe_index_launch_fused(ctx, ix, b, pl, keys, ctx->probe_all_sets);
-                if (rc) return rc;
-                if (ctx->probe_all_sets == 2) {              // partial counts: nothing to scan from until the ranks' counts are summed
-                    ctx->c0_hits_ix = nullptr;
-                    ctx->hits_mask = 0;
-                    ctx->counts_ptr = ix->ecnt_own[0];
-                } else {
-                    ctx->c0_hits_ix = ix;
-                    ctx->hits_mask = ctx->probe_all_sets ? (1u << kSets) - 1 : 1u;
-                }
-                ctx->sent_scattered = ctx->probe_all_sets == 1;
-                ctx->planeless = ctx->probe_all_sets != 0;
-            } else {
-                if (ctx->probe_all_sets == 2) { set_error("probe_all_sets 2: the count could not be fused with the probe index"); return PALACE_ESTATE; }
-                hipLaunchKernelGGL((eref_lds_count_kernel<true, true>), dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2,
-                                   ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, no_probe);
-            }
-            ctx->final_only = true;
-        } else if (clean)
-            hipLaunchKernelGGL(eref_lds_count_kernel<true>, dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2,
-                               ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, no_probe);
-        else
-            hipLaunchKernelGGL(eref_lds_count_kernel<false>, dim3(kFine), dim3(kCountThreads), 0, ctx->stream, b.cursor2, b.buf2, pl.caps2,
-                               ctx->plane[0], ctx->plane[1], ctx->plane[2], b.touched, keys, no_probe);
-        PALACE_HIP_TRY(hipGetLastError());
-        ctx->table_clean = false;
+        ProbeArgs pr{};
+        if (!(clean && n_slabs == 1 && ctx->want_final)) {
+            rc = launch_lds_count(ctx, b, pl, keys, clean, false, 0, pr);
+            if (rc) return rc;
+            ctx->table.counted_plain();
+            continue;
+        }
+        // the final count.  Over the whole key space with a probe index attached, channel 0 of Phase B rides along -- or (option
+        // probe_all_sets) all of Phase B's look-ups, and the ">= 3" plane is never written
+        const palace_eref_probe_index *ix = ctx->probe_ix;
+        const int probe = ix && keys.all() && probe_index_usable(ctx, ix) ? 1 + ctx->probe_all_sets : 0;
+        if (!probe && ctx->probe_all_sets == 2) { set_error("probe_all_sets 2: the count could not be fused with the probe index"); return PALACE_ESTATE; }
+        if (probe) { rc = fused_probe_args(ctx, ix, probe, &pr); if (rc) return rc; }
+        rc = launch_lds_count(ctx, b, pl, keys, true, true, probe, pr);
+        if (rc) return rc;
+        if (probe == 0) ctx->table.counted_final();
+        else if (probe == 1) ctx->table.counted_final_channel0(ix);
+        else if (probe == 2) ctx->table.counted_final_all_sets(ix);
+        else ctx->table.counted_partial(ix->ecnt_own[0]);        // partial counts: nothing to scan from until the ranks' counts are summed
     }
     return PALACE_OK;
+}
+
+// The count driver.  The reads of one call: ASCII with offsets (palace_eref_count_reads), or the caller's three bit streams, which the
+// partition kernels read where they lie (palace_eref_count_reads_packed).  The two differ in how the number of positions is known,
+// which direct kernel runs and whether the streams are built into the workspace first; everything else is one sequence.
+struct CountInput {
+    const char *entry;                                      // the entry point, as its messages name it
+    bool packed;
+    const uint8_t *bases; const int64_t *offsets; const uint8_t *keep;
+    const uint32_t *p0, *p1, *u;
+    int64_t n_reads;                                        // (packed: a hint, 0 = unknown)
+    int64_t total;                                          // positions (ASCII: -1 = read the two end offsets back)
+};
+
+static int count_reads_from(palace_ctx *ctx, const CountInput &in)
+{
+    if (!ctx->coder_set) { set_error("%s: coder not set", in.entry); return PALACE_ESTATE; }
+    const bool partial = ctx->probe_all_sets == 2;       // the call leaves partial entry counts or fails (partial_counts_ready)
+    if (partial) { int rc0 = partial_counts_ready(ctx); if (rc0) return rc0; }
+    if ((in.packed ? in.total : in.n_reads) == 0) return partial ? partial_counts_zero(ctx) : PALACE_OK;      // (before any state check: eref_table_state.hpp)
+    if (in.packed) {
+        PALACE_REQUIRE_AS(in.entry, in.p0 && in.p1 && in.u, "null device pointer");
+        PALACE_REQUIRE_AS(in.entry, ((reinterpret_cast<uintptr_t>(in.p0) | reinterpret_cast<uintptr_t>(in.p1) | reinterpret_cast<uintptr_t>(in.u)) & 7) == 0,
+                          "the streams must be 8-byte aligned");
+    } else {
+        PALACE_REQUIRE_AS(in.entry, in.bases && in.offsets, "null device pointer");
+    }
+    PALACE_REQUIRE_AS(in.entry, ctx->table.takes_counts(), kTableTopOnly);
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    int rc = ensure_table(ctx);
+    if (rc) return rc;
+    int64_t n = in.total;
+    if (n < 0) {                                            // caller does not know: read the two end offsets back
+        int64_t h_off[2];
+        PALACE_HIP_TRY(hipMemcpyAsync(&h_off[0], in.offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PALACE_HIP_TRY(hipMemcpyAsync(&h_off[1], in.offsets + in.n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
+        PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));
+        n = h_off[1] - h_off[0];
+        PALACE_REQUIRE_AS(in.entry, n >= 0, "offsets not ascending");
+    }
+    ctx->table.keys_added(3 * n);
+    if (!count_is_binned(ctx, n)) {
+        ctx->table.count_started();
+        const int64_t cap = static_cast<int64_t>(kCUs) * 8 * 8;                  // grid-stride beyond 16 Ki blocks
+        if (in.packed)
+            hipLaunchKernelGGL(eref_count_packed_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((n + 255) / 256, cap))), dim3(256), 0, ctx->stream,
+                               in.p0, in.p1, in.u, n, ctx->masks, ctx_buckets(ctx), ctx->plane[0], ctx->plane[1], ctx->plane[2]);
+        else                                                                      // 4 waves (reads) per 256-thread block
+            hipLaunchKernelGGL(eref_count_kernel, dim3(static_cast<unsigned>(std::min<int64_t>((in.n_reads + 3) / 4, cap))), dim3(256), 0, ctx->stream,
+                               in.bases, in.offsets, in.n_reads, in.keep, ctx->masks, ctx_buckets(ctx), ctx->plane[0], ctx->plane[1], ctx->plane[2]);
+        PALACE_HIP_TRY(hipGetLastError());
+        ctx->table.counted_direct();
+        return PALACE_OK;
+    }
+    CountPlan pl;
+    rc = plan_count(ctx, n, &pl);
+    if (rc) return rc;
+    if (partial && pl.n_slabs != 1) { set_error("probe_all_sets 2: the read share does not fit one slab (%lld positions)", static_cast<long long>(n)); return PALACE_ESTATE; }
+    // (packed: palace_eref_packed_bytes covers what plan_count checks the look-ahead of the last tile against: (n >> 5) + 3 words of 4 bytes)
+    rc = ensure_workspace(ctx, pl.total() - (in.packed ? 5 * pl.words_bytes : 0));
+    if (rc) return rc;
+    CountBufs cb;
+    carve_count(pl, static_cast<char *>(ctx->ws.ptr), !in.packed, &cb);
+    const uint32_t *w[3] = {in.p0, in.p1, in.u};          // P0, P1, U
+    if (!in.packed) {                                       // built in the workspace: words = read ends, dropped, P0, P1, U
+        const size_t words = pl.words_bytes / 8;
+        unsigned long long *strm[3];
+        for (int q = 0; q < 3; q++) { strm[q] = cb.words + (2 + q) * words; w[q] = reinterpret_cast<const uint32_t *>(strm[q]); }
+        rc = build_streams(ctx, in.bases, in.offsets, in.n_reads, in.keep, n, cb.words, cb.words + words, strm, pl.words_bytes);
+        if (rc) return rc;
+    }
+    const double keys_per_pos = in.n_reads ? 3.0 * std::max(0.02, 1.0 - 31.0 * static_cast<double>(in.n_reads) / std::max<double>(1.0, static_cast<double>(n))) : 3.0;
+    return bin_and_count(ctx, pl, cb, w[0], w[1], w[2], n, keys_per_pos);
 }
 
 extern "C" {
@@ -1139,56 +1209,7 @@ int palace_eref_count_reads(palace_ctx *ctx, const uint8_t *d_bases, const int64
                             int64_t n_reads, const uint8_t *d_keep, int64_t total_bases)
 {
     PALACE_REQUIRE(ctx && n_reads >= 0, "bad argument");
-    if (!ctx->coder_set) { set_error("palace_eref_count_reads: coder not set"); return PALACE_ESTATE; }
-    const bool partial = ctx->probe_all_sets == 2;       // the call leaves partial entry counts or fails (partial_counts_ready)
-    if (partial) { int rc0 = partial_counts_ready(ctx); if (rc0) return rc0; }
-    if (n_reads == 0) return partial ? partial_counts_zero(ctx) : PALACE_OK;
-    PALACE_REQUIRE(d_bases && d_offsets, "null device pointer");
-    PALACE_REQUIRE(!ctx->final_only, "the table holds only its \">= 3\" plane (option final_count): reset it first");
-    PALACE_HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ensure_table(ctx);
-    if (rc) return rc;
-    // total bases bound the number of keys; tiny inputs keep the direct path (a 16 Ki-workgroup launch
-    // per call would dominate them), everything else is binned
-    if (total_bases < 0) {                                  // caller does not know: read the two end offsets back
-        int64_t h_off[2];
-        PALACE_HIP_TRY(hipMemcpyAsync(&h_off[0], d_offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
-        PALACE_HIP_TRY(hipMemcpyAsync(&h_off[1], d_offsets + n_reads, 8, hipMemcpyDeviceToHost, ctx->stream));
-        PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));
-        total_bases = h_off[1] - h_off[0];
-        PALACE_REQUIRE(total_bases >= 0, "offsets not ascending");
-    }
-    if (ctx->keys_counted >= 0) ctx->keys_counted += 3 * total_bases;
-    const bool binned = partial || ctx->count_mode == 2 || (ctx->count_mode == 0 && total_bases >= (1ll << 22));
-    if (!binned) {
-        int64_t blocks = (n_reads + 3) / 4;                 // 4 waves (reads) per 256-thread block
-        int64_t cap = static_cast<int64_t>(kCUs) * 8 * 8;   // grid-stride beyond 16 Ki blocks
-        if (blocks > cap) blocks = cap;
-        ctx->c0_hits_ix = nullptr;
-        hipLaunchKernelGGL(eref_count_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ctx->stream,
-                           d_bases, d_offsets, n_reads, d_keep, ctx->masks, ctx_buckets(ctx), ctx->plane[0], ctx->plane[1],
-                           ctx->plane[2]);
-        PALACE_HIP_TRY(hipGetLastError());
-        ctx->table_clean = false;
-        return PALACE_OK;
-    }
-    CountPlan pl;
-    rc = plan_count(ctx, total_bases, &pl);
-    if (rc) return rc;
-    if (partial && pl.n_slabs != 1) { set_error("probe_all_sets 2: the read share does not fit one slab (%lld positions)", static_cast<long long>(total_bases)); return PALACE_ESTATE; }
-    const size_t words_bytes = pl.words_bytes;
-    rc = ensure_workspace(ctx, pl.total());
-    if (rc) return rc;
-    CountBufs cb;
-    carve_count(pl, static_cast<char *>(ctx->ws.ptr), true, &cb);
-    unsigned long long *ends = cb.words, *dropped = cb.words + words_bytes / 8;
-    unsigned long long *strm[3];                           // P0, P1, U
-    for (int q = 0; q < 3; q++) strm[q] = cb.words + (2 + q) * (words_bytes / 8);
-    rc = build_streams(ctx, d_bases, d_offsets, n_reads, d_keep, total_bases, ends, dropped, strm, words_bytes);
-    if (rc) return rc;
-    const double keys_per_pos = 3.0 * std::max(0.02, 1.0 - 31.0 * static_cast<double>(n_reads) / std::max<double>(1.0, static_cast<double>(total_bases)));
-    return bin_and_count(ctx, pl, cb, reinterpret_cast<const uint32_t *>(strm[0]), reinterpret_cast<const uint32_t *>(strm[1]),
-                         reinterpret_cast<const uint32_t *>(strm[2]), total_bases, keys_per_pos);
+    return count_reads_from(ctx, CountInput{__func__, false, d_bases, d_offsets, d_keep, nullptr, nullptr, nullptr, n_reads, total_bases});
 }
 
 /* E4, packed input (include/palace_hip.h): the three bit streams come from the caller, the partition kernels read them where
@@ -1220,39 +1241,7 @@ int palace_eref_count_reads_packed(palace_ctx *ctx, const uint32_t *d_p0, const 
                                    int64_t n_positions, int64_t n_reads_hint)
 {
     PALACE_REQUIRE(ctx && n_positions >= 0 && n_reads_hint >= 0, "bad argument");
-    if (!ctx->coder_set) { set_error("palace_eref_count_reads_packed: coder not set"); return PALACE_ESTATE; }
-    const bool partial = ctx->probe_all_sets == 2;       // the call leaves partial entry counts or fails (partial_counts_ready)
-    if (partial) { int rc0 = partial_counts_ready(ctx); if (rc0) return rc0; }
-    if (n_positions == 0) return partial ? partial_counts_zero(ctx) : PALACE_OK;
-    PALACE_REQUIRE(d_p0 && d_p1 && d_u, "null device pointer");
-    PALACE_REQUIRE(((reinterpret_cast<uintptr_t>(d_p0) | reinterpret_cast<uintptr_t>(d_p1) | reinterpret_cast<uintptr_t>(d_u)) & 7) == 0,
-                   "the streams must be 8-byte aligned");
-    PALACE_REQUIRE(!ctx->final_only, "the table holds only its \">= 3\" plane (option final_count): reset it first");
-    PALACE_HIP_TRY(hipSetDevice(ctx->device));
-    int rc = ensure_table(ctx);
-    if (rc) return rc;
-    if (ctx->keys_counted >= 0) ctx->keys_counted += 3 * n_positions;
-    const bool binned = partial || ctx->count_mode == 2 || (ctx->count_mode == 0 && n_positions >= (1ll << 22));
-    if (!binned) {
-        const int64_t blocks = std::min<int64_t>((n_positions + 255) / 256, static_cast<int64_t>(kCUs) * 8 * 8);
-        ctx->c0_hits_ix = nullptr;
-        hipLaunchKernelGGL(eref_count_packed_kernel, dim3(static_cast<unsigned>(blocks)), dim3(256), 0, ctx->stream, d_p0, d_p1, d_u,
-                           n_positions, ctx->masks, ctx_buckets(ctx), ctx->plane[0], ctx->plane[1], ctx->plane[2]);
-        PALACE_HIP_TRY(hipGetLastError());
-        ctx->table_clean = false;
-        return PALACE_OK;
-    }
-    CountPlan pl;
-    rc = plan_count(ctx, n_positions, &pl);
-    if (rc) return rc;
-    if (partial && pl.n_slabs != 1) { set_error("probe_all_sets 2: the read share does not fit one slab (%lld positions)", static_cast<long long>(n_positions)); return PALACE_ESTATE; }
-    // (palace_eref_packed_bytes covers what plan_count checks the look-ahead of the last tile against: (n >> 5) + 3 words of 4 bytes)
-    rc = ensure_workspace(ctx, pl.total() - 5 * pl.words_bytes);
-    if (rc) return rc;
-    CountBufs cb;
-    carve_count(pl, static_cast<char *>(ctx->ws.ptr), false, &cb);
-    const double keys_per_pos = n_reads_hint ? 3.0 * std::max(0.02, 1.0 - 31.0 * static_cast<double>(n_reads_hint) / static_cast<double>(n_positions)) : 3.0;
-    return bin_and_count(ctx, pl, cb, d_p0, d_p1, d_u, n_positions, keys_per_pos);
+    return count_reads_from(ctx, CountInput{__func__, true, nullptr, nullptr, nullptr, d_p0, d_p1, d_u, n_reads_hint, n_positions});
 }
 
 int palace_eref_set_key_buckets(palace_ctx *ctx, const uint32_t mask128[4])

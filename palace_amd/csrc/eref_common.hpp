@@ -271,6 +271,7 @@ __device__ __forceinline__ uint32_t probe_vector(const uint32_t *__restrict__ l3
 // the per-DB probe index (eref_index.hip): entry sets and grouping
 constexpr int kIndexGroups = 1 << 16, kGroupsPerProbe = kIndexGroups / kBuckets;
 constexpr int kSets = 4, kSentinelSet = 3, kSentinelStride = 4;
+static_assert(kAllEntrySets == (1u << kSets) - 1, "the table's fused-hits record names every entry set");
 
 static inline int masks_from_header(const uint8_t *hdr, CoderMasks *out)
 {

@@ -264,7 +264,7 @@ int palace_eref_probe_index_free(palace_ctx *ctx, palace_eref_probe_index *ix)
     if (!ix) return PALACE_OK;
     if (ctx) { (void)hipSetDevice(ctx->device); (void)hipStreamSynchronize(ctx->stream); }
     if (ctx && ctx->probe_ix == ix) ctx->probe_ix = nullptr;
-    if (ctx && ctx->c0_hits_ix == ix) ctx->c0_hits_ix = nullptr;
+    if (ctx) ctx->table.index_gone(ix);
     if (ix->first) (void)hipFree(ix->first);
     for (int k = 0; k < palace::kSets; k++) if (ix->keys16[k]) (void)hipFree(ix->keys16[k]);
     for (int c = 0; c < 3; c++) if (ix->eix[c]) (void)hipFree(ix->eix[c]);
@@ -280,7 +280,7 @@ int palace_eref_attach_probe_index(palace_ctx *ctx, const palace_eref_probe_inde
     PALACE_REQUIRE(ctx, "ctx is null");
     if (ix) PALACE_REQUIRE(std::memcmp(&ix->masks, &ctx->masks, sizeof(CoderMasks)) == 0 && ctx->coder_set, "probe index was built with another coder");
     ctx->probe_ix = ix;
-    if (!ix) ctx->c0_hits_ix = nullptr;
+    if (!ix) ctx->table.index_detached();
     return PALACE_OK;
 }
 
@@ -335,14 +335,14 @@ int palace_eref_entry_buffers_attach(palace_ctx *ctx, palace_eref_probe_index *i
     PALACE_REQUIRE((reinterpret_cast<uintptr_t>(d_counts) | reinterpret_cast<uintptr_t>(d_hits)) % 256 == 0, "buffers must be 256-byte aligned");
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     PALACE_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (ctx->c0_hits_ix == ix) ctx->c0_hits_ix = nullptr;
+    ctx->table.index_gone(ix);
     uint8_t *counts = static_cast<uint8_t *>(d_counts);
     if (!counts) {                                                     // the index's own count block (made on first use: 2 x the hit bits), zero
         if (!ix->counts_block) PALACE_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&ix->counts_block), 2 * ix->entry_hits_bytes));
         counts = ix->counts_block;
         PALACE_HIP_TRY(hipMemsetAsync(counts, 0, 2 * ix->entry_hits_bytes, ctx->stream));
     }
-    ctx->counts_ptr = nullptr;                                         // (whatever this context counted lies in the blocks attached before)
+    ctx->table.count_block_detached();                                 // (whatever this context counted lies in the blocks attached before)
     uint8_t *hits = d_hits ? static_cast<uint8_t *>(d_hits) : ix->hits_block;
     for (int k = 0; k < kSets; k++) { ix->ecnt_own[k] = counts + 2 * ix->set_at[k]; ix->ehits_own[k] = hits + ix->set_at[k]; }
     return PALACE_OK;
@@ -374,20 +374,18 @@ int palace_eref_entry_hits_complete(palace_ctx *ctx, const palace_eref_probe_ind
 {
     PALACE_REQUIRE(ctx && ix, "null argument");
     PALACE_REQUIRE(ctx->probe_ix == ix && ctx->probe_all_sets == 2, "the index is not attached to this context with option probe_all_sets 2");
-    if (!ctx->counts_ptr || ctx->counts_ptr != ix->ecnt_own[0]) {
+    if (!ctx->table.counts_lie_in(ix->ecnt_own[0])) {
         set_error("palace_eref_entry_hits_complete: no count call of this context has left its partial counts in the index's count block since the last reset");
         return PALACE_ESTATE;
     }
-    ctx->c0_hits_ix = ix;
-    ctx->hits_mask = (1u << kSets) - 1;
-    ctx->sent_scattered = false;                                       // (the scan carries the sentinels' hits to position order)
-    ctx->keys_counted = keys_counted;                                  // key instances of ALL ranks (what the scan's pruning goes by); -1: unknown
+    ctx->table.hits_whole(ix, keys_counted);                           // (the scan carries the sentinels' hits to position order; the keys are those
+                                                                       //  of ALL ranks -- what the scan's pruning goes by; -1: unknown)
     return PALACE_OK;
 }
 
 int palace_eref_entry_counts_valid(const palace_ctx *ctx, const palace_eref_probe_index *ix)
 {
-    return ctx && ix && ctx->counts_ptr && ctx->counts_ptr == ix->ecnt_own[0] ? 1 : 0;
+    return ctx && ix && ctx->table.counts_lie_in(ix->ecnt_own[0]) ? 1 : 0;
 }
 
 }  // extern "C"

@@ -697,7 +697,7 @@ int palace_eref_scan_refs(palace_ctx *ctx, const uint8_t *d_bases, const int64_t
 {
     int rc = scan_args_ok(ctx, d_bases, d_offsets, n_refs, total_bases, d_rows);
     if (rc || n_refs == 0) return rc;
-    PALACE_REQUIRE(!ctx->planeless, "the table holds nothing (option probe_all_sets: its last count tested the attached index and wrote no plane): reset it first");
+    PALACE_REQUIRE(ctx->table.planes_readable(), kTableHoldsNothing);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     rc = ensure_table(ctx);
     if (rc) return rc;
@@ -728,8 +728,8 @@ int palace_eref_scan_refs_indexed(palace_ctx *ctx, const palace_eref_probe_index
     if (rc) return rc;
     // channel 0's hit bits: the count launch has left them when this index was attached to it and nothing has touched the planes
     // since; every other entry set (and channel 0 otherwise) is probed now, the plane read once for all of them
-    const uint32_t fused = ctx->c0_hits_ix == ix ? ctx->hits_mask : 0u;      // bit k: set k's hit bits are the count launch's
-    PALACE_REQUIRE(!ctx->planeless || fused == (1u << kSets) - 1,
+    const uint32_t fused = ctx->table.hit_sets_for(ix);                      // bit k: set k's hit bits are the count launch's
+    PALACE_REQUIRE(ctx->table.scannable_through(ix),
                    "the table holds nothing (option probe_all_sets): only the index that rode along in the count can be scanned through; reset the table first");
     size_t eb[kSets];
     for (int k = 0; k < kSets; k++) eb[k] = ((fused >> k) & 1u) ? 0 : ix->ehits_bytes[k];
@@ -737,7 +737,7 @@ int palace_eref_scan_refs_indexed(palace_ctx *ctx, const palace_eref_probe_index
     rc = scan_buffers(ctx, d_offsets, n_refs, total_bases, &b, true, eb);
     if (rc) return rc;
     PALACE_REQUIRE(static_cast<size_t>(b.max_words) * 64 == ix->hit_bytes_size, "probe index was built for another layout of the hit words");
-    const bool sent_done = fused == (1u << kSets) - 1 && ctx->sent_scattered;   // the count launch carried the sentinels' hits to position order as well
+    const bool sent_done = ctx->table.sentinels_placed_for(ix);                 // the count launch carried the sentinels' hits to position order as well
     if (!sent_done) PALACE_HIP_TRY(hipMemsetAsync(b.hit_bytes, 0, static_cast<size_t>(b.max_words) * (64 / kSentinelStride), ctx->stream));
     ProbeSets sets{};
     for (int k = 0; k < kSets; k++) {
@@ -774,7 +774,7 @@ int palace_eref_scan_refs_indexed(palace_ctx *ctx, const palace_eref_probe_index
     // slots, half of all keys at >= 3) chance alone gives that -- every ref would be gathered in full.  So unless the table is known
     // to be sparse (fewer key instances counted since the reset than 0.9 x 2^32: the 1M-contig sample has 2.4 G), channel 0 is
     // gathered first, the exact rule prunes once more, and channels 1 and 2 are gathered for what is left.
-    const bool sparse_table = ctx->keys_counted >= 0 && ctx->keys_counted < static_cast<int64_t>(0.9 * 4294967296.0);
+    const bool sparse_table = ctx->table.known_sparse();
     if (sparse_table) {
         hipLaunchKernelGGL(eref_gather_hits_kernel<0>, tiles, dim3(256), 0, ctx->stream, d_offsets, n_refs, b.tile_pre, b.word_pre, ga, need, active,
                            b.any_w, b.all_w);

@@ -211,22 +211,17 @@ int palace_eref_table_reset(palace_ctx *ctx)
     bool fresh = ctx->plane[0] == nullptr;
     int rc = ensure_table(ctx);
     if (rc) return rc;
-    if (!fresh && !ctx->planeless)                             // (a count that probed every entry set itself left all three planes zero)
-        for (int p = ctx->final_only ? 2 : 0; p < 3; p++)       // (after a final count the two lower planes are zero already)
+    if (!fresh)                                                // (planes a final or plane-less count left zero are skipped)
+        for (int p = ctx->table.first_plane_to_clear(); p < 3; p++)
             PALACE_HIP_TRY(hipMemsetAsync(ctx->plane[p], 0, kPlaneBytes, ctx->stream));
-    ctx->planeless = false;
-    ctx->table_clean = true;
-    ctx->keys_counted = 0;
-    ctx->final_only = false;
-    ctx->c0_hits_ix = nullptr;
-    ctx->counts_ptr = nullptr;
+    ctx->table.reset();
     return PALACE_OK;
 }
 
 int palace_eref_table_planes(palace_ctx *ctx, void **d_planes3, size_t *bytes_per_plane)
 {
     PALACE_REQUIRE(ctx && d_planes3 && bytes_per_plane, "null argument");
-    PALACE_REQUIRE(!ctx->planeless, "the table holds nothing (option probe_all_sets: its last count tested the attached index and wrote no plane): reset it first");
+    PALACE_REQUIRE(ctx->table.planes_readable(), kTableHoldsNothing);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
@@ -247,24 +242,14 @@ int palace_eref_table_attach(palace_ctx *ctx, void *const d_planes3[3])
         ctx->plane[p] = static_cast<uint32_t *>(d_planes3[p]);
     }
     ctx->planes_external = true;
-    ctx->planeless = false;
-    ctx->table_clean = false;                              // caller-owned memory: contents unknown
-    ctx->keys_counted = -1;
-    ctx->final_only = false;
-    ctx->c0_hits_ix = nullptr;
-    ctx->counts_ptr = nullptr;
+    ctx->table.planes_unknown();                           // caller-owned memory: contents unknown
     return PALACE_OK;
 }
 
 int palace_eref_table_invalidate(palace_ctx *ctx)
 {
     PALACE_REQUIRE(ctx, "ctx is null");
-    ctx->table_clean = false;
-    ctx->planeless = false;
-    ctx->keys_counted = -1;
-    ctx->final_only = false;
-    ctx->c0_hits_ix = nullptr;
-    ctx->counts_ptr = nullptr;
+    ctx->table.planes_unknown();
     return PALACE_OK;
 }
 
@@ -273,14 +258,13 @@ static int merge_slices_impl(palace_ctx *ctx, const void *d_parts, int n_parts, 
     PALACE_REQUIRE(ctx && d_parts && n_parts > 0, "bad argument");
     PALACE_REQUIRE(slice_off % 16 == 0 && slice_bytes % 16 == 0 && slice_off + slice_bytes <= kPlaneBytes,
                    "slice must be 16-byte aligned and inside the plane");
-    PALACE_REQUIRE(!ctx->final_only, "the table holds only its \">= 3\" plane (option final_count): reset it first");
+    PALACE_REQUIRE(ctx->table.takes_counts(), kTableTopOnly);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
     size_t n16 = slice_bytes / 16;
     if (n16 == 0) return PALACE_OK;
-    ctx->table_clean = false;
-    ctx->keys_counted = -1;                                // (partial tables of other ranks folded in: how many keys stand behind the planes is not known here)
+    ctx->table.merged();                                   // (drops the fused-hits record like every other write of the planes)
     char *b1 = reinterpret_cast<char *>(ctx->plane[0]) + slice_off;
     char *b2 = reinterpret_cast<char *>(ctx->plane[1]) + slice_off;
     char *b3 = reinterpret_cast<char *>(ctx->plane[2]) + slice_off;
@@ -313,7 +297,7 @@ int palace_eref_table_pack_low(palace_ctx *ctx, void *d_low)
 {
     PALACE_REQUIRE(ctx && d_low, "null argument");
     PALACE_REQUIRE(reinterpret_cast<uintptr_t>(d_low) % 16 == 0, "buffer must be 16-byte aligned");
-    PALACE_REQUIRE(!ctx->final_only, "the table holds only its \">= 3\" plane (option final_count): reset it first");
+    PALACE_REQUIRE(ctx->table.takes_counts(), kTableTopOnly);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
@@ -337,7 +321,7 @@ int palace_eref_plane_pack(palace_ctx *ctx, const uint32_t mask128[4], uint32_t 
                            unsigned long long *d_first)
 {
     PALACE_REQUIRE(ctx && mask128 && d_counts && d_keys && d_first && cap_keys >= 0, "bad argument");
-    PALACE_REQUIRE(!ctx->planeless, "the table holds nothing (option probe_all_sets: its last count tested the attached index and wrote no plane): reset it first");
+    PALACE_REQUIRE(ctx->table.planes_readable(), kTableHoldsNothing);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
@@ -356,7 +340,7 @@ int palace_eref_plane_unpack(palace_ctx *ctx, const uint32_t mask128[4], const u
                              unsigned long long *d_first)
 {
     PALACE_REQUIRE(ctx && mask128 && d_counts && d_keys && d_first && cap_keys >= 0, "bad argument");
-    PALACE_REQUIRE(!ctx->planeless, "the table holds nothing (option probe_all_sets: its last count tested the attached index and wrote no plane): reset it first");
+    PALACE_REQUIRE(ctx->table.planes_readable(), kTableHoldsNothing);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
@@ -367,8 +351,7 @@ int palace_eref_plane_unpack(palace_ctx *ctx, const uint32_t mask128[4], const u
     hipLaunchKernelGGL(plane_sparse_unpack_kernel, dim3(kFine), dim3(256), 0, ctx->stream, ctx->plane[2], kb, d_first, d_keys,
                        static_cast<unsigned long long>(cap_keys));
     PALACE_HIP_TRY(hipGetLastError());
-    ctx->table_clean = false;
-    ctx->c0_hits_ix = nullptr;
+    ctx->table.unpacked_sparse();
     return PALACE_OK;
 }
 
@@ -377,7 +360,7 @@ int palace_eref_table_lookup(palace_ctx *ctx, const uint32_t *d_keys, int64_t n,
     PALACE_REQUIRE(ctx && n >= 0, "bad argument");
     if (n == 0) return PALACE_OK;
     PALACE_REQUIRE(d_keys && d_counts, "null device pointer");
-    PALACE_REQUIRE(!ctx->final_only, "the table holds only its \">= 3\" plane (option final_count): reset it first");
+    PALACE_REQUIRE(ctx->table.takes_counts(), kTableTopOnly);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
@@ -390,7 +373,7 @@ int palace_eref_table_lookup(palace_ctx *ctx, const uint32_t *d_keys, int64_t n,
 int palace_eref_table_popcounts(palace_ctx *ctx, uint64_t out3[3])
 {
     PALACE_REQUIRE(ctx && out3, "null argument");
-    PALACE_REQUIRE(!ctx->planeless, "the table holds nothing (option probe_all_sets: its last count tested the attached index and wrote no plane): reset it first");
+    PALACE_REQUIRE(ctx->table.planes_readable(), kTableHoldsNothing);
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_table(ctx);
     if (rc) return rc;
