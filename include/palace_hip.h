@@ -881,6 +881,42 @@ int palace_path_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palace
                             const int64_t *d_tok_cum, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_hdr,
                             const int64_t *d_hdr_off, const int64_t *d_path_out, int64_t lo, int64_t hi, uint8_t *d_out);
 
+/* ---- the final FASTA: the cycle test of every path, the trim, and the output text (make_final_fa; the rules: DESIGN.md 8) ---- */
+
+/* The fuzzy cycle test.  Tokens are integers: d_node[t] the id of the whole token, d_base[t] >= 0 the id of its base name,
+ * d_len[t] >= 0 its length (n_tok < 2^31 entries each; tokens of equal base have equal lengths -- the caller's promise -- and a
+ * path's lengths sum to less than 2^62).  Path p holds the tokens d_path_off[p] .. d_path_off[p + 1] (n_paths + 1 ascending
+ * entries, the last one n_tok, which is handed in so that the call need not wait for the device).  d_arcs: n_arcs keys
+ * (source node id << 32 | destination node id), ascending, duplicates allowed.  Over all 0 <= i <= j < L of a path of L tokens an
+ * interval [i, j] passes when trimmed = sum len[0 .. i) + sum len(j .. L) <= trim_threshold, the arc path[j] -> path[i] exists,
+ * and the lengths of the DISTINCT bases of path[i .. j] sum to min_cycle_length at least.  d_first[p] / d_last[p] = i / j of the
+ * passing interval of least (trimmed, i, j), both -1 when none passes (a path without tokens, a negative threshold, no arcs).  No
+ * length of a path is compiled in: a workgroup owns a path, its waves take values of i, their lanes values of j; the prefix sums
+ * bound i from above and j from below before an arc is searched.  The previous token of the same base in the path -- the
+ * distinct-base sum of [i, j] adds len[k] where that token lies before i -- comes from a stable palace_sort_u64 of the bases.
+ * Temporaries come from the context's workspace.  Enqueues only. */
+int palace_cycle_trim(palace_ctx *ctx, const int32_t *d_node, const int32_t *d_base, const int64_t *d_len, int64_t n_tok,
+                      const int64_t *d_path_off, int64_t n_paths, const uint64_t *d_arcs, int64_t n_arcs, int64_t trim_threshold,
+                      int64_t min_cycle_length, int32_t *d_first, int32_t *d_last);
+
+/* palace_path_fasta_lengths for the final FASTA.  d_code as palace_path_resolve leaves it, except that a code with
+ * PALACE_PATH_SECOND_TRY set counts as not found like a negative one.  A found token is preceded by sep_len separator bytes iff
+ * the found tokens before it in its path brought at least one byte.  d_tok_cum[0 .. n_tok]: the bytes, separators included, of
+ * all tokens in front of token t (token t's own separator lies at d_tok_cum[t], its record behind it); d_path_len[p]: the
+ * sequence bytes of path p.  Enqueues only. */
+int palace_final_fasta_lengths(palace_ctx *ctx, const palace_fasta_rec *d_recs, const int32_t *d_code, int64_t n_tok, const int64_t *d_path_off,
+                               int64_t n_paths, int64_t sep_len, int64_t *d_tok_cum, int64_t *d_path_len);
+
+/* palace_path_fasta_write for the final FASTA: bytes [lo, hi) of the output text to d_out[0 .. hi - lo), nothing outside them.  A
+ * path with d_path_out[p + 1] == d_path_out[p] has no text at all (no header either): that is a path whose sequence is empty.
+ * Every other path is '>' header LF sequence LF as there, its sequence the tokens' separators (sep_byte) and records as
+ * palace_final_fasta_lengths placed them.  A reversed record is read from its end and complemented by the ambiguous-DNA table in
+ * either case: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W, N and every other byte stay.  A lane writes 16 aligned bytes, the
+ * path of a tile's first and last byte is searched once per tile.  Enqueues only. */
+int palace_final_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const int32_t *d_code,
+                             const int64_t *d_tok_cum, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_hdr,
+                             const int64_t *d_hdr_off, const int64_t *d_path_out, int32_t sep_byte, int64_t lo, int64_t hi, uint8_t *d_out);
+
 /* ---- FASTG -> node FASTA and the `.fai` rows of both, on the device (split_fastg; the rules: DESIGN.md 8) -------------------- */
 
 /* Faults of a FASTG text beyond those of palace_fasta_index, reported in a palace_fasta_status like them */

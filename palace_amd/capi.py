@@ -253,6 +253,11 @@ _SIGS = {
     "palace_fai_rows_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
     "palace_path_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_cycle_trim": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                          C.c_void_p, C.c_void_p],
+    "palace_final_fasta_lengths": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
+    "palace_final_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p],
     "palace_bam_sort_keys": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "palace_sort_u64_scratch_bytes": [C.c_int64],       # (returns size_t: restype set below)
     "palace_sort_u64": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t],
@@ -1645,6 +1650,72 @@ class PathFasta:
 
     def close(self):
         _check(lib().palace_fasta_names_destroy(self.ctx.h, self.names), "palace_fasta_names_destroy")
+
+
+def cycle_trim(ctx: Ctx, node, base, length, path_off, arcs, trim_threshold: int, min_cycle_length: int, guard: int = 8):
+    """palace_cycle_trim on host arrays (arcs: uint64 keys, sorted here as the ABI asks) -> (first, last, the guard entries around both
+    results untouched)"""
+    node, base = np.ascontiguousarray(node, np.int32), np.ascontiguousarray(base, np.int32)
+    length, path_off = np.ascontiguousarray(length, np.int64), np.ascontiguousarray(path_off, np.int64)
+    arcs = np.sort(np.ascontiguousarray(arcs, np.uint64))
+    n_tok, n_paths = len(node), len(path_off) - 1
+    assert len(base) == n_tok and len(length) == n_tok and int(path_off[-1]) == n_tok
+    bufs = [ctx.upload(a) for a in (node, base, length, path_off, arcs)]
+    d_first, d_last = (ctx.upload(np.full(n_paths + 2 * guard, -77, np.int32)) for _ in range(2))
+    try:
+        _check(lib().palace_cycle_trim(ctx.h, bufs[0].ptr, bufs[1].ptr, bufs[2].ptr, n_tok, bufs[3].ptr, n_paths, bufs[4].ptr, len(arcs),
+                                       int(trim_threshold), int(min_cycle_length), d_first.ptr + 4 * guard, d_last.ptr + 4 * guard), "palace_cycle_trim")
+        first, last = d_first.to_host(), d_last.to_host()
+    finally:
+        for b in bufs + [d_first, d_last]:
+            b.free()
+    intact = all(bool((a[:guard] == -77).all() and (a[guard + n_paths:] == -77).all()) for a in (first, last))
+    return first[guard:guard + n_paths], last[guard:guard + n_paths], intact
+
+
+class FinalFasta(PathFasta):
+    """The chain behind make_final_fa's output at the ABI: PathFasta's index, names and resolve, then palace_final_fasta_lengths and
+    palace_final_fasta_write.  Headers are given for the paths that have text only; the others get no byte."""
+
+    def lengths(self, d_code: DevBuf, path_off: np.ndarray, sep_len: int = 50):
+        n_tok, n_paths = int(path_off[-1]), len(path_off) - 1
+        d_path_off = self.ctx.upload(np.asarray(path_off, np.int64))
+        d_cum = self.ctx.empty((n_tok + 1,), np.int64)
+        d_len = self.ctx.empty((max(n_paths, 1),), np.int64)
+        _check(lib().palace_final_fasta_lengths(self.ctx.h, self.d_recs.ptr, d_code.ptr, n_tok, d_path_off.ptr, n_paths, sep_len, d_cum.ptr, d_len.ptr),
+               "palace_final_fasta_lengths")
+        return d_len.to_host()[:n_paths], d_cum, d_path_off
+
+    def writer(self, d_code: DevBuf, d_cum: DevBuf, d_path_off: DevBuf, headers, lens, sep_byte: int = ord("N")):
+        """headers[p]: the header of path p, None for a path without text -> (total bytes of the output text, windows(cuts))"""
+        n_paths = len(headers)
+        hdr_off = np.zeros(n_paths + 1, np.int64)
+        np.cumsum([len(h or b"") for h in headers], out=hdr_off[1:])
+        path_out = np.zeros(n_paths + 1, np.int64)
+        np.cumsum([0 if h is None else len(h) + int(l) + 3 for h, l in zip(headers, lens)], out=path_out[1:])
+        d_hdr = self.ctx.upload(np.frombuffer(b"".join(h or b"" for h in headers), np.uint8))
+        d_hdr_off, d_path_out = self.ctx.upload(hdr_off), self.ctx.upload(path_out)
+        total = int(path_out[-1])
+
+        def windows(cuts, guard: int = 32):
+            """as PathFasta.writer's: the text in the windows the ascending cuts give, every window in a slot of its own between
+            guards -> (the windows' bytes joined, every guard byte untouched)"""
+            bounds = [0] + [int(c) for c in cuts] + [total]
+            slots, at = [], 0
+            for lo, hi in zip(bounds, bounds[1:]):
+                slots.append(at + guard)
+                at += guard + (hi - lo + 15) // 16 * 16 + guard
+            d_out = self.ctx.upload(np.full(max(at, 1), 0xA5, np.uint8))
+            for (lo, hi), slot in zip(zip(bounds, bounds[1:]), slots):
+                _check(lib().palace_final_fasta_write(self.ctx.h, self.d_text.ptr, self.d_recs.ptr, d_code.ptr, d_cum.ptr, d_path_off.ptr, n_paths, d_hdr.ptr,
+                                                      d_hdr_off.ptr, d_path_out.ptr, sep_byte, lo, hi, d_out.ptr + slot), "palace_final_fasta_write")
+            got = d_out.to_host()
+            d_out.free()
+            keep = np.zeros(len(got), bool)
+            for (lo, hi), slot in zip(zip(bounds, bounds[1:]), slots):
+                keep[slot:slot + hi - lo] = True
+            return got[keep].tobytes(), bool((got[~keep] == 0xA5).all())
+        return total, windows
 
 
 FASTG_EPLUS, FASTG_EHIGH, FASTG_ECR, FASTG_ENOLF, FASTG_EEMPTY, FASTG_ENONAME, FASTG_EBASE = range(6, 13)
