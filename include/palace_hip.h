@@ -427,6 +427,20 @@ int palace_bgzf_inflate(palace_ctx *ctx, const uint8_t *d_in, int64_t n_members,
 int palace_bgzf_deflate(palace_ctx *ctx, const uint8_t *d_text, int64_t n_members, const int64_t *d_off, const int32_t *d_len,
                         const uint32_t *d_crc, uint8_t *d_slots, int32_t *d_member_len);
 
+/* The same call for text without lines -- the records of a BAM (`bamsort --lz`, `samview --lz`): the same pieces (0 .. 0xff00 bytes
+ * at any alignment), slots (65536 bytes each, 4-byte aligned), member lengths (28 .. 65311), stored fallback and EOF member, and
+ * palace_bgzf_compact takes its slots as it takes the other call's.  Only the tokens differ; the rule is a function of the piece's n
+ * bytes alone (csrc/deflate_lz.hpp states it, DESIGN.md 8 repeats it): h(p) = the top 14 bits of (the little-endian word of bytes
+ * p .. p + 3) * 2654435761 mod 2^32, for p <= n - 4; the piece is taken in rounds of 512 positions and the candidate of p is the
+ * greatest q with h(q) == h(p) that lies before p's round and at most 32768 back -- never inside p's own round; thread t of 512
+ * parses bytes [t * chunk, (t + 1) * chunk), chunk = ceil(n / 512), greedily from its first byte: the equal bytes at the candidate,
+ * at most 258 and never past the chunk's or the piece's end, are a match from 3 bytes on, a literal below.  Not zlib's bytes: every
+ * member inflates to its piece in zlib and in palace_bgzf_inflate, and the same input always gives the same bytes.  The distances of
+ * the members in flight (131072 bytes for each of min(n_members, 256) workgroups) come from the context's workspace: the call
+ * enqueues only, unless that workspace has to grow, which waits for the stream once. */
+int palace_bgzf_deflate_lz(palace_ctx *ctx, const uint8_t *d_text, int64_t n_members, const int64_t *d_off, const int32_t *d_len,
+                           const uint32_t *d_crc, uint8_t *d_slots, int32_t *d_member_len);
+
 /* The members of such a batch as consecutive file bytes: d_member_off[m] = sum of the lengths in front of member m
  * (n_members + 1 entries, the last = all bytes), member m copied to d_file + d_member_off[m] (room for 65311 bytes per member is
  * always enough).  A batch then leaves the device as one copy of d_member_off[n_members] bytes.  Enqueues only. */

@@ -204,6 +204,7 @@ _SIGS = {
     "palace_fastq_scratch_bytes": [C.c_int64],          # (returns size_t: restype set below)
     "palace_crc32_members": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_bgzf_deflate": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_bgzf_deflate_lz": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_bgzf_compact": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_depth_text_create": [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                  C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)],
@@ -566,6 +567,10 @@ class Ctx:
         _check(lib().palace_bgzf_deflate(self.h, d_text_ptr, n_members, d_off.ptr, d_len.ptr, d_crc.ptr, d_slots.ptr, d_member_len.ptr),
                "palace_bgzf_deflate")
 
+    def bgzf_deflate_lz(self, d_text_ptr: int, n_members: int, d_off: DevBuf, d_len: DevBuf, d_crc: DevBuf, d_slots: DevBuf, d_member_len: DevBuf):
+        _check(lib().palace_bgzf_deflate_lz(self.h, d_text_ptr, n_members, d_off.ptr, d_len.ptr, d_crc.ptr, d_slots.ptr, d_member_len.ptr),
+               "palace_bgzf_deflate_lz")
+
     def bgzf_compact(self, d_slots: DevBuf, n_members: int, d_member_len: DevBuf, d_file: DevBuf, d_member_off: DevBuf):
         _check(lib().palace_bgzf_compact(self.h, d_slots.ptr, n_members, d_member_len.ptr, d_file.ptr, d_member_off.ptr), "palace_bgzf_compact")
 
@@ -769,9 +774,10 @@ def crc32_members(ctx: Ctx, data: bytes, lengths) -> np.ndarray:
             b.free()
 
 
-def bgzf_deflate(ctx: Ctx, pieces, lead: int = 0):
+def bgzf_deflate(ctx: Ctx, pieces, lead: int = 0, lz: bool = False):
     """One BGZF member per piece (bytes, at most 0xff00 each), written on the device: CRC-32, DEFLATE and the compaction to file bytes.
-    -> (file bytes, member offsets with the total as last entry).  lead: bytes in front of the first piece (any alignment)."""
+    -> (file bytes, member offsets with the total as last entry).  lead: bytes in front of the first piece (any alignment).
+    lz: the hashed matcher (palace_bgzf_deflate_lz) in the place of the previous-line one."""
     lens = np.array([len(p) for p in pieces], dtype=np.int32)
     n = len(lens)
     offs = (lead + np.concatenate([[0], np.cumsum(lens, dtype=np.int64)[:-1]])).astype(np.int64) if n else np.zeros(0, np.int64)
@@ -782,7 +788,7 @@ def bgzf_deflate(ctx: Ctx, pieces, lead: int = 0):
     d_text, d_off, d_len, d_crc, d_slots, d_mlen, d_file, d_moff = bufs
     try:
         ctx.crc32_members(d_text.ptr, n, d_off, d_len, d_crc)
-        ctx.bgzf_deflate(d_text.ptr, n, d_off, d_len, d_crc, d_slots, d_mlen)
+        (ctx.bgzf_deflate_lz if lz else ctx.bgzf_deflate)(d_text.ptr, n, d_off, d_len, d_crc, d_slots, d_mlen)
         ctx.bgzf_compact(d_slots, n, d_mlen, d_file, d_moff)
         moff = d_moff.to_host()
         return d_file.to_host()[:int(moff[-1])].tobytes(), moff
@@ -794,8 +800,8 @@ def bgzf_deflate(ctx: Ctx, pieces, lead: int = 0):
 BGZF_SLOT = 65536
 
 
-def bgzf_deflate_slots(ctx: Ctx, blob: bytes, offs, lens, crcs, before: int = 1, after: int = 1, fill: int = 0xa5):
-    """palace_bgzf_deflate alone, on ranges and CRCs exactly as the caller states them (d_len as it is: nothing is clamped here), into
+def bgzf_deflate_slots(ctx: Ctx, blob: bytes, offs, lens, crcs, before: int = 1, after: int = 1, fill: int = 0xa5, lz: bool = False):
+    """palace_bgzf_deflate (lz: palace_bgzf_deflate_lz) alone, on ranges and CRCs exactly as the caller states them (d_len as it is: nothing is clamped here), into
     slots pre-filled with `fill` with `before` / `after` spare slots around them.  blob: the text, 4 bytes of room behind it are added (the kernel reads whole dwords).
     -> (member_len int32[n], every slot as uint8[before + n + after, 65536]); the guard behind member_len must be intact."""
     lens, offs, crcs = np.ascontiguousarray(lens, np.int32), np.ascontiguousarray(offs, np.int64), np.ascontiguousarray(crcs, np.uint32)
@@ -805,8 +811,8 @@ def bgzf_deflate_slots(ctx: Ctx, blob: bytes, offs, lens, crcs, before: int = 1,
             ctx.upload(np.full((before + n + after) * BGZF_SLOT, fill, np.uint8)), _guarded(ctx, n, np.int32)]
     d_text, d_off, d_len, d_crc, d_slots, d_mlen = bufs
     try:
-        _check(lib().palace_bgzf_deflate(ctx.h, d_text.ptr, n, d_off.ptr, d_len.ptr, d_crc.ptr, d_slots.ptr + before * BGZF_SLOT, d_mlen.ptr),
-               "palace_bgzf_deflate")
+        name = "palace_bgzf_deflate_lz" if lz else "palace_bgzf_deflate"
+        _check(getattr(lib(), name)(ctx.h, d_text.ptr, n, d_off.ptr, d_len.ptr, d_crc.ptr, d_slots.ptr + before * BGZF_SLOT, d_mlen.ptr), name)
         ctx.sync()
         return _unguard(d_mlen, n, np.int32, "member lengths"), d_slots.to_host().reshape(before + n + after, BGZF_SLOT)
     finally:

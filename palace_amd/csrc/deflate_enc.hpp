@@ -117,6 +117,13 @@ PALACE_ENC_FN void enc_walk(const EncShared &s, int tid, F &f)
     }
 }
 
+// A walk is the token source of a member: walk(s, tid, f) calls f.literal / f.match for the tokens of thread tid, in text order, and gives
+// the same tokens every time.  The phases below take one; without one they take the lines' (deflate_lz.hpp has the other).
+struct EncLineWalk {
+    template <class F>
+    PALACE_ENC_FN void operator()(const EncShared &s, int tid, F &f) const { enc_walk(s, tid, f); }
+};
+
 struct EncCountFreq {
     EncShared &s;
     PALACE_ENC_FN void literal(uint8_t b) { enc_add(&s.lit_freq[b], 1); }
@@ -207,12 +214,14 @@ PALACE_ENC_FN void enc_phase_clear(EncShared &s, int tid)
     for (int i = tid; i < kEncSegs; i += kEncThreads) s.merge[i] = 0;
 }
 
-PALACE_ENC_FN void enc_phase_freq(EncShared &s, int tid)
+template <class W>
+PALACE_ENC_FN void enc_phase_freq(EncShared &s, int tid, const W &walk)
 {
     EncCountFreq f{s};
-    enc_walk(s, tid, f);
+    walk(s, tid, f);
     if (tid == 0) enc_add(&s.lit_freq[256], 1);
 }
+PALACE_ENC_FN void enc_phase_freq(EncShared &s, int tid) { enc_phase_freq(s, tid, EncLineWalk{}); }
 
 // rank of symbol `sym` among the used symbols by (frequency, symbol)
 PALACE_ENC_FN void enc_rank(const uint32_t *freq, int n_sym, int sym, uint32_t *key, uint16_t *sorted)
@@ -334,12 +343,17 @@ PALACE_ENC_FN void enc_phase_cl_code(EncShared &s, int tid)
     s.seg_off[0] = bits;                                                  // lengths until the scan
 }
 
-PALACE_ENC_FN void enc_phase_bits(EncShared &s, int tid)
+template <class W>
+PALACE_ENC_FN uint32_t enc_token_bits(const EncShared &s, int tid, const W &walk)
 {
     EncCountBits f{s, 0};
-    enc_walk(s, tid, f);
-    s.seg_off[1 + tid] = f.bits;
+    walk(s, tid, f);
+    return f.bits;
 }
+
+template <class W>
+PALACE_ENC_FN void enc_phase_bits(EncShared &s, int tid, const W &walk) { s.seg_off[1 + tid] = enc_token_bits(s, tid, walk); }
+PALACE_ENC_FN void enc_phase_bits(EncShared &s, int tid) { enc_phase_bits(s, tid, EncLineWalk{}); }
 
 // one thread (the device runs a workgroup scan in its place): lengths -> offsets; stored or coded; the member's length
 PALACE_ENC_FN void enc_finish_scan(EncShared &s, uint32_t token_bits_end)
@@ -374,7 +388,8 @@ PALACE_ENC_FN uint8_t enc_stored_byte(const EncShared &s, uint32_t k)     // byt
 }
 
 // slot: the member's 65 536 bytes as dwords
-PALACE_ENC_FN void enc_phase_write(EncShared &s, int tid, uint32_t *slot)
+template <class W>
+PALACE_ENC_FN void enc_phase_write(EncShared &s, int tid, uint32_t *slot, const W &walk)
 {
     if (tid < 4) {
         const uint32_t head[4] = {0x04088b1fu, 0u, 0x0006ff00u, 0x00024342u};  // 1f 8b 08 04 | mtime | xfl 00, os ff, xlen 6 | 'B' 'C' 2 0
@@ -392,7 +407,7 @@ PALACE_ENC_FN void enc_phase_write(EncShared &s, int tid, uint32_t *slot)
     {
         EncBitWriter w(s, out, s.seg_off[1 + tid]);
         EncEmit f{s, w};
-        enc_walk(s, tid, f);
+        walk(s, tid, f);
         w.finish();
     }
     if (tid == 0) {                                                       // BSIZE and the block header
@@ -421,6 +436,7 @@ PALACE_ENC_FN void enc_phase_write(EncShared &s, int tid, uint32_t *slot)
         w.finish();
     }
 }
+PALACE_ENC_FN void enc_phase_write(EncShared &s, int tid, uint32_t *slot) { enc_phase_write(s, tid, slot, EncLineWalk{}); }
 
 // the dwords that were put together in LDS: segment k stores the one it ends in, if it holds that dword's first bit
 PALACE_ENC_FN void enc_phase_merge(EncShared &s, int tid, uint32_t *slot)

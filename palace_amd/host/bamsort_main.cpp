@@ -10,6 +10,7 @@
 // palace_bgzf_deflate, palace_bgzf_compact; bgzf_members_device.hpp), and the .bai computed from the stream that was
 // written (bai.hpp).  The host rewrites the header and lays out the index, nothing else.  The rules are DESIGN.md 8.
 // Needs a device: there is no host path behind it.  On any failure no output file is left.
+//   --lz                             the members come from the coder for text without lines (palace_bgzf_deflate_lz: hashed matches)
 //   -@ <n>                           host threads that inflate the header's members; otherwise ignored
 //   PALACE_DEVICE, PALACE_TRACE      as in the other tools
 //   PALACE_OPT_BAMSORT_BATCH=<n>     members per deflate batch (tests); PALACE_OPT_BAM_BATCH / PALACE_OPT_BAM_CHUNK on the input side
@@ -27,8 +28,9 @@ namespace {
 
 int usage()
 {
-    std::cerr << "Usage: bamsort [-@ <threads>] [-O BAM] -o <out.bam> [--bai] <in.bam>   (coordinate sort; --bai also writes <out.bam>.bai)\n"
-              << "       bamsort --sam [-F <mask>] ... -o <out.bam> [--bai] <in.sam | ->     (the input is SAM text, as samview takes it)\n"
+    std::cerr << "Usage: bamsort [-@ <threads>] [-O BAM] -o <out.bam> [--bai] [--lz] <in.bam>   (coordinate sort; --bai also writes <out.bam>.bai;\n"
+              << "                                                                            --lz: members with hashed matches, smaller files)\n"
+              << "       bamsort --sam [-F <mask>] ... -o <out.bam> [--bai] [--lz] <in.sam | ->     (the input is SAM text, as samview takes it)\n"
               << "       bamsort --index <sorted.bam> [<out.bai>]                       (default <sorted.bam>.bai)\n"
               << "no other option of `samtools sort` / `samtools index` is taken\n";
     return 1;
@@ -88,7 +90,7 @@ void require_whole(const DeviceBamStream &st)
     if (st.n_records > 0x7fffffffll) throw std::runtime_error("more than 2^31 - 1 records");
 }
 
-int main_sort(const std::string &in, const std::string &out, bool bai, int threads, bool sam, uint32_t mask)
+int main_sort(const std::string &in, const std::string &out, bool bai, int threads, bool sam, uint32_t mask, bool lz)
 {
     return with_device("bamsort", [&](palace_ctx *ctx) {
         const bool trace = std::getenv("PALACE_TRACE") != nullptr;
@@ -148,7 +150,7 @@ int main_sort(const std::string &in, const std::string &out, bool bai, int threa
         outputs.f = std::fopen(out.c_str(), "wb");
         if (!outputs.f) throw std::runtime_error("cannot open " + out + " for writing");
         outputs.made.push_back(out);
-        write_bam_file_device(ctx, bamsort_no_room, d_out, out_bytes, bamsort_batch_members(), false, outputs.f, out, clock, laps.write, member_u, member_c, &file_bytes);
+        write_bam_file_device(ctx, bamsort_no_room, d_out, out_bytes, bamsort_batch_members(), false, lz, outputs.f, out, clock, laps.write, member_u, member_c, &file_bytes);
         const int rc_close = std::fclose(outputs.f);
         outputs.f = nullptr;
         if (rc_close != 0) throw std::runtime_error("write failed: " + out);
@@ -214,7 +216,7 @@ int main(int argc, char **argv)
         return main_index(pos[0], pos.size() == 2 ? pos[1] : pos[0] + ".bai", 16);
     }
     std::string in, out, fmt = "BAM";
-    bool bai = false, have_in = false, sam = false, have_mask = false;
+    bool bai = false, have_in = false, sam = false, have_mask = false, lz = false;
     uint32_t mask = 0;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string &s = a[i];
@@ -226,6 +228,7 @@ int main(int argc, char **argv)
         };
         if (s == "--bai") bai = true;
         else if (s == "--sam") sam = true;
+        else if (s == "--lz") lz = true;
         else if (s == "-" && !have_in) { in = s; have_in = true; }
         else if (s.rfind("-F", 0) == 0) {
             std::string v;
@@ -245,5 +248,5 @@ int main(int argc, char **argv)
     }
     if (!have_in || out.empty() || (!sam && (have_mask || in == "-"))) return usage();
     if (fmt != "BAM" && fmt != "bam") { std::cerr << "bamsort: -O " << fmt << ": only BAM is written\n"; return 1; }
-    return main_sort(in, out, bai, std::min(threads, 64), sam, mask);
+    return main_sort(in, out, bai, std::min(threads, 64), sam, mask, lz);
 }

@@ -2,8 +2,9 @@
 // kBgzfText = 0xff00 bytes of text, the last one shorter, a batch at a time -- palace_crc32_members for the trailers,
 // palace_bgzf_deflate and palace_bgzf_compact for the members, one copy back per batch, fwrite.  A batch's text is either a piece of a
 // resident stream or what a callback writes into the batch's buffer (the depth file: palace_depth_text_emit).  `stored` (samview -u):
-// the members hold stored blocks (DEFLATE BTYPE 00); the device still supplies every CRC, the host only frames the bytes.  The EOF
-// member is the caller's.
+// the members hold stored blocks (DEFLATE BTYPE 00); the device still supplies every CRC, the host only frames the bytes.  `lz`
+// (bamsort --lz, samview --lz): the members come from palace_bgzf_deflate_lz, the coder for text without lines.  The EOF member is the
+// caller's.
 #pragma once
 #include <cstdio>
 #include <functional>
@@ -53,7 +54,7 @@ using MemberFill = std::function<void(uint64_t t_beg, uint64_t t_end, uint8_t *d
 // `bytes` bytes of text to f, members of at most `batch_cap` per batch.  member_off gets every member's file offset, file_bytes grows by
 // the bytes written (it is the file offset of the first member on entry).  no_room, write_failed: the caller's messages.
 inline void write_members_device(palace_ctx *ctx, NoRoomText no_room, const uint8_t *d_stream, const MemberFill &fill, uint64_t bytes, size_t batch_cap, bool stored,
-                                 FILE *f, const std::string &write_failed, StageClock &clock, MemberWriteTimes &tm, std::vector<uint64_t> &member_off,
+                                 bool lz, FILE *f, const std::string &write_failed, StageClock &clock, MemberWriteTimes &tm, std::vector<uint64_t> &member_off,
                                  uint64_t &file_bytes)
 {
     const size_t n_members = bgzf_member_count(bytes), batch = bgzf_batch_members(n_members, batch_cap);
@@ -97,7 +98,8 @@ inline void write_members_device(palace_ctx *ctx, NoRoomText no_room, const uint
             bytes_at = framed.data();
             n_bytes = framed.size();
         } else {
-            ck(palace_bgzf_deflate(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc, d_slots, d_mlen), "palace_bgzf_deflate");
+            if (lz) ck(palace_bgzf_deflate_lz(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc, d_slots, d_mlen), "palace_bgzf_deflate_lz");
+            else ck(palace_bgzf_deflate(ctx, d_text, static_cast<int64_t>(nm), d_off, d_len, d_crc, d_slots, d_mlen), "palace_bgzf_deflate");
             ck(palace_bgzf_compact(ctx, d_slots, static_cast<int64_t>(nm), d_mlen, d_file, d_moff), "palace_bgzf_compact");
             clock.lap(&tm.deflate, true);
             ck(palace_d2h(ctx, moff.data(), d_moff, (nm + 1) * 8), "palace_d2h");
@@ -126,13 +128,13 @@ struct OutputFiles {
 // A BAM stream d_out[0 .. out_bytes) to f as a whole BGZF file (`bamsort`, `samview`): the members, then the 28-byte EOF member; f is left
 // open.  member_u / member_c get every member's stream and file offset, the EOF member's last (it stands for the stream's end);
 // *file_bytes the bytes written.
-inline void write_bam_file_device(palace_ctx *ctx, NoRoomText no_room, const uint8_t *d_out, int64_t out_bytes, size_t batch_cap, bool stored, FILE *f,
+inline void write_bam_file_device(palace_ctx *ctx, NoRoomText no_room, const uint8_t *d_out, int64_t out_bytes, size_t batch_cap, bool stored, bool lz, FILE *f,
                                   const std::string &out, StageClock &clock, MemberWriteTimes &tm, std::vector<int64_t> &member_u, std::vector<int64_t> &member_c,
                                   uint64_t *file_bytes)
 {
     std::vector<uint64_t> member_off;
     *file_bytes = 0;
-    write_members_device(ctx, no_room, d_out, {}, static_cast<uint64_t>(out_bytes), batch_cap, stored, f, "write failed: " + out, clock, tm, member_off, *file_bytes);
+    write_members_device(ctx, no_room, d_out, {}, static_cast<uint64_t>(out_bytes), batch_cap, stored, lz, f, "write failed: " + out, clock, tm, member_off, *file_bytes);
     for (size_t k = 0; k < member_off.size(); k++) {
         member_u.push_back(static_cast<int64_t>(k * kBgzfText));
         member_c.push_back(static_cast<int64_t>(member_off[k]));

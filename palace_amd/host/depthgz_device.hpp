@@ -55,7 +55,7 @@ inline DepthGzResult write_depth_gz_device(palace_ctx *ctx, int64_t n_segs, cons
     BgzfTextWriter w(gz_path, 6, 1);
     write_members_device(ctx, no_room_plain, nullptr,
                          [&](uint64_t t_beg, uint64_t t_end, uint8_t *d_text) { ck(palace_depth_text_emit(ctx, dt.h, t_beg, t_end, d_text), "palace_depth_text_emit"); },
-                         text_bytes, depthgz_batch_members(), false, w.f, "write failed", clock, tm.members, w.member_off, w.file_bytes);
+                         text_bytes, depthgz_batch_members(), false, false, w.f, "write failed", clock, tm.members, w.member_off, w.file_bytes);
     w.text_bytes = text_bytes;
     w.close();                                                             // (nothing pending: the EOF member)
     res.text_bytes = w.text_bytes; res.file_bytes = w.file_bytes;

@@ -3,7 +3,7 @@
 // as  bwa mem ... | samview -@ "$threads" -F 0x0800 -buS - > tmp.bam        (the argument list as the driver has it)
 // The SAM text goes up once; its lines are found, validated, filtered and encoded as BAM records on the device (sam_device.hpp,
 // csrc/sam.hip), the stream is cut into members of 0xff00 bytes -- stored ones with -u, the host framing what the device has summed;
-// the device coder's otherwise (bgzf_members_device.hpp) -- and the EOF member ends the file.  The host parses the header and the
+// the device coder's otherwise (bgzf_members_device.hpp; --lz: the coder for text without lines, palace_bgzf_deflate_lz) -- and the EOF member ends the file.  The host parses the header and the
 // command line, nothing else.  The rules are DESIGN.md 8; htslib is not at hand, so parity with samtools is UNPINNED.
 // Needs a device: there is no host path behind it.  On any failure no output file is left and nothing has gone to stdout.
 //   PALACE_DEVICE, PALACE_TRACE      as in the other tools
@@ -20,8 +20,9 @@ namespace {
 
 int usage()
 {
-    std::cerr << "Usage: samview [-@ <threads>] [-F <mask>] -b [-u] [-S] [-h] [-o <out.bam>] <in.sam | ->\n"
+    std::cerr << "Usage: samview [-@ <threads>] [-F <mask>] -b [-u | --lz] [-S] [-h] [-o <out.bam>] <in.sam | ->\n"
               << "  SAM text to BAM; -F: drop the lines whose FLAG has a bit of <mask> (decimal or 0x hex); -u: stored (uncompressed) members;\n"
+              << "  --lz: members with hashed matches (smaller files; not with -u);\n"
               << "  -b is required (only BAM is written); -S, -h and -@ are accepted and ignored; short flags may be clustered (-buS);\n"
               << "  output goes to -o or stdout.  Tags of type f and B:f are refused (no text-to-float on the device; bwa writes none).\n"
               << "  no other option of `samtools view` is taken; parity with samtools is unpinned (DESIGN.md 8)\n";
@@ -34,7 +35,7 @@ int main(int argc, char **argv)
 {
     std::vector<std::string> a(argv + 1, argv + argc);
     std::string in, out;
-    bool have_in = false, bam = false, stored = false;
+    bool have_in = false, bam = false, stored = false, lz = false;
     uint32_t mask = 0;
     for (size_t i = 0; i < a.size(); i++) {
         const std::string &s = a[i];
@@ -43,6 +44,7 @@ int main(int argc, char **argv)
             in = s; have_in = true;
             continue;
         }
+        if (s == "--lz") { lz = true; continue; }
         for (size_t k = 1; k < s.size(); k++) {
             const char c = s[k];
             if (c == 'b') bam = true;
@@ -60,7 +62,7 @@ int main(int argc, char **argv)
             } else return usage();
         }
     }
-    if (!have_in || in.empty()) return usage();
+    if (!have_in || in.empty() || (lz && stored)) return usage();
     if (!bam) { std::cerr << "samview: only BAM is written: -b is required\n"; return 1; }
 
     return with_device("samview", [&](palace_ctx *ctx) {
@@ -78,7 +80,7 @@ int main(int argc, char **argv)
         if (!out.empty()) outputs.made.push_back(out);
         std::vector<int64_t> member_u, member_c;
         uint64_t file_bytes = 0;
-        write_bam_file_device(ctx, bamsort_no_room, st.d_stream, st.total, 8192, stored, f, out_name, clock, wt, member_u, member_c, &file_bytes);
+        write_bam_file_device(ctx, bamsort_no_room, st.d_stream, st.total, 8192, stored, lz, f, out_name, clock, wt, member_u, member_c, &file_bytes);
         const int rc_close = out.empty() ? std::fflush(f) : std::fclose(f);
         outputs.f = nullptr;
         if (rc_close != 0) throw std::runtime_error("write failed: " + out_name);

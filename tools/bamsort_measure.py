@@ -1,5 +1,5 @@
-"""profiles/bamsort.md: traced runs of `bamsort --bai` on the e2e leg's 1M-contig BAM with its records permuted (fixed seed), and
-palace_sort_u64 alone at that many 53-bit keys.
+"""profiles/bamsort.md: traced runs of `bamsort --bai` on the e2e leg's 1M-contig BAM with its records permuted (fixed seed), without and
+with `--lz` in turns, and palace_sort_u64 alone at that many 53-bit keys.
     python tools/bamsort_measure.py [<log file> [<contigs>]]        (default tools/out/bamsort_measure.log, 1 000 000 contigs)"""
 import os
 import subprocess
@@ -53,20 +53,28 @@ with open(os.path.join(P["cols"], "targets.tsv"), "w") as f:
     f.write("".join(f"{nm}\t{l}\n" for nm, l in zip(gs["names"], gs["lens"].tolist())))
 subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "synthbam"), P["cols"], P["bam"], "16", "1"], check=True)
 say(f"input: {n} records, {n_contigs} targets, {os.path.getsize(P['bam'])} B (zlib level 1, records permuted with seed 12345)")
-sorted_bam = os.path.join(work, "first.bam")
-for rep in range(2):                      # the first run also pays the code objects' load; both are printed
-    t0 = time.perf_counter()
-    r = subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "bamsort"), "-@", "16", P["bam"], "-O", "BAM", "-o", sorted_bam, "--bai"],
-                       env=dict(os.environ, PALACE_TRACE="1"), stderr=subprocess.PIPE, timeout=300)
-    say(f"run {rep}: exit {r.returncode}, wall {time.perf_counter() - t0:.3f} s")
-    say(r.stderr.decode())
-    if r.returncode:
-        sys.exit(1)
+sorted_bam, lz_bam = os.path.join(work, "first.bam"), os.path.join(work, "first_lz.bam")
+# the two coders in turns in one call: the unflagged run is the yardstick of the --lz run next to it.  The first run also pays the
+# code objects' load; every run is printed
+for rep in range(3):
+    for flags, dst in (([], sorted_bam), (["--lz"], lz_bam)):
+        t0 = time.perf_counter()
+        r = subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "bamsort"), "-@", "16"] + flags + [P["bam"], "-O", "BAM", "-o", dst, "--bai"],
+                           env=dict(os.environ, PALACE_TRACE="1"), stderr=subprocess.PIPE, timeout=300)
+        say(f"run {rep}{' --lz' if flags else ''}: exit {r.returncode}, wall {time.perf_counter() - t0:.3f} s, output {os.path.getsize(dst) if r.returncode == 0 else 0} B")
+        say(r.stderr.decode())
+        if r.returncode:
+            sys.exit(1)
+r = subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "bamsort"), "--index", lz_bam, os.path.join(work, "again_lz.bai")], stderr=subprocess.PIPE, timeout=300)
+say(f"--lz: --index exit {r.returncode}; same bytes as --bai: {open(os.path.join(work, 'again_lz.bai'), 'rb').read() == open(lz_bam + '.bai', 'rb').read()}")
 say(f"output: {os.path.getsize(sorted_bam)} B, .bai {os.path.getsize(sorted_bam + '.bai')} B")
 r = subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "bamsort"), "--index", sorted_bam, os.path.join(work, "again.bai")], stderr=subprocess.PIPE, timeout=300)
 say(f"--index exit {r.returncode}; same bytes as --bai: {open(os.path.join(work, 'again.bai'), 'rb').read() == open(sorted_bam + '.bai', 'rb').read()}")
 r = subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "bamsort"), "-o", os.path.join(work, "again.bam"), sorted_bam], stderr=subprocess.PIPE, timeout=300)
 say(f"sorting the output again: exit {r.returncode}; same file: {open(os.path.join(work, 'again.bam'), 'rb').read() == open(sorted_bam, 'rb').read()}")
+r = subprocess.run([os.path.join(ROOT, "palace_amd", "bin", "bamsort"), "-o", os.path.join(work, "again.bam"), lz_bam], stderr=subprocess.PIPE, timeout=300)
+say(f"sorting the --lz output without the flag: exit {r.returncode}; the unflagged run's file (so the same stream): "
+    f"{open(os.path.join(work, 'again.bam'), 'rb').read() == open(sorted_bam, 'rb').read()}")
 
 # the sort alone: n keys of 53 bits, as the tool's (20 bits of refID + 33)
 keys = rng.integers(0, 1 << 53, n, dtype=np.uint64)
