@@ -9,7 +9,6 @@
 namespace palace {
 namespace {
 
-inline size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 // small[0] = records a .bai cannot hold, [1] = the first of them, [2] = the first record out of order, [3] = records without a contig
 __global__ __launch_bounds__(256) void bai_records_kernel(const uint8_t *stream, const int64_t *starts, int64_t n, int32_t n_ref, int32_t *ref, int32_t *bin,

@@ -24,7 +24,6 @@ constexpr int kWaveKeys = kSortTile / kSortWaves, kRounds = kWaveKeys / kWave;
 static_assert(kSortThreads == 256, "one lane per digit combines the waves' counts");
 static_assert(kRounds * kWave * kSortWaves == kSortTile, "a tile is whole rounds of whole waves");
 
-inline size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 // small[0] = records without a key, small[1] = the smallest ordinal among them
 __global__ __launch_bounds__(256) void sort_keys_kernel(const uint8_t *stream, int64_t total, const int64_t *starts, int64_t n, int32_t n_ref,

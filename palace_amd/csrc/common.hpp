@@ -44,6 +44,9 @@ struct CoderMasks {
     uint32_t m[3][3];
 };
 
+// the parts of a scratch buffer begin on multiples of 256 bytes
+inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
+
 struct Workspace {
     void *ptr = nullptr;
     size_t bytes = 0;

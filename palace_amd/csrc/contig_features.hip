@@ -75,28 +75,6 @@ struct ValueAt {
     __device__ __forceinline__ long long operator()(int64_t c) const { return v[c]; }
 };
 
-template <class Size>
-__global__ __launch_bounds__(kScanThreads) void contig_scan_kernel(Size size, int64_t n, int64_t *cum, long long *block_sum)
-{
-    __shared__ long long s_scan[kScanThreads / 64 + 1];
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kScanThreads + threadIdx.x;
-    const long long v = i < n ? size(i) : 0;
-    long long total;
-    const long long ex = block_exclusive<long long, kScanThreads>(v, s_scan, &total);
-    if (i < n) cum[i] = ex;
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-// cum[0 .. n]: the exclusive prefix sums of size(0 .. n) and their total (n > 0)
-template <class Size>
-void scan_into(palace_ctx *ctx, Size size, int64_t n, int64_t *cum, long long *sums)
-{
-    const int64_t nb = (n + kScanThreads - 1) / kScanThreads;
-    hipLaunchKernelGGL(contig_scan_kernel<Size>, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, size, n, cum, sums);
-    hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
-    hipLaunchKernelGGL(add_block_base_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n, cum, sums, nb);
-}
-
 // ---- a lane's 16 positions of S ----------------------------------------------------------------------------------------------
 
 // 0..3 for A C G T in either case, 4 for a digit, 5 for every other byte
@@ -320,10 +298,10 @@ extern "C" int palace_contig_features(palace_ctx *ctx, const uint8_t *d_text, in
     const palace_fasta_rec *recs = d_recs + r0;
     const dim3 chunks(static_cast<unsigned>(s.nc)), records(static_cast<unsigned>(n_rec)), threads(kThreads);
 
-    scan_into(ctx, ChunksOf{recs}, n_rec, s.chunk_cum, s.sums);
+    scan_sizes_into(ctx, ChunksOf{recs}, n_rec, s.chunk_cum, s.sums);
     hipLaunchKernelGGL(contig_classify_kernel, chunks, threads, 0, ctx->stream, d_text, n, recs, n_rec, s.chunk_cum, s.kept_cum,
                        reinterpret_cast<unsigned long long *>(d_bad));
-    scan_into(ctx, ValueAt{s.kept_cum}, s.nc, s.kept_cum, s.sums);
+    scan_sizes_into(ctx, ValueAt{s.kept_cum}, s.nc, s.kept_cum, s.sums);
     hipLaunchKernelGGL(contig_scatter_kernel, chunks, threads, 0, ctx->stream, d_text, n, recs, n_rec, s.chunk_cum, s.kept_cum, s.codes);
     hipLaunchKernelGGL(contig_rows_begin_kernel, records, threads, 0, ctx->stream, recs, s.chunk_cum, s.kept_cum, d_feat, d_fsum, d_info);
     hipLaunchKernelGGL(contig_count_kernel, chunks, threads, 0, ctx->stream, recs, n_rec, s.chunk_cum, s.kept_cum, s.codes, d_feat, d_fsum);

@@ -40,7 +40,6 @@ struct TileBase { int64_t line0, run0, name0; int32_t last_eff, pad; };
 struct ScratchHead { int32_t skip, tail_buf, tail_len, name0_len; int32_t pad[12]; };
 
 inline size_t tiles_of(int64_t n) { return static_cast<size_t>((n + kTileBytes - 1) / kTileBytes); }
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 
 // the file's text around the window: byte i of the window for i >= 0, the carried tail at -tail_len .. -1
 struct Text {

@@ -8,21 +8,18 @@
 //           records -- knowing its record from one search per tile and one per lane.  A fault is kept as the smallest OFFSET
 //           per code; the lines of those offsets are counted afterwards (only a text at fault pays for that), so the verdict
 //           does not depend on tiling.
-//   plan:   a 64-bit scan of the kept records' output sizes (a dropped record has none).
-//   write:  a lane makes 16 aligned bytes of any window [lo, hi) of the output; the records of a tile's first and last byte are
-//           searched once per tile; 16 bytes that are neighbours in one source line are one load and one store, a primed
-//           record is read from its end through the upper-casing complement.
+//   plan:   a 64-bit scan of the kept records' output sizes (a dropped record has none; scan64.hpp).
+//   write:  any window [lo, hi) of the output, by the lanes, the gather and the upper-casing complement of window_lanes.hpp: the
+//           items are the kept records, a primed record is read from its end.
 //   rows:   length pass, scan, write of the five-column index rows, one lane per row.
 #include "common.hpp"
-#include "scan64.hpp"
-#include "text_lanes.hpp"
+#include "window_lanes.hpp"
 
 #include <climits>
 
 namespace palace {
 namespace {
 
-constexpr int kTileThreads = 256, kTileBytes = kTileThreads * kLaneBytes;
 constexpr int kCodes = 16;                       // fault codes are below this
 // ctx->d_small, in 64-bit words: the smallest offset per fault code, the line ends in front of each, and the plan's two words
 constexpr int kOffAt = 0, kLinesAt = kCodes, kFirstEmptyAt = 2 * kCodes, kKeptAt = 2 * kCodes + 1;
@@ -177,32 +174,6 @@ struct RowSize {
     }
 };
 
-template <class Size>
-__global__ __launch_bounds__(kScanThreads) void size_scan_kernel(Size size, int64_t n, int64_t *cum, long long *block_sum)
-{
-    __shared__ long long s_scan[kScanThreads / 64 + 1];
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kScanThreads + threadIdx.x;
-    const long long v = i < n ? size(i) : 0;
-    long long total;
-    const long long ex = block_exclusive<long long, kScanThreads>(v, s_scan, &total);
-    if (i < n) cum[i] = ex;
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-// cum[0 .. n]: the exclusive prefix sums of size(0 .. n) and their total (n > 0)
-template <class Size>
-int scan_sizes(palace_ctx *ctx, Size size, int64_t n, int64_t *cum)
-{
-    const int64_t nb = (n + kScanThreads - 1) / kScanThreads;
-    const int rc = ensure_workspace(ctx, static_cast<size_t>(nb + 1) * sizeof(long long));
-    if (rc) return rc;
-    long long *sums = static_cast<long long *>(ctx->ws.ptr);
-    hipLaunchKernelGGL(size_scan_kernel<Size>, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, size, n, cum, sums);
-    hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
-    hipLaunchKernelGGL(add_block_base_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n, cum, sums, nb);
-    return PALACE_OK;
-}
-
 __global__ __launch_bounds__(256) void first_empty_kernel(const palace_fasta_rec *recs, int64_t n_records, unsigned long long *small)
 {
     const int64_t r = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
@@ -226,81 +197,33 @@ __global__ __launch_bounds__(256) void out_recs_kernel(const palace_fasta_rec *r
 
 // ---- the writer -------------------------------------------------------------------------------------------------------------------
 
-// the other strand's base in upper case: A<->T, C<->G in either case (a primed record holds nothing else)
-__device__ __forceinline__ uint32_t complement_upper(uint32_t b)
-{
-    const uint32_t u = b & 0xdfu;
-    return is_base(b) ? u ^ ((u == 'A' || u == 'T') ? 0x15u : 0x04u) : b;
-}
-__device__ __forceinline__ uint32_t complement_upper4(uint32_t w)
-{
-    return complement_upper(w & 0xffu) | (complement_upper((w >> 8) & 0xffu) << 8) | (complement_upper((w >> 16) & 0xffu) << 16) |
-           (complement_upper(w >> 24) << 24);
-}
-
+// the items are the records; a primed one is read from its end through the upper-casing complement (window_lanes.hpp)
 __global__ __launch_bounds__(kTileThreads) void fastg_write_kernel(const uint8_t *text, const palace_fasta_rec *recs, const uint8_t *primed,
                                                                    const int64_t *out_off, int64_t n_records, int64_t lo, int64_t hi, uint8_t *out)
 {
     __shared__ long long s_rec[2];
-    const int64_t tile0 = static_cast<int64_t>(blockIdx.x) * kTileBytes;
-    if (threadIdx.x < 2) {                                                   // the records of the tile's first and last byte
-        const int64_t end = lo + tile0 + kTileBytes < hi ? lo + tile0 + kTileBytes : hi;
-        s_rec[threadIdx.x] = last_le(out_off, 0, n_records - 1, threadIdx.x == 0 ? lo + tile0 : end - 1);
-    }
-    __syncthreads();
-    const int64_t j0 = tile0 + threadIdx.x * kLaneBytes, o0 = lo + j0;
-    if (o0 >= hi) return;
-    const int cnt = hi - o0 < kLaneBytes ? static_cast<int>(hi - o0) : kLaneBytes;
-    int64_t r = last_le(out_off, s_rec[0], s_rec[1], o0);                    // (behind dropped records it is the last of equal entries: the kept one)
-    uint64_t acc_lo = 0, acc_hi = 0;
-    int k = 0;
-    auto put = [&](uint32_t b) {
-        if (k < 8) acc_lo |= static_cast<uint64_t>(b) << (8 * k); else acc_hi |= static_cast<uint64_t>(b) << (8 * (k - 8));
-        k++;
-    };
-    while (k < cnt && r < n_records) {
-        const palace_fasta_rec rec = recs[r];
-        const bool rev = primed[r] != 0;
+    LaneOut l;
+    int64_t r = window_lane(out_off, n_records, lo, hi, s_rec, &l);          // (behind dropped records it is the kept one)
+    if (r < 0) return;
+    while (!l.full() && r < n_records) {
+        palace_fasta_rec rec = recs[r];
+        if (rec.line_bases <= 0) rec.line_bases = 1;                         // (an indexed record with bases has a first line)
         const int64_t h = rec.name_len, len = rec.length;
-        int64_t x = o0 + k - out_off[r];                                     // the byte's place in the record's text
-        for (; k < cnt && x < h + 2; x++) put(x == 0 ? '>' : x == h + 1 ? '\n' : text[rec.name_off + x - 1]);
-        if (k >= cnt) break;
+        int64_t x = l.o0 + l.k - out_off[r];                                 // the byte's place in the record's text
+        put_header(l, text + rec.name_off, h, x);
+        if (l.full()) break;
         const int64_t q = x - (h + 2);                                       // ... in its sequence
         if (q < len) {
             const int64_t left = len - q;
-            const int m = left < cnt - k ? static_cast<int>(left) : cnt - k;
-            const int64_t pos = rev ? len - 1 - q : q;
-            const int64_t line_bases = rec.line_bases > 0 ? rec.line_bases : 1;        // (an indexed record with bases has a first line)
-            const int64_t row = pos / line_bases;
-            int64_t col = pos - row * line_bases, src = rec.seq_off + row * rec.line_width + col;
-            if (m == kLaneBytes && (rev ? col >= kLaneBytes - 1 : col + kLaneBytes <= line_bases)) {
-                // the lane's 16 bytes are 16 neighbours of one line: one load, one store
-                uint4 v;
-                __builtin_memcpy(&v, text + (rev ? src - (kLaneBytes - 1) : src), sizeof v);
-                if (rev)
-                    v = make_uint4(__builtin_bswap32(complement_upper4(v.w)), __builtin_bswap32(complement_upper4(v.z)),
-                                   __builtin_bswap32(complement_upper4(v.y)), __builtin_bswap32(complement_upper4(v.x)));
-                *reinterpret_cast<uint4 *>(out + j0) = v;
-                return;
-            }
-            const int64_t gap = rec.line_width - line_bases;
-            for (int i = 0; i < m; i++) {
-                const uint32_t b = text[src];
-                put(rev ? complement_upper(b) : b);
-                if (rev) { if (col == 0) { col = line_bases - 1; src -= gap + 1; } else { col--; src--; } }
-                else if (++col == line_bases) { col = 0; src += gap + 1; } else src++;
-            }
-            if (k >= cnt) break;
+            const int m = left < l.cnt - l.k ? static_cast<int>(left) : l.cnt - l.k;
+            if (gather_bases(l, text, rec, q, m, primed[r] != 0, out, ComplementUpper())) return;
+            if (l.full()) break;
         }
-        put('\n');                                                           // the sequence's LF: the record is done
+        l.put('\n');                                                         // the sequence's LF: the record is done
         r++;
         while (r < n_records && out_off[r + 1] == out_off[r]) r++;           // (dropped records)
     }
-    if (cnt == kLaneBytes)
-        *reinterpret_cast<uint4 *>(out + j0) = make_uint4(static_cast<uint32_t>(acc_lo), static_cast<uint32_t>(acc_lo >> 32), static_cast<uint32_t>(acc_hi),
-                                                          static_cast<uint32_t>(acc_hi >> 32));
-    else
-        for (int i = 0; i < cnt; i++) out[j0 + i] = static_cast<uint8_t>((i < 8 ? acc_lo >> (8 * i) : acc_hi >> (8 * (i - 8))) & 0xffu);
+    l.store(out);
 }
 
 // ---- the index rows ---------------------------------------------------------------------------------------------------------------

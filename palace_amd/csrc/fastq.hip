@@ -25,7 +25,6 @@ struct TileBase { int64_t read0, byte0; int32_t phase, pad; };
 struct ScratchHead { int32_t skip; int32_t pad[15]; };
 
 inline size_t tiles_of(int64_t n) { return static_cast<size_t>((n + kTileBytes - 1) / kTileBytes); }
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 
 __device__ __forceinline__ uint64_t rotl64(uint64_t x, int s) { return s ? (x << s) | (x >> (64 - s)) : x; }
 

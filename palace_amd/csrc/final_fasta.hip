@@ -13,12 +13,11 @@
 //      lane whose j is a candidate and whose sum suffices looks its arc up by binary search.  The lanes keep their least key; a
 //      reduction over the wave and the four waves leaves the path's.
 //
-// The writer is path_fasta.hip's with three differences: a token's place in its path's sequence includes the separator in front
-// of it (palace_final_fasta_lengths decides that: separator iff bytes were accumulated before), a path without bytes has no text
-// at all, and a reversed record is complemented by the ambiguous-DNA table.
+// The writer is paths_writer.hpp's, under FinalPolicy (below): a token's bytes include the separator in front of it (FinalTokSize
+// decides that: separator iff bytes were accumulated before), a path without bytes has no text at all, and a reversed record is
+// complemented by the ambiguous-DNA table.
 #include "common.hpp"
-#include "scan64.hpp"
-#include "text_lanes.hpp"
+#include "paths_writer.hpp"
 
 #include <climits>
 
@@ -26,7 +25,6 @@ namespace palace {
 namespace {
 
 constexpr int kTrimThreads = 256, kTrimWaves = kTrimThreads / 64;
-constexpr int kTileThreads = 256, kTileBytes = kTileThreads * kLaneBytes;
 
 // ---- the cycle test ---------------------------------------------------------------------------------------------------------------
 
@@ -159,125 +157,25 @@ __global__ __launch_bounds__(256) void final_first_kernel(const palace_fasta_rec
     atomicMin(&first_nz[last_le(path_off, 0, n_paths - 1, t)], static_cast<unsigned long long>(t));
 }
 
-__global__ __launch_bounds__(kScanThreads) void final_tok_scan_kernel(const palace_fasta_rec *recs, const int32_t *code, int64_t n_tok, const int64_t *path_off,
-                                                                      int64_t n_paths, const unsigned long long *first_nz, int64_t sep_len, int64_t *cum,
-                                                                      long long *block_sum)
-{
-    __shared__ long long s_scan[kScanThreads / 64 + 1];
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kScanThreads + threadIdx.x;
-    long long v = 0;
-    if (i < n_tok && is_found(code[i]))
-        v = recs[code[i] >> 2].length + (static_cast<unsigned long long>(i) > first_nz[last_le(path_off, 0, n_paths - 1, i)] ? sep_len : 0);
-    long long total;
-    const long long ex = block_exclusive<long long, kScanThreads>(v, s_scan, &total);
-    if (i < n_tok) cum[i] = ex;
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
-
-__global__ __launch_bounds__(256) void final_path_len_kernel(const int64_t *cum, const int64_t *path_off, int64_t n_paths, int64_t *len)
-{
-    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (p < n_paths) len[p] = cum[path_off[p + 1]] - cum[path_off[p]];
-}
-
-// ---- the writer -------------------------------------------------------------------------------------------------------------------
-
-// Biopython's ambiguous-DNA complement as the XOR of a letter's low five bits: A<->T, C<->G, R<->Y, K<->M, B<->V, D<->H; S, W, N
-// and every other byte stay.  The same in either case.
-__constant__ uint8_t kCompXor[32] = {
-    0,
-    'A' ^ 'T', 'B' ^ 'V', 'C' ^ 'G', 'D' ^ 'H', 0, 0, 'G' ^ 'C', 'H' ^ 'D', 0, 0, 'K' ^ 'M', 0, 'M' ^ 'K',   // A .. M
-    0, 0, 0, 0, 'R' ^ 'Y', 0, 'T' ^ 'A', 0, 'V' ^ 'B', 0, 0, 'Y' ^ 'R', 0,                                   // N .. Z
-    0, 0, 0, 0, 0};
-__device__ __forceinline__ uint32_t complement(uint32_t b)
-{
-    return (b & 0xc0u) == 0x40u ? b ^ kCompXor[b & 0x1fu] : b;
-}
-__device__ __forceinline__ uint32_t complement4(uint32_t w)
-{
-    return complement(w & 0xffu) | (complement((w >> 8) & 0xffu) << 8) | (complement((w >> 16) & 0xffu) << 16) | (complement(w >> 24) << 24);
-}
-
-__global__ __launch_bounds__(kTileThreads) void final_write_kernel(const uint8_t *text, const palace_fasta_rec *recs, const int32_t *code, const int64_t *cum,
-                                                                   const int64_t *path_off, int64_t n_paths, const uint8_t *hdr, const int64_t *hdr_off,
-                                                                   const int64_t *path_out, uint32_t sep_byte, int64_t lo, int64_t hi, uint8_t *out)
-{
-    __shared__ long long s_path[2];
-    const int64_t tile0 = static_cast<int64_t>(blockIdx.x) * kTileBytes;
-    if (threadIdx.x < 2) {                                                   // the paths of the tile's first and last byte
-        const int64_t end = lo + tile0 + kTileBytes < hi ? lo + tile0 + kTileBytes : hi;
-        s_path[threadIdx.x] = last_le(path_out, 0, n_paths - 1, threadIdx.x == 0 ? lo + tile0 : end - 1);
+// a token's bytes: its record's bases, and the separator in front of them behind its path's first token with bytes
+struct FinalTokSize {
+    const palace_fasta_rec *recs;
+    const int32_t *code;
+    const int64_t *path_off;
+    int64_t n_paths;
+    const unsigned long long *first_nz;
+    int64_t sep_len;
+    __device__ __forceinline__ long long operator()(int64_t t) const
+    {
+        if (!is_found(code[t])) return 0;
+        return recs[code[t] >> 2].length + (static_cast<unsigned long long>(t) > first_nz[last_le(path_off, 0, n_paths - 1, t)] ? sep_len : 0);
     }
-    __syncthreads();
-    const int64_t j0 = tile0 + threadIdx.x * kLaneBytes, o0 = lo + j0;
-    if (o0 >= hi) return;
-    const int cnt = hi - o0 < kLaneBytes ? static_cast<int>(hi - o0) : kLaneBytes;
-    int64_t p = last_le(path_out, s_path[0], s_path[1], o0);                 // (the last of equal entries: a path with text)
-    uint64_t acc_lo = 0, acc_hi = 0;
-    int k = 0;
-    auto put = [&](uint32_t b) {
-        if (k < 8) acc_lo |= static_cast<uint64_t>(b) << (8 * k); else acc_hi |= static_cast<uint64_t>(b) << (8 * (k - 8));
-        k++;
-    };
-    while (k < cnt) {
-        const int64_t h0 = hdr_off[p], h = hdr_off[p + 1] - h0, ta = path_off[p], tb = path_off[p + 1], base = cum[ta], len = cum[tb] - base;
-        int64_t x = o0 + k - path_out[p];                                    // the byte's place in the path's text
-        for (; k < cnt && x < h + 2; x++) put(x == 0 ? '>' : x == h + 1 ? '\n' : hdr[h0 + x - 1]);
-        if (k >= cnt) break;
-        int64_t q = x - (h + 2);                                             // ... in its sequence
-        if (q < len) {
-            int64_t t = last_le(cum, ta, tb - 1, base + q);                  // (behind tokens without bytes it is the last of equal entries)
-            while (k < cnt && q < len) {
-                while (cum[t + 1] <= base + q) t++;
-                const int32_t c = code[t];
-                const palace_fasta_rec r = recs[c >> 2];
-                const int64_t sep = cum[t + 1] - cum[t] - r.length, u = base + q - cum[t];     // the separator's bytes come first
-                if (u < sep) {
-                    const int64_t left = sep - u;
-                    const int m = left < cnt - k ? static_cast<int>(left) : cnt - k;
-                    for (int i = 0; i < m; i++) put(sep_byte);
-                    q += m;
-                    continue;
-                }
-                const int64_t left = cum[t + 1] - base - q;
-                const int m = left < cnt - k ? static_cast<int>(left) : cnt - k;
-                const bool rev = (c & PALACE_PATH_REVERSE) != 0;
-                int64_t pos = u - sep;
-                if (rev) pos = r.length - 1 - pos;
-                const int64_t row = pos / r.line_bases;
-                int64_t col = pos - row * r.line_bases, src = r.seq_off + row * r.line_width + col;
-                if (m == kLaneBytes && (rev ? col >= kLaneBytes - 1 : col + kLaneBytes <= r.line_bases)) {
-                    // the lane's 16 bytes are 16 neighbours of one line: one load, one store
-                    uint4 v;
-                    __builtin_memcpy(&v, text + (rev ? src - (kLaneBytes - 1) : src), sizeof v);
-                    if (rev)
-                        v = make_uint4(__builtin_bswap32(complement4(v.w)), __builtin_bswap32(complement4(v.z)), __builtin_bswap32(complement4(v.y)),
-                                       __builtin_bswap32(complement4(v.x)));
-                    *reinterpret_cast<uint4 *>(out + j0) = v;
-                    return;
-                }
-                const int64_t gap = r.line_width - r.line_bases;
-                for (int i = 0; i < m; i++) {
-                    const uint32_t b = text[src];
-                    put(rev ? complement(b) : b);
-                    if (rev) { if (col == 0) { col = r.line_bases - 1; src -= gap + 1; } else { col--; src--; } }
-                    else if (++col == r.line_bases) { col = 0; src += gap + 1; } else src++;
-                }
-                q += m;
-            }
-            if (k >= cnt) break;
-        }
-        put('\n');                                                           // the sequence's LF: the path is done
-        do p++; while (p < n_paths - 1 && path_out[p + 1] == path_out[p]);   // (paths without text are passed over)
-    }
-    if (cnt == kLaneBytes)
-        *reinterpret_cast<uint4 *>(out + j0) = make_uint4(static_cast<uint32_t>(acc_lo), static_cast<uint32_t>(acc_lo >> 32), static_cast<uint32_t>(acc_hi),
-                                                          static_cast<uint32_t>(acc_hi >> 32));
-    else
-        for (int i = 0; i < cnt; i++) out[j0 + i] = static_cast<uint8_t>((i < 8 ? acc_lo >> (8 * i) : acc_hi >> (8 * (i - 8))) & 0xffu);
-}
+};
 
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
+struct FinalPolicy {
+    using Comp = ComplementAmbiguous;
+    static constexpr bool kSeparator = true, kSkipEmptyPaths = true;
+};
 
 }  // namespace
 }  // namespace palace
@@ -326,27 +224,18 @@ extern "C" int palace_final_fasta_lengths(palace_ctx *ctx, const palace_fasta_re
     PALACE_REQUIRE(ctx && n_tok >= 0 && n_paths >= 0 && n_tok < (1ll << 39) && n_paths < (1ll << 39) && sep_len >= 0, "bad argument");
     PALACE_REQUIRE(d_tok_cum && d_path_off && (d_path_len || n_paths == 0) && (n_tok == 0 || (d_recs && d_code && n_paths > 0)), "null device pointer");
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
-    const int64_t nb = (n_tok + kScanThreads - 1) / kScanThreads;
-    if (nb == 0) PALACE_HIP_TRY(hipMemsetAsync(d_tok_cum, 0, sizeof(int64_t), ctx->stream));
-    else {
-        const size_t b_first = align256(static_cast<size_t>(n_paths) * sizeof(unsigned long long));
-        const int rc = ensure_workspace(ctx, b_first + static_cast<size_t>(nb + 1) * sizeof(long long));
+    // the workspace: first_nz, and the scan's block sums behind it
+    const size_t b_first = align256(static_cast<size_t>(n_paths) * sizeof(unsigned long long));
+    unsigned long long *first_nz = nullptr;
+    if (n_tok) {
+        const int rc = ensure_workspace(ctx, b_first + scan_sizes_bytes(n_tok));
         if (rc) return rc;
-        unsigned long long *first_nz = static_cast<unsigned long long *>(ctx->ws.ptr);
-        long long *sums = reinterpret_cast<long long *>(static_cast<uint8_t *>(ctx->ws.ptr) + b_first);
+        first_nz = static_cast<unsigned long long *>(ctx->ws.ptr);
         PALACE_HIP_TRY(hipMemsetAsync(first_nz, 0xff, static_cast<size_t>(n_paths) * sizeof(unsigned long long), ctx->stream));       // every path: none
         hipLaunchKernelGGL(final_first_kernel, dim3(static_cast<unsigned>((n_tok + 255) / 256)), dim3(256), 0, ctx->stream, d_recs, d_code, n_tok, d_path_off,
                            n_paths, first_nz);
-        hipLaunchKernelGGL(final_tok_scan_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, d_recs, d_code, n_tok, d_path_off, n_paths,
-                           first_nz, sep_len, d_tok_cum, sums);
-        hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
-        hipLaunchKernelGGL(add_block_base_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n_tok, d_tok_cum, sums, nb);
     }
-    if (n_paths)
-        hipLaunchKernelGGL(final_path_len_kernel, dim3(static_cast<unsigned>((n_paths + 255) / 256)), dim3(256), 0, ctx->stream, d_tok_cum, d_path_off, n_paths,
-                           d_path_len);
-    PALACE_HIP_TRY(hipGetLastError());
-    return PALACE_OK;
+    return paths_lengths(ctx, FinalTokSize{d_recs, d_code, d_path_off, n_paths, first_nz, sep_len}, n_tok, d_path_off, n_paths, d_tok_cum, d_path_len, b_first);
 }
 
 extern "C" int palace_final_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const int32_t *d_code,
@@ -354,14 +243,6 @@ extern "C" int palace_final_fasta_write(palace_ctx *ctx, const uint8_t *d_text, 
                                         const int64_t *d_hdr_off, const int64_t *d_path_out, int32_t sep_byte, int64_t lo, int64_t hi, uint8_t *d_out)
 {
     PALACE_REQUIRE(ctx && n_paths >= 0 && lo >= 0 && lo <= hi && sep_byte >= 0 && sep_byte <= 255, "bad argument");
-    if (lo == hi) return PALACE_OK;
-    PALACE_REQUIRE(n_paths > 0 && d_tok_cum && d_path_off && d_hdr_off && d_path_out && d_out, "null device pointer (or bytes asked of an empty text)");
-    PALACE_REQUIRE((reinterpret_cast<uintptr_t>(d_out) & 15) == 0, "the output must be 16-byte aligned");
-    const int64_t nt = (hi - lo + kTileBytes - 1) / kTileBytes;
-    PALACE_REQUIRE(nt < (1ll << 31), "window too long");
-    PALACE_HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(final_write_kernel, dim3(static_cast<unsigned>(nt)), dim3(kTileThreads), 0, ctx->stream, d_text, d_recs, d_code, d_tok_cum, d_path_off,
-                       n_paths, d_hdr, d_hdr_off, d_path_out, static_cast<uint32_t>(sep_byte), lo, hi, d_out);
-    PALACE_HIP_TRY(hipGetLastError());
-    return PALACE_OK;
+    return paths_write<FinalPolicy>(__func__, ctx, d_text, d_recs, d_code, d_tok_cum, d_path_off, n_paths, d_hdr, d_hdr_off, d_path_out,
+                                    static_cast<uint32_t>(sep_byte), lo, hi, d_out);
 }

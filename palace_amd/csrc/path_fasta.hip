@@ -12,13 +12,10 @@
 // A line's verdict needs the line itself, its neighbour and its record's first line: no running state, so no tiling shows in it.
 // Faults are kept as the minimum of (line << 3 | code).
 //
-// The writer maps an output byte to its path (searched between the paths of the tile's first and last byte, which are searched
-// once per tile), to its token (searched once per lane in the scan of the tokens' lengths, then walked), to the base's place in
-// the text; see DESIGN.md 4 for the loads it issues.
+// The writer is paths_writer.hpp's, with this tool's token sizes and policy (below).
 #include "common.hpp"
 #include "name_hash.hpp"
-#include "scan64.hpp"
-#include "text_lanes.hpp"
+#include "paths_writer.hpp"
 
 #include <climits>
 
@@ -33,7 +30,6 @@ struct palace_fasta_names {
 namespace palace {
 namespace {
 
-constexpr int kTileThreads = 256, kTileBytes = kTileThreads * kLaneBytes;
 constexpr int64_t kNone = INT64_MAX;
 
 static_assert(kTileBytes == PALACE_FASTA_TILE_BYTES, "the header states the tile");
@@ -48,7 +44,6 @@ struct TileBase { int64_t line0, rec0, prev_le, next_le; };
 struct Head { unsigned long long key; int64_t n_records; int32_t skip, pad[11]; };
 
 inline size_t tiles_of(int64_t n) { return n <= 0 ? 0 : static_cast<size_t>((n + 1 + kTileBytes - 1) / kTileBytes); }   // (the text's end is a place too)
-inline size_t align256(size_t b) { return (b + 255) & ~static_cast<size_t>(255); }
 
 __device__ __forceinline__ uint32_t eq_mask(const uint32_t w[4], int valid, uint32_t c)
 {
@@ -345,108 +340,20 @@ __global__ __launch_bounds__(256) void path_resolve_kernel(palace_fasta_names t,
     code[i] = r < 0 ? PALACE_PATH_NOT_FOUND : (r << 2) | second | (last == '-' ? PALACE_PATH_REVERSE : 0);
 }
 
-// ---- the tokens' lengths and their scan -------------------------------------------------------------------------------------------
+// ---- the tokens' sizes and the writer's policy (paths_writer.hpp) --------------------------------------------------------------------
 
-__global__ __launch_bounds__(kScanThreads) void path_tok_scan_kernel(const palace_fasta_rec *recs, const int32_t *code, int64_t n_tok, int64_t *cum, long long *block_sum)
-{
-    __shared__ long long s_scan[kScanThreads / 64 + 1];
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * kScanThreads + threadIdx.x;
-    const long long v = (i < n_tok && code[i] >= 0) ? recs[code[i] >> 2].length : 0;
-    long long total;
-    const long long ex = block_exclusive<long long, kScanThreads>(v, s_scan, &total);
-    if (i < n_tok) cum[i] = ex;
-    if (threadIdx.x == 0) block_sum[blockIdx.x] = total;
-}
+// a token's bytes: its record's bases
+struct PathTokSize {
+    const palace_fasta_rec *recs;
+    const int32_t *code;
+    __device__ __forceinline__ long long operator()(int64_t t) const { return code[t] >= 0 ? recs[code[t] >> 2].length : 0; }
+};
 
-__global__ __launch_bounds__(256) void path_len_kernel(const int64_t *cum, const int64_t *path_off, int64_t n_paths, int64_t *len)
-{
-    const int64_t p = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
-    if (p < n_paths) len[p] = cum[path_off[p + 1]] - cum[path_off[p]];
-}
-
-// ---- the writer -------------------------------------------------------------------------------------------------------------------
-
-// A<->T, C<->G in either case; every other byte as it is
-__device__ __forceinline__ uint32_t complement(uint32_t b)
-{
-    const uint32_t u = b & 0xdfu;
-    return b ^ ((u == 'A' || u == 'T') ? 0x15u : (u == 'C' || u == 'G') ? 0x04u : 0u);
-}
-__device__ __forceinline__ uint32_t complement4(uint32_t w)
-{
-    return complement(w & 0xffu) | (complement((w >> 8) & 0xffu) << 8) | (complement((w >> 16) & 0xffu) << 16) | (complement(w >> 24) << 24);
-}
-
-__global__ __launch_bounds__(kTileThreads) void path_write_kernel(const uint8_t *text, const palace_fasta_rec *recs, const int32_t *code, const int64_t *cum,
-                                                                  const int64_t *path_off, int64_t n_paths, const uint8_t *hdr, const int64_t *hdr_off,
-                                                                  const int64_t *path_out, int64_t lo, int64_t hi, uint8_t *out)
-{
-    __shared__ long long s_path[2];
-    const int64_t tile0 = static_cast<int64_t>(blockIdx.x) * kTileBytes;
-    if (threadIdx.x < 2) {                                                   // the paths of the tile's first and last byte
-        const int64_t end = lo + tile0 + kTileBytes < hi ? lo + tile0 + kTileBytes : hi;
-        s_path[threadIdx.x] = last_le(path_out, 0, n_paths - 1, threadIdx.x == 0 ? lo + tile0 : end - 1);
-    }
-    __syncthreads();
-    const int64_t j0 = tile0 + threadIdx.x * kLaneBytes, o0 = lo + j0;
-    if (o0 >= hi) return;
-    const int cnt = hi - o0 < kLaneBytes ? static_cast<int>(hi - o0) : kLaneBytes;
-    int64_t p = last_le(path_out, s_path[0], s_path[1], o0);
-    uint64_t acc_lo = 0, acc_hi = 0;
-    int k = 0;
-    auto put = [&](uint32_t b) {
-        if (k < 8) acc_lo |= static_cast<uint64_t>(b) << (8 * k); else acc_hi |= static_cast<uint64_t>(b) << (8 * (k - 8));
-        k++;
-    };
-    while (k < cnt) {
-        const int64_t h0 = hdr_off[p], h = hdr_off[p + 1] - h0, ta = path_off[p], tb = path_off[p + 1], base = cum[ta], len = cum[tb] - base;
-        int64_t x = o0 + k - path_out[p];                                    // the byte's place in the path's text
-        for (; k < cnt && x < h + 2; x++) put(x == 0 ? '>' : x == h + 1 ? '\n' : hdr[h0 + x - 1]);
-        if (k >= cnt) break;
-        int64_t q = x - (h + 2);                                             // ... in its sequence
-        if (q < len) {
-            int64_t t = last_le(cum, ta, tb - 1, base + q);                  // (behind tokens without bases it is the last of equal entries)
-            while (k < cnt && q < len) {
-                while (cum[t + 1] <= base + q) t++;
-                const int64_t left = cum[t + 1] - base - q;
-                const int m = left < cnt - k ? static_cast<int>(left) : cnt - k;
-                const int32_t c = code[t];
-                const palace_fasta_rec r = recs[c >> 2];
-                const bool rev = (c & PALACE_PATH_REVERSE) != 0;
-                int64_t pos = q - (cum[t] - base);
-                if (rev) pos = r.length - 1 - pos;
-                const int64_t row = pos / r.line_bases;
-                int64_t col = pos - row * r.line_bases, src = r.seq_off + row * r.line_width + col;
-                if (m == kLaneBytes && (rev ? col >= kLaneBytes - 1 : col + kLaneBytes <= r.line_bases)) {
-                    // the lane's 16 bytes are 16 neighbours of one line: one load, one store
-                    uint4 v;
-                    __builtin_memcpy(&v, text + (rev ? src - (kLaneBytes - 1) : src), sizeof v);
-                    if (rev)
-                        v = make_uint4(__builtin_bswap32(complement4(v.w)), __builtin_bswap32(complement4(v.z)), __builtin_bswap32(complement4(v.y)),
-                                       __builtin_bswap32(complement4(v.x)));
-                    *reinterpret_cast<uint4 *>(out + j0) = v;
-                    return;
-                }
-                const int64_t gap = r.line_width - r.line_bases;
-                for (int i = 0; i < m; i++) {
-                    const uint32_t b = text[src];
-                    put(rev ? complement(b) : b);
-                    if (rev) { if (col == 0) { col = r.line_bases - 1; src -= gap + 1; } else { col--; src--; } }
-                    else if (++col == r.line_bases) { col = 0; src += gap + 1; } else src++;
-                }
-                q += m;
-            }
-            if (k >= cnt) break;
-        }
-        put('\n');                                                           // the sequence's LF: the path is done
-        p++;
-    }
-    if (cnt == kLaneBytes)
-        *reinterpret_cast<uint4 *>(out + j0) = make_uint4(static_cast<uint32_t>(acc_lo), static_cast<uint32_t>(acc_lo >> 32), static_cast<uint32_t>(acc_hi),
-                                                          static_cast<uint32_t>(acc_hi >> 32));
-    else
-        for (int i = 0; i < cnt; i++) out[j0 + i] = static_cast<uint8_t>((i < 8 ? acc_lo >> (8 * i) : acc_hi >> (8 * (i - 8))) & 0xffu);
-}
+// the tokens' bases and nothing between them; every path has its header and its LF
+struct PathsPolicy {
+    using Comp = ComplementAcgt;
+    static constexpr bool kSeparator = false, kSkipEmptyPaths = false;
+};
 
 }  // namespace
 }  // namespace palace
@@ -545,20 +452,7 @@ extern "C" int palace_path_fasta_lengths(palace_ctx *ctx, const palace_fasta_rec
     PALACE_REQUIRE(ctx && n_tok >= 0 && n_paths >= 0 && n_tok < (1ll << 39) && n_paths < (1ll << 39), "bad argument");
     PALACE_REQUIRE(d_tok_cum && d_path_off && (d_path_len || n_paths == 0) && (n_tok == 0 || (d_recs && d_code)), "null device pointer");
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
-    const int64_t nb = (n_tok + kScanThreads - 1) / kScanThreads;
-    if (nb == 0) PALACE_HIP_TRY(hipMemsetAsync(d_tok_cum, 0, sizeof(int64_t), ctx->stream));
-    else {
-        const int rc = ensure_workspace(ctx, static_cast<size_t>(nb + 1) * sizeof(long long));
-        if (rc) return rc;
-        long long *sums = static_cast<long long *>(ctx->ws.ptr);
-        hipLaunchKernelGGL(path_tok_scan_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, d_recs, d_code, n_tok, d_tok_cum, sums);
-        hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sums, nb);
-        hipLaunchKernelGGL(add_block_base_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n_tok, d_tok_cum, sums, nb);
-    }
-    if (n_paths)
-        hipLaunchKernelGGL(path_len_kernel, dim3(static_cast<unsigned>((n_paths + 255) / 256)), dim3(256), 0, ctx->stream, d_tok_cum, d_path_off, n_paths, d_path_len);
-    PALACE_HIP_TRY(hipGetLastError());
-    return PALACE_OK;
+    return paths_lengths(ctx, PathTokSize{d_recs, d_code}, n_tok, d_path_off, n_paths, d_tok_cum, d_path_len);
 }
 
 extern "C" int palace_path_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const int32_t *d_code,
@@ -566,14 +460,5 @@ extern "C" int palace_path_fasta_write(palace_ctx *ctx, const uint8_t *d_text, c
                                        const int64_t *d_hdr_off, const int64_t *d_path_out, int64_t lo, int64_t hi, uint8_t *d_out)
 {
     PALACE_REQUIRE(ctx && n_paths >= 0 && lo >= 0 && lo <= hi, "bad argument");
-    if (lo == hi) return PALACE_OK;
-    PALACE_REQUIRE(n_paths > 0 && d_tok_cum && d_path_off && d_hdr_off && d_path_out && d_out, "null device pointer (or bytes asked of an empty text)");
-    PALACE_REQUIRE((reinterpret_cast<uintptr_t>(d_out) & 15) == 0, "the output must be 16-byte aligned");
-    const int64_t nt = (hi - lo + kTileBytes - 1) / kTileBytes;
-    PALACE_REQUIRE(nt < (1ll << 31), "window too long");
-    PALACE_HIP_TRY(hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(path_write_kernel, dim3(static_cast<unsigned>(nt)), dim3(kTileThreads), 0, ctx->stream, d_text, d_recs, d_code, d_tok_cum, d_path_off,
-                       n_paths, d_hdr, d_hdr_off, d_path_out, lo, hi, d_out);
-    PALACE_HIP_TRY(hipGetLastError());
-    return PALACE_OK;
+    return paths_write<PathsPolicy>(__func__, ctx, d_text, d_recs, d_code, d_tok_cum, d_path_off, n_paths, d_hdr, d_hdr_off, d_path_out, 0, lo, hi, d_out);
 }

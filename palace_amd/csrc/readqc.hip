@@ -17,18 +17,17 @@
 // The filter's counts are ballots over the kept prefix.  The waves walk the pairs with a stride, so the eleven sums leave a wave
 // once, not once per pair.
 //
-// The writer is path_fasta.hip's pattern: a lane owns 16 bytes of the window and stores them once; the record of a tile's first and
-// last byte is searched once per tile, a lane searches between them.
+// The writer's lanes are window_lanes.hpp's: a lane owns 16 bytes of the window and stores them once; the items are the pairs, an
+// item's text is the four lines of a read.
 #include "common.hpp"
 #include "fastq_rules.hpp"
-#include "scan64.hpp"
+#include "window_lanes.hpp"
 
 namespace palace {
 namespace {
 
 constexpr int kQcThreads = 256, kQcWaves = kQcThreads / kWave;
 constexpr int kQcGridCap = kCUs * 5 * 4;                 // the plan's workgroups: four times what is resident (32 KiB of LDS each)
-constexpr int kTileThreads = 256, kTileBytes = kTileThreads * kLaneBytes;
 
 static_assert(sizeof(palace_readqc_params) == 48, "params layout");
 static_assert(kQcWaves * 2 * PALACE_FASTQ_MAX_SEQ == 32768, "a workgroup's LDS");
@@ -182,50 +181,33 @@ __global__ __launch_bounds__(kTileThreads) void readqc_write_kernel(const uint8_
                                                                     int64_t lo, int64_t hi, uint8_t *out)
 {
     __shared__ long long s_rec[2];
-    const int64_t tile0 = static_cast<int64_t>(blockIdx.x) * kTileBytes;
-    if (threadIdx.x < 2) {                                                   // the records of the tile's first and last byte
-        const int64_t end = lo + tile0 + kTileBytes < hi ? lo + tile0 + kTileBytes : hi;
-        s_rec[threadIdx.x] = last_le(off, 0, n_pairs - 1, threadIdx.x == 0 ? lo + tile0 : end - 1);
-    }
-    __syncthreads();
-    const int64_t j0 = tile0 + threadIdx.x * kLaneBytes, o0 = lo + j0;
-    if (o0 >= hi) return;
-    const int cnt = hi - o0 < kLaneBytes ? static_cast<int>(hi - o0) : kLaneBytes;
-    int64_t p = last_le(off, s_rec[0], s_rec[1], o0);                        // (behind dropped pairs it is the last of equal entries: a kept one)
-    uint64_t acc_lo = 0, acc_hi = 0;
-    int k = 0;
-    auto put = [&](uint32_t b) {
-        if (k < 8) acc_lo |= static_cast<uint64_t>(b) << (8 * k); else acc_hi |= static_cast<uint64_t>(b) << (8 * (k - 8));
-        k++;
-    };
-    while (k < cnt) {
+    LaneOut l;
+    int64_t p = window_lane(off, n_pairs, lo, hi, s_rec, &l);                // (behind dropped pairs it is a kept one)
+    if (p < 0) return;
+    while (!l.full()) {
         const int64_t n = len[p];
         const int64_t src[4] = {start[4 * p], start[4 * p + 1], start[4 * p + 2], start[4 * p + 3]};
         const int64_t ln[4] = {src[1] - 1 - src[0], n, src[3] - 1 - src[2], n};
-        int64_t x = o0 + k - off[p];                                         // the byte's place in the record
+        int64_t x = l.o0 + l.k - off[p];                                     // the byte's place in the record
 #pragma unroll
         for (int s = 0; s < 4; s++) {
-            if (k >= cnt) break;
+            if (l.full()) break;
             if (x > ln[s]) { x -= ln[s] + 1; continue; }
-            if (k == 0 && cnt == kLaneBytes && x + kLaneBytes <= ln[s]) {    // the lane's 16 bytes are 16 neighbours of one line: one load, one store
+            if (l.k == 0 && l.cnt == kLaneBytes && x + kLaneBytes <= ln[s]) {    // the lane's 16 bytes are 16 neighbours of one line: one load, one store
                 uint4 v;
                 __builtin_memcpy(&v, text + src[s] + x, sizeof v);
-                *reinterpret_cast<uint4 *>(out + j0) = v;
+                *reinterpret_cast<uint4 *>(out + l.j0) = v;
                 return;
             }
-            for (; x < ln[s] && k < cnt; x++) put(text[src[s] + x]);
-            if (k < cnt) put('\n');
+            for (; x < ln[s] && !l.full(); x++) l.put(text[src[s] + x]);
+            if (!l.full()) l.put('\n');
             x = 0;
         }
-        if (k >= cnt) break;
+        if (l.full()) break;
         do p++; while (p < n_pairs && off[p + 1] == off[p]);                 // the next kept pair: bytes are left, so there is one
         if (p >= n_pairs) break;                                             // (hi beyond the text: the caller's fault, nothing is read for it)
     }
-    if (cnt == kLaneBytes)
-        *reinterpret_cast<uint4 *>(out + j0) = make_uint4(static_cast<uint32_t>(acc_lo), static_cast<uint32_t>(acc_lo >> 32), static_cast<uint32_t>(acc_hi),
-                                                          static_cast<uint32_t>(acc_hi >> 32));
-    else
-        for (int i = 0; i < cnt; i++) out[j0 + i] = static_cast<uint8_t>((i < 8 ? acc_lo >> (8 * i) : acc_hi >> (8 * (i - 8))) & 0xffu);
+    l.store(out);
 }
 
 }  // namespace

@@ -28,7 +28,6 @@ constexpr int kLineThreads = 256, kLineTile = PALACE_SAM_TILE;
 static_assert(kLineThreads * kLaneBytes == kLineTile, "a lane takes 16 bytes of the tile");
 constexpr int64_t kMaxLine = 1ll << 29;
 
-inline size_t align256(size_t v) { return (v + 255) & ~static_cast<size_t>(255); }
 
 // the lane's LFs that begin a line: every LF but one that is the text's last byte
 __device__ __forceinline__ uint32_t line_lf_mask(const uint8_t *text, int64_t n, int64_t at)

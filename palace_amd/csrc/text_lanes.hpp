@@ -1,5 +1,7 @@
-// What the text kernels (fastq.hip, depth_parse.hip) share: a lane's 16 bytes of a text window, the mask of its newlines, and the
-// workgroup's exclusive prefix sum that turns newline counts into line ordinals.
+// What the kernels that read a text 16 bytes a lane share (fastq.hip, depth_parse.hip, sam.hip, the FASTA index of path_fasta.hip,
+// the checks of fastg_split.hip): a lane's 16 bytes of a text window, the mask of its newlines, and the
+// workgroup's exclusive prefix sum that turns newline counts into line ordinals -- which is also the block step of every scan of
+// scan64.hpp.  The lanes that WRITE a text are window_lanes.hpp's.
 #pragma once
 #include "common.hpp"
 

@@ -1,7 +1,8 @@
-// device_scope.hpp, mapped_file.hpp and the member writer's arithmetic on their own (tests/test_host_device_scope.py; also built
-// with the host sanitizers).  No device and no libpalace_hip.so: the few palace_* calls the headers make are stubs here that count
-// their calls, remember what is live and can be told to fail.  `device_scope_selftest <scratch directory>` prints one line per
-// failed check and `ok <checks>` at the end; exit code 1 if any check failed.
+// device_scope.hpp, mapped_file.hpp, output_windows.hpp and the member writer's arithmetic on their own
+// (tests/test_host_device_scope.py; also built with the host sanitizers).  No device and no libpalace_hip.so: the few palace_* calls
+// the headers make are stubs here that count their calls, remember what is live, queue the asynchronous copies and can be told to
+// fail.  `device_scope_selftest <scratch directory>` prints one line per failed check and `ok <checks>` at the end; exit code 1 if
+// any check failed.
 #include <zlib.h>
 
 #include <algorithm>
@@ -9,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <map>
 #include <string>
 #include <vector>
@@ -18,6 +20,7 @@
 #include "bgzf_members_device.hpp"
 #include "device_scope.hpp"
 #include "mapped_file.hpp"
+#include "output_windows.hpp"
 #include "sam_device.hpp"
 
 using namespace palace_host;
@@ -30,6 +33,10 @@ struct Stub {
     bool fail_sync = false, fail_host_alloc = false;
     std::map<void *, size_t> live, live_host;      // pointer -> bytes asked for
     std::vector<size_t> asked;
+    struct Copy { void *dst; const void *src; size_t bytes; };
+    std::vector<Copy> queue;                        // palace_d2h_async calls in order; the first queue_done of them have happened
+    size_t queue_done = 0, mark_at[2] = {0, 0};     // mark k stands behind the first mark_at[k] copies
+    bool in_flight[2] = {false, false};             // mark k was set and not yet waited for
     void reset() { *this = Stub(); }
 } stub;
 const char *kErr = "out of memory (stub)";
@@ -83,6 +90,27 @@ int palace_h2d(palace_ctx *, void *d_dst, const void *h_src, size_t bytes)
     return 0;
 }
 int palace_sync(palace_ctx *) { stub.syncs++; return stub.fail_sync ? -1 : 0; }
+// the stream of the stubs: a copy back is only queued; it happens when a mark behind it is waited for
+int palace_d2h_async(palace_ctx *, void *h_dst, const void *d_src, size_t bytes)
+{
+    stub.queue.push_back(Stub::Copy{h_dst, d_src, bytes});
+    return 0;
+}
+int palace_mark(palace_ctx *, int idx)
+{
+    stub.mark_at[idx & 1] = stub.queue.size();
+    stub.in_flight[idx & 1] = true;
+    return 0;
+}
+int palace_mark_wait(palace_ctx *, int idx)
+{
+    for (; stub.queue_done < stub.mark_at[idx & 1]; stub.queue_done++) {
+        const Stub::Copy &c = stub.queue[stub.queue_done];
+        std::memcpy(c.dst, c.src, c.bytes);
+    }
+    stub.in_flight[idx & 1] = false;
+    return 0;
+}
 int palace_bam_names_destroy(palace_ctx *, palace_bam_names *) { stub.destroys++; return 0; }
 int palace_fasta_names_destroy(palace_ctx *, palace_fasta_names *) { stub.destroys++; return 0; }
 int palace_depth_text_destroy(palace_ctx *, palace_depth_text *) { stub.destroys++; return 0; }
@@ -273,6 +301,96 @@ void test_mapped_file(const std::string &dir)
     }
 }
 
+std::string file_bytes(const std::string &path)
+{
+    std::ifstream f(path, std::ios::binary);
+    return std::string(std::istreambuf_iterator<char>(f), std::istreambuf_iterator<char>());
+}
+
+// output_windows.hpp: one writer, 64-byte windows, texts of several lengths one after the other from the same buffers
+void test_windows(const std::string &dir)
+{
+    const char *unset = "PALACE_SELFTEST_WINDOW_UNSET", *var = "PALACE_SELFTEST_WINDOW";
+    unsetenv(unset);
+    CHECK(window_bytes(unset) == (256ll << 20));
+    for (const char *v : {"", "0", "-5", "abc"}) {
+        setenv(var, v, 1);
+        CHECK(window_bytes(var) == (256ll << 20));
+    }
+    setenv(var, "64", 1);
+    CHECK(window_bytes(var) == 64);
+
+    const int64_t win = 64;
+    stub.reset();
+    {
+        DeviceScope dev(ctx);
+        {   // the window is no longer than the longest text and never empty
+            WindowWriter none(ctx, dev, unset, 0), small(ctx, dev, var, 10), whole(ctx, dev, unset, 1000);
+            CHECK(none.win == 1 && small.win == 10 && whole.win == 1000);
+            CHECK(stub.asked == (std::vector<size_t>{1, 1, 10, 10, 1000, 1000}) && stub.live_host.size() == 6);
+        }
+        CHECK(stub.live_host.empty() && stub.host_allocs == 6 && stub.host_frees == 6);
+        WindowWriter ww(ctx, dev, var, 3 * win);
+        CHECK(ww.win == win && stub.mallocs == 8 && stub.host_allocs == 8 && stub.live_host.size() == 2);
+        for (const auto &kv : stub.live_host) CHECK(kv.second == static_cast<size_t>(win));
+        std::vector<char> text(static_cast<size_t>(3 * win));
+        for (size_t i = 0; i < text.size(); i++) text[i] = static_cast<char>((i * 2654435761u) >> 11);
+        for (int64_t total : {int64_t{0}, int64_t{1}, win, win + 1, 3 * win}) {
+            const std::string path = dir + "/windows_" + std::to_string(total);
+            std::FILE *f = std::fopen(path.c_str(), "wb");
+            CHECK(f != nullptr);
+            const size_t copies = stub.queue.size();
+            int64_t next = 0;
+            ww.write(total, f, path, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
+                CHECK(lo == next && hi == (lo + win < total ? lo + win : total) && hi > lo);
+                const int k = d_win == ww.d_win[1] ? 1 : 0;
+                CHECK(d_win == ww.d_win[k] && k == ((lo / win) & 1));
+                CHECK(!stub.in_flight[k]);                                   // what was copied out of this window before has arrived
+                std::memset(d_win, 0xee, static_cast<size_t>(win));
+                std::memcpy(d_win, text.data() + lo, static_cast<size_t>(hi - lo));
+                next = hi;
+            });
+            CHECK(next == total && stub.queue.size() - copies == static_cast<size_t>((total + win - 1) / win));
+            CHECK(stub.queue_done == stub.queue.size() && !stub.in_flight[0] && !stub.in_flight[1]);     // nothing is left on its way
+            CHECK(std::fclose(f) == 0);
+            CHECK(file_bytes(path) == std::string(text.data(), static_cast<size_t>(total)));
+        }
+        // a file that takes no byte: the stated text, for the first window and for a later one; nothing of it when there is no byte
+        std::vector<std::string> targets{dir + "/windows_0"};                // (opened for reading: a write to it fails)
+        if (std::FILE *full = std::fopen("/dev/full", "wb")) { std::fclose(full); targets.push_back("/dev/full"); }
+        for (const std::string &target : targets)
+            for (int64_t total : {int64_t{0}, int64_t{1}, 3 * win}) {
+                std::FILE *f = std::fopen(target.c_str(), target == "/dev/full" ? "wb" : "rb");
+                CHECK(f != nullptr);
+                std::setvbuf(f, nullptr, _IONBF, 0);
+                std::string said;
+                try {
+                    ww.write(total, f, "the name", [&](int64_t lo, int64_t hi, uint8_t *d_win) { std::memcpy(d_win, text.data() + lo, static_cast<size_t>(hi - lo)); });
+                } catch (const Failure &e) { said = e.what(); }
+                CHECK(said == (total ? "cannot write the name" : ""));
+                std::fclose(f);
+            }
+        CHECK(stub.mallocs == 8 && stub.host_allocs == 8);                   // (the buffers of the start served every text)
+    }
+    CHECK(stub.live.empty() && stub.live_host.empty() && stub.frees == 8 && stub.host_frees == 8 && stub.bad_frees == 0);
+    stub.reset();
+    stub.fail_host_alloc = true;                                             // no pinned memory: the label, and the device windows go with the scope
+    std::string said;
+    try {
+        DeviceScope dev(ctx);
+        WindowWriter ww(ctx, dev, var, 100);
+    } catch (const std::runtime_error &e) { said = e.what(); }
+    CHECK(said == "no pinned memory for an output window: out of memory (stub)" && stub.mallocs == 2 && stub.live.empty() && stub.bad_frees == 0);
+    stub.reset();
+    stub.fail_malloc = 2;
+    said.clear();
+    try {
+        DeviceScope dev(ctx, no_room_does_not_fit);
+        WindowWriter ww(ctx, dev, var, 100);
+    } catch (const DeviceNoRoom &e) { said = e.what(); }
+    CHECK(said == "an output window (64 bytes) does not fit the device: out of memory (stub)" && stub.live.empty() && stub.host_allocs == 0);
+}
+
 void test_member_arithmetic()
 {
     const uint64_t T = 0xff00;
@@ -337,6 +455,7 @@ int main(int argc, char **argv)
     test_guards();
     test_clock();
     test_mapped_file(argv[1]);
+    test_windows(argv[1]);
     test_member_arithmetic();
     test_stored_member();
     std::printf("%s %d\n", failed ? "failed" : "ok", checks);

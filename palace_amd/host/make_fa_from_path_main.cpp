@@ -18,7 +18,9 @@
 #include "device_pick.hpp"
 #include "device_scope.hpp"
 #include "fast_exit.hpp"
+#include "fasta_device.hpp"
 #include "fastx.hpp"
+#include "output_windows.hpp"
 #include "path_tokens.hpp"
 #include "textio.hpp"
 #include "trace.hpp"
@@ -48,19 +50,12 @@ struct Assembly {
         const int64_t n = static_cast<int64_t>(text.size);
         d_text = dev.upload(text.bytes(), text.size, "the FASTA is read on the device and has no other path: it");
         tr.lap("FASTA uploaded");
-        const size_t sb = palace_fasta_index_scratch_bytes(n);
-        void *d_scratch = dev.alloc(sb, "the index's scratch");
-        palace_fasta_status st{};
-        HIP_OK(palace_fasta_index(ctx, d_text, n, nullptr, 0, d_scratch, sb, &st));                                  // how many records
-        d_recs = dev.array<palace_fasta_rec>(static_cast<size_t>(st.n_records), "the FASTA's index");
-        HIP_OK(palace_fasta_index(ctx, d_text, n, d_recs, st.n_records, d_scratch, sb, &st));
-        if (st.error) throw Failure(fasta + ": line " + std::to_string(st.bad_line) + ": " + fasta_fault_text(st.error));
-        n_records = st.n_records;
+        const palace_host::FastaIndex ix = palace_host::index_fasta(ctx, dev, d_text, n, "the FASTA's index");
+        if (ix.st.error) throw Failure(fasta + ": line " + std::to_string(ix.st.bad_line) + ": " + fasta_fault_text(ix.st.error));
+        d_recs = ix.d_recs;
+        n_records = ix.st.n_records;
         tr.lap("FASTA indexed");
-        uint8_t *d_dup = dev.array<uint8_t>(static_cast<size_t>(n_records), "the duplicate flags");
-        HIP_OK(palace_fasta_names_create(ctx, d_text, d_recs, n_records, d_dup, &names.h));
-        std::vector<uint8_t> h_dup(static_cast<size_t>(n_records));
-        if (n_records) HIP_OK(palace_d2h(ctx, h_dup.data(), d_dup, h_dup.size()));
+        const std::vector<uint8_t> h_dup = palace_host::hash_names(ctx, dev, d_text, d_recs, n_records, names);
         size_t k = 0;
         for (; k < h_dup.size() && !h_dup[k]; k++) {}
         if (k < h_dup.size()) {                                             // (rare: the records come to the host only to name them)
@@ -71,18 +66,9 @@ struct Assembly {
                     std::fprintf(stderr, "make_fa_from_path: warning: %s: sequence name '%.*s' appears again in record %zu: the first one is used\n", fasta.c_str(),
                                  static_cast<int>(recs[k].name_len), text.data + recs[k].name_off, k + 1);
         }
-        dev.give_back(d_scratch);
-        dev.give_back(d_dup);
         tr.lap("names hashed");
     }
 };
-
-int64_t window_bytes()
-{
-    const char *e = std::getenv("PALACE_PATHFA_WINDOW");
-    const long long v = (e && *e) ? std::atoll(e) : 0;
-    return v > 0 ? static_cast<int64_t>(v) : (256ll << 20);
-}
 
 struct Job { std::string paths, out, mode; };
 
@@ -97,7 +83,7 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
     catch (const std::exception &) { throw Failure("cannot open " + job.paths); }
     std::FILE *out = std::fopen(job.out.c_str(), "wb");
     if (!out) throw Failure("cannot write " + job.out);
-    struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{out};
+    palace_host::FileGuard closer{out};
     const palace_host::PathTokens tk = palace_host::split_paths(ptext.data, ptext.size);
     const int64_t n_tok = static_cast<int64_t>(tk.tokens()), n_paths = static_cast<int64_t>(tk.lines());
     tr.lap("paths split");
@@ -149,29 +135,13 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
     const int64_t *d_path_out = dev.upload(path_out.data(), path_out.size(), "the paths' places");
     tr.lap("lengths and headers");
 
-    // windows of the output text: window w is computed and copied back while window w - 1 goes to the file
-    const int64_t win = total < window_bytes() ? total : window_bytes();
-    if (total) {
-        uint8_t *d_win[2] = {dev.array<uint8_t>(static_cast<size_t>(win), "an output window"), dev.array<uint8_t>(static_cast<size_t>(win), "an output window")};
-        const palace_host::PinnedBuffer pin0(ctx, static_cast<size_t>(win), "no pinned memory for an output window"),
-            pin1(ctx, static_cast<size_t>(win), "no pinned memory for an output window");
-        void *const pin[2] = {pin0.p, pin1.p};
-        auto flush = [&](int64_t w) {
-            const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
-            HIP_OK(palace_mark_wait(ctx, static_cast<int>(w & 1)));
-            if (std::fwrite(pin[w & 1], 1, static_cast<size_t>(hi - lo), out) != static_cast<size_t>(hi - lo)) throw Failure("cannot write " + job.out);
-        };
-        const int64_t n_win = (total + win - 1) / win;
-        for (int64_t w = 0; w < n_win; w++) {
-            const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
-            HIP_OK(palace_path_fasta_write(ctx, as.d_text, as.d_recs, d_code, d_cum, d_path_off, n_paths, d_hdr, d_hdr_off, d_path_out, lo, hi, d_win[w & 1]));
-            HIP_OK(palace_d2h_async(ctx, pin[w & 1], d_win[w & 1], static_cast<size_t>(hi - lo)));
-            HIP_OK(palace_mark(ctx, static_cast<int>(w & 1)));
-            if (w) flush(w - 1);
-        }
-        flush(n_win - 1);
+    if (total) {                                                             // the output text, in windows (output_windows.hpp)
+        palace_host::WindowWriter windows(ctx, dev, "PALACE_PATHFA_WINDOW", total);
+        windows.write(total, out, job.out, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
+            HIP_OK(palace_path_fasta_write(ctx, as.d_text, as.d_recs, d_code, d_cum, d_path_off, n_paths, d_hdr, d_hdr_off, d_path_out, lo, hi, d_win));
+        });
     }
-    closer.f = nullptr;
+    closer.release();
     if (std::fclose(out) != 0) throw Failure("cannot write " + job.out);
     tr.lap("output written");
 }

@@ -17,9 +17,11 @@
 #include "device_pick.hpp"
 #include "device_scope.hpp"
 #include "fast_exit.hpp"
+#include "fasta_device.hpp"
 #include "fastx.hpp"
 #include "final_tokens.hpp"
 #include "mapped_file.hpp"
+#include "output_windows.hpp"
 #include "trace.hpp"
 
 namespace {
@@ -30,13 +32,6 @@ using palace_host::fsv;
 
 constexpr int64_t kSepLen = 50;
 constexpr int32_t kSepByte = 'N';
-
-int64_t window_bytes()
-{
-    const char *e = std::getenv("PALACE_FINALFA_WINDOW");
-    const long long v = (e && *e) ? std::atoll(e) : 0;
-    return v > 0 ? static_cast<int64_t>(v) : (256ll << 20);
-}
 
 struct Args {
     std::string paths, graph, fasta, out, prefix;
@@ -139,19 +134,11 @@ void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
     palace_host::FastaNamesHandle names(ctx);
     const int64_t fn = static_cast<int64_t>(ftext.size);
     const uint8_t *d_text = as.upload(ftext.bytes(), ftext.size, "the FASTA is read on the device and has no other path: it");
-    palace_fasta_rec *d_recs = nullptr;
+    const palace_host::FastaIndex ix = palace_host::index_fasta(ctx, as, d_text, fn, "the FASTA's index");
+    if (ix.st.error) fault(a.fasta, ix.st.bad_line, palace_host::fasta_fault_text(ix.st.error));
+    palace_fasta_rec *const d_recs = ix.d_recs;
     {
-        const size_t sb = palace_fasta_index_scratch_bytes(fn);
-        void *d_scratch = as.alloc(sb, "the index's scratch");
-        palace_fasta_status st{};
-        HIP_OK(palace_fasta_index(ctx, d_text, fn, nullptr, 0, d_scratch, sb, &st));                                  // how many records
-        d_recs = as.array<palace_fasta_rec>(static_cast<size_t>(st.n_records), "the FASTA's index");
-        HIP_OK(palace_fasta_index(ctx, d_text, fn, d_recs, st.n_records, d_scratch, sb, &st));
-        if (st.error) fault(a.fasta, st.bad_line, palace_host::fasta_fault_text(st.error));
-        uint8_t *d_dup = as.array<uint8_t>(static_cast<size_t>(st.n_records), "the duplicate flags");
-        HIP_OK(palace_fasta_names_create(ctx, d_text, d_recs, st.n_records, d_dup, &names.h));
-        std::vector<uint8_t> dup(static_cast<size_t>(st.n_records));
-        if (st.n_records) HIP_OK(palace_d2h(ctx, dup.data(), d_dup, dup.size()));
+        const std::vector<uint8_t> dup = palace_host::hash_names(ctx, as, d_text, d_recs, ix.st.n_records, names);
         for (size_t k = 0; k < dup.size(); k++)
             if (dup[k]) {                                                    // (rare: the record comes to the host only to be named)
                 palace_fasta_rec r;
@@ -160,8 +147,6 @@ void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
                 for (int64_t i = 0; i < r.name_off; i++) line += ftext.data[i] == '\n';
                 fault(a.fasta, line, "sequence name '" + std::string(ftext.data + r.name_off, static_cast<size_t>(r.name_len)) + "' appears a second time");
             }
-        as.give_back(d_scratch);
-        as.give_back(d_dup);
     }
     tr.lap("FASTA indexed, names hashed");
 
@@ -269,33 +254,14 @@ void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
     const std::string tmp = a.out + ".tmp";
     std::FILE *out = std::fopen(tmp.c_str(), "wb");
     if (!out) throw Failure("cannot write " + tmp);
-    struct Closer {
-        std::FILE *f;
-        const std::string &path;
-        ~Closer() { if (f) { std::fclose(f); std::remove(path.c_str()); } }
-    } closer{out, tmp};
-    const int64_t win = total < window_bytes() ? total : window_bytes();
+    palace_host::FileGuard closer{out, tmp.c_str()};
     if (total) {
-        uint8_t *d_win[2] = {dev.array<uint8_t>(static_cast<size_t>(win), "an output window"), dev.array<uint8_t>(static_cast<size_t>(win), "an output window")};
-        const palace_host::PinnedBuffer pin0(ctx, static_cast<size_t>(win), "no pinned memory for an output window"),
-            pin1(ctx, static_cast<size_t>(win), "no pinned memory for an output window");
-        void *const pin[2] = {pin0.p, pin1.p};
-        auto flush = [&](int64_t w) {
-            const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
-            HIP_OK(palace_mark_wait(ctx, static_cast<int>(w & 1)));
-            if (std::fwrite(pin[w & 1], 1, static_cast<size_t>(hi - lo), out) != static_cast<size_t>(hi - lo)) throw Failure("cannot write " + tmp);
-        };
-        const int64_t n_win = (total + win - 1) / win;
-        for (int64_t w = 0; w < n_win; w++) {
-            const int64_t lo = w * win, hi = lo + win < total ? lo + win : total;
-            HIP_OK(palace_final_fasta_write(ctx, d_text, d_recs, d_out_code, d_cum, d_out_off, n_paths, d_hdr, d_hdr_off, d_path_out, kSepByte, lo, hi, d_win[w & 1]));
-            HIP_OK(palace_d2h_async(ctx, pin[w & 1], d_win[w & 1], static_cast<size_t>(hi - lo)));
-            HIP_OK(palace_mark(ctx, static_cast<int>(w & 1)));
-            if (w) flush(w - 1);
-        }
-        flush(n_win - 1);
+        palace_host::WindowWriter windows(ctx, dev, "PALACE_FINALFA_WINDOW", total);
+        windows.write(total, out, tmp, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
+            HIP_OK(palace_final_fasta_write(ctx, d_text, d_recs, d_out_code, d_cum, d_out_off, n_paths, d_hdr, d_hdr_off, d_path_out, kSepByte, lo, hi, d_win));
+        });
     }
-    closer.f = nullptr;
+    closer.release();
     if (std::fclose(out) != 0 || std::rename(tmp.c_str(), a.out.c_str()) != 0) {
         std::remove(tmp.c_str());
         throw Failure("cannot write " + a.out);

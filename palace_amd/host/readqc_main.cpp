@@ -27,6 +27,7 @@
 #include "device_scope.hpp"
 #include "fast_exit.hpp"
 #include "mapped_file.hpp"
+#include "output_windows.hpp"
 #include "trace.hpp"
 
 namespace {
@@ -185,13 +186,6 @@ Lines lines_and_records(palace_ctx *ctx, DeviceScope &dev, const DeviceText &t)
     return l;
 }
 
-int64_t window_bytes()
-{
-    const char *e = std::getenv("PALACE_READQC_WINDOW");
-    const long long v = (e && *e) ? std::atoll(e) : 0;
-    return v > 0 ? static_cast<int64_t>(v) : (256ll << 20);
-}
-
 // the temporaries of a run: removed unless it completes
 struct Outputs {
     std::vector<std::string> tmp;
@@ -249,33 +243,18 @@ void run(palace_ctx *ctx, const Options &o, palace_host::Trace &tr)
 
     // windows of the output texts: window w is computed and copied back while window w - 1 goes to its file
     const int64_t total[2] = {n[PALACE_READQC_BYTES_1], n[PALACE_READQC_BYTES_2]};
-    const int64_t most = total[0] > total[1] ? total[0] : total[1], win = most < window_bytes() ? (most ? most : 1) : window_bytes();
-    uint8_t *d_win[2] = {dev.array<uint8_t>(static_cast<size_t>(win), "an output window"), dev.array<uint8_t>(static_cast<size_t>(win), "an output window")};
-    const palace_host::PinnedBuffer pin0(ctx, static_cast<size_t>(win), "no pinned memory for an output window"),
-        pin1(ctx, static_cast<size_t>(win), "no pinned memory for an output window");
-    void *const pin[2] = {pin0.p, pin1.p};
+    palace_host::WindowWriter windows(ctx, dev, "PALACE_READQC_WINDOW", total[0] > total[1] ? total[0] : total[1]);
     Outputs outputs;
     for (int k = 0; k < 2; k++) {
         const std::string tmp = *outp[k] + ".tmp";
         std::FILE *f = std::fopen(tmp.c_str(), "wb");
         if (!f) throw Failure("cannot write " + tmp);
         outputs.tmp.push_back(tmp);
-        struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{f};
-        auto flush = [&](int64_t w) {
-            const int64_t lo = w * win, hi = lo + win < total[k] ? lo + win : total[k];
-            HIP_OK(palace_mark_wait(ctx, static_cast<int>(w & 1)));
-            if (std::fwrite(pin[w & 1], 1, static_cast<size_t>(hi - lo), f) != static_cast<size_t>(hi - lo)) throw Failure("cannot write " + tmp);
-        };
-        const int64_t n_win = (total[k] + win - 1) / win;
-        for (int64_t w = 0; w < n_win; w++) {
-            const int64_t lo = w * win, hi = lo + win < total[k] ? lo + win : total[k];
-            HIP_OK(palace_readqc_write(ctx, text[k].d, lines[k].d_start, d_len[k], d_off[k], n_pairs, lo, hi, d_win[w & 1]));
-            HIP_OK(palace_d2h_async(ctx, pin[w & 1], d_win[w & 1], static_cast<size_t>(hi - lo)));
-            HIP_OK(palace_mark(ctx, static_cast<int>(w & 1)));
-            if (w) flush(w - 1);
-        }
-        if (n_win) flush(n_win - 1);
-        closer.f = nullptr;
+        palace_host::FileGuard closer{f};
+        windows.write(total[k], f, tmp, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
+            HIP_OK(palace_readqc_write(ctx, text[k].d, lines[k].d_start, d_len[k], d_off[k], n_pairs, lo, hi, d_win));
+        });
+        closer.release();
         if (std::fclose(f) != 0) throw Failure("cannot write " + tmp);
     }
     tr.lap("outputs written");

@@ -18,7 +18,9 @@
 #include "device_pick.hpp"
 #include "device_scope.hpp"
 #include "fast_exit.hpp"
+#include "fasta_device.hpp"
 #include "fastx.hpp"
+#include "output_windows.hpp"
 #include "trace.hpp"
 
 namespace {
@@ -64,9 +66,9 @@ void write_fai(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d
     HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off, d_rows));
     std::FILE *f = std::fopen(path.c_str(), "wb");
     if (!f) throw Failure("cannot write " + path);
-    struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{f};
+    palace_host::FileGuard closer{f};
     to_file(ctx, d_rows, bytes, f, path);
-    closer.f = nullptr;
+    closer.release();
     if (std::fclose(f) != 0) throw Failure("cannot write " + path);
 }
 
@@ -77,22 +79,18 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     catch (const std::exception &) { throw Failure("cannot open " + graph); }
     std::FILE *out = std::fopen(output.c_str(), "wb");                       // (exists, empty, from here on: as the script's)
     if (!out) throw Failure("cannot write " + output);
-    struct Closer { std::FILE *f; ~Closer() { if (f) std::fclose(f); } } closer{out};
+    palace_host::FileGuard closer{out};
     tr.lap("FASTG read");
     const int64_t n = static_cast<int64_t>(text.size);
     DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
     const uint8_t *d_text = dev.upload(text.bytes(), text.size, "the FASTG is read on the device and has no other path: it");
     tr.lap("FASTG uploaded");
 
-    palace_fasta_status st{}, fg{};
-    const size_t sb = palace_fasta_index_scratch_bytes(n);
-    void *d_scratch = dev.alloc(sb, "the index's scratch");
-    HIP_OK(palace_fasta_index(ctx, d_text, n, nullptr, 0, d_scratch, sb, &st));                                      // how many records
+    const palace_host::FastaIndex ix = palace_host::index_fasta(ctx, dev, d_text, n, "the FASTG's index");
+    palace_fasta_status st = ix.st, fg{};
+    palace_fasta_rec *const d_recs = ix.d_recs;
     const int64_t n_records = st.n_records;
     const size_t nr = static_cast<size_t>(n_records);
-    palace_fasta_rec *d_recs = dev.array<palace_fasta_rec>(nr, "the FASTG's index");
-    HIP_OK(palace_fasta_index(ctx, d_text, n, d_recs, n_records, d_scratch, sb, &st));
-    dev.give_back(d_scratch);
     tr.lap("FASTG indexed");
     palace_fasta_rec *d_name_recs = dev.array<palace_fasta_rec>(nr, "the records' names");
     uint8_t *d_primed = dev.array<uint8_t>(nr, "the primed bits");
@@ -115,7 +113,7 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     tr.lap("output gathered");
     to_file(ctx, d_out, total, out, output);
     dev.give_back(d_out);
-    closer.f = nullptr;
+    closer.release();
     if (std::fclose(out) != 0) throw Failure("cannot write " + output);
     tr.lap("output written");
     if (!fai) return;
