@@ -931,6 +931,66 @@ int palace_final_fasta_write(palace_ctx *ctx, const uint8_t *d_text, const palac
                              const int64_t *d_tok_cum, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_hdr,
                              const int64_t *d_hdr_off, const int64_t *d_path_out, int32_t sep_byte, int64_t lo, int64_t hi, uint8_t *d_out);
 
+/* ---- filter_result: the BLAST table's groups, the paths' classes, the first of equal paths (the rules: DESIGN.md 8) ---------- */
+
+/* Faults of a line of the BLAST table (csrc/blast_line.hpp states the grammar) */
+#define PALACE_BLAST_ECOLUMNS 1   /* fewer than four TAB-separated columns */
+#define PALACE_BLAST_ENAME 2      /* an empty query or subject */
+#define PALACE_BLAST_EIDENTITY 3  /* column 2 is not digits[.digits] with at most 3 digits before and 6 behind the point */
+#define PALACE_BLAST_ELENGTH 4    /* column 3 is not 1-10 digits */
+#define PALACE_BLAST_EQUERY 5     /* the query of a group's first line is no record of the FASTA */
+#define PALACE_BLAST_EQEMPTY 6    /* ... or a record without bases */
+
+/* cut[k], k = 0 .. 6: the smallest integer N in [0, 10^(3 + k)] with (double)N / 10^k > threshold (10^(3 + k) when there is none):
+ * an identity spelt with k decimals, its digits read as the integer V, passes `float(text) > threshold` iff V >= cut[k].  Host
+ * arithmetic only. */
+int palace_blast_identity_cuts(double threshold, int64_t *cut);
+
+/* The groups of a BLAST table (`-outfmt 6`) that lies on the device, its lines cut by palace_sam_lines (line i =
+ * [d_line_start[i], d_line_start[i + 1] - 1), n_lines < 2^29).  Lines are taken in file order; a line begins a new group when its
+ * query or its subject differs from the previous line's, compared byte by byte.  A group's sum: the line that begins it by
+ * differing adds its alignment length whatever its identity, the table's first line and every line inside a group add theirs when
+ * the identity passes cut (palace_blast_identity_cuts of blast_ratio * 100).  A group with (double)sum / (double)length of the
+ * query's record > blast_ratio -- an IEEE division -- sets d_seg[record] = 1; d_seg[0 .. n_records) is cleared first (n_records:
+ * the records of `names`, whose text and records must still be there).  The query of a group's first line is looked up in `names`.
+ * out[0] = lines, out[1] = groups, out[2] = records flagged, out[3] / out[4] = the smallest 1-based number of a faulty line and
+ * its PALACE_BLAST_E* code, 0 / 0 for none; with a fault no group is judged and d_seg stays clear.  A wavefront owns a line and
+ * finds its TABs by ballot; the sums are two scans over the lines, so a group may span any number of workgroups.  Results are
+ * integers and do not depend on scheduling.  Temporaries come from the context's workspace.  Waits for the stream. */
+int palace_blast_groups(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, int64_t n_lines, const palace_fasta_names *names,
+                        int64_t n_records, double blast_ratio, const int64_t *cut, uint8_t *d_seg, int64_t *out);
+
+#define PALACE_FILTERRES_REC_GENE 1    /* a record's byte: its name is in the gene hit list */
+#define PALACE_FILTERRES_REC_S07 2     /* its score is > 0.7 */
+#define PALACE_FILTERRES_REC_S09 4     /* its score is >= 0.9 */
+#define PALACE_FILTERRES_REC_BLAST 8   /* palace_blast_groups flagged it */
+#define PALACE_FILTERRES_TAG_SELF 1    /* a path's tag byte: a line beginning with "self" stands before it */
+#define PALACE_FILTERRES_TAG_CYCLE 2   /* ... a line beginning with "iter" */
+#define PALACE_FILTERRES_WRITE 1       /* a path's class byte: it gets a FASTA record (if it is the first of its equals that do) */
+#define PALACE_FILTERRES_PLAIN 2       /* `<joined>` enters the result set */
+#define PALACE_FILTERRES_SELFGENE 4    /* `selfgene<joined>` is printed and enters the result set */
+#define PALACE_FILTERRES_CYCLEGENE 8   /* `cyclegene<joined>` */
+#define PALACE_FILTERRES_CYCLESCORE 16 /* `cyclescore<joined>` */
+#define PALACE_FILTERRES_GENESCORE 32  /* `genescore<joined>` is printed */
+
+/* The class of every path (d_code as palace_path_resolve left it, a negative code or one with PALACE_PATH_SECOND_TRY brings
+ * nothing; path p holds the tokens d_path_off[p] .. d_path_off[p + 1]; n_paths < 2^31).  gene / s07 / s09: any token's record has
+ * the bit; all_len: the records' lengths summed; blast_len: those of the records with PALACE_FILTERRES_REC_BLAST.  A path of one
+ * token under TAG_SELF is SELFGENE when gene or s07, else WRITE | PLAIN.  Every other path with tokens: under TAG_CYCLE, gene gives
+ * CYCLEGENE and s09 CYCLESCORE; with flags = gene or (all_len != 0 and (double)blast_len / (double)all_len > 0.2) the path is
+ * dropped when not flags and (not s09 or all_len < 1000); a path that is not dropped has WRITE, and GENESCORE when gene and s09.
+ * d_class[p] / d_all_len[p] get the class and all_len.  A wavefront owns a path, its lanes stride the tokens.  Enqueues only. */
+int palace_filter_result_plan(palace_ctx *ctx, const int32_t *d_code, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_tag,
+                              const palace_fasta_rec *d_recs, const uint8_t *d_rec_bits, uint8_t *d_class, int64_t *d_all_len);
+
+/* d_first[p]: the bits of d_class[p] (its low six) for which p is the first path, in file order, with that bit among the paths whose
+ * code sequence is IDENTICAL to p's.  Exact and deterministic: the low hash_bits (0 .. 64; an executable passes 64) of a 64-bit
+ * hash of the sequences only bring candidates together -- a stable palace_sort_u64 -- and every path then finds the first member of
+ * its run that equals it code by code; what is kept per class bit is a minimum of path indices.  Temporaries come from the
+ * context's workspace.  Enqueues only. */
+int palace_paths_first_of_equal(palace_ctx *ctx, const int32_t *d_code, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_class,
+                                int32_t hash_bits, uint8_t *d_first);
+
 /* ---- FASTG -> node FASTA and the `.fai` rows of both, on the device (split_fastg; the rules: DESIGN.md 8) -------------------- */
 
 /* Faults of a FASTG text beyond those of palace_fasta_index, reported in a palace_fasta_status like them */

@@ -259,6 +259,11 @@ _SIGS = {
     "palace_final_fasta_lengths": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p],
     "palace_final_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_blast_identity_cuts": [C.c_double, C.POINTER(C.c_int64)],
+    "palace_blast_groups": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_double, C.POINTER(C.c_int64), C.c_void_p,
+                            C.POINTER(C.c_int64)],
+    "palace_filter_result_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
+    "palace_paths_first_of_equal": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
     "palace_bam_sort_keys": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "palace_sort_u64_scratch_bytes": [C.c_int64],       # (returns size_t: restype set below)
     "palace_sort_u64": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t],
@@ -1805,3 +1810,81 @@ class FastgSplit:
             if t:
                 _check(lib().palace_fasta_names_destroy(self.ctx.h, t), "palace_fasta_names_destroy")
         self.names, self.whole_names = C.c_void_p(), C.c_void_p()
+
+
+# ---- filter_result: the BLAST groups, the paths' classes, the first of equal paths ----------------------------------------------------
+
+def blast_identity_cuts(threshold: float):
+    """palace_blast_identity_cuts -> the seven cuts (host arithmetic; the library need not reach a device)"""
+    cut = (C.c_int64 * 7)()
+    _check(lib().palace_blast_identity_cuts(float(threshold), cut), "palace_blast_identity_cuts")
+    return list(cut)
+
+
+def blast_groups(ctx: Ctx, fasta: "PathFasta", table: bytes, ratio: float, guard: int = 64):
+    """palace_sam_lines and palace_blast_groups over `table` against the names of `fasta` -> dict: lines, groups, flagged, err_line,
+    err_code, seg (uint8 per record), intact (the guard bytes around seg came back as they went in)"""
+    table = bytes(table)
+    n = len(table)
+    nscr = int(lib().palace_sam_scratch_bytes(n))
+    bufs = [ctx.upload(np.frombuffer(table, dtype=np.uint8) if n else np.zeros(1, np.uint8)), ctx.empty(max(nscr, 1), np.uint8)]
+    out = (C.c_int64 * 5)()
+    try:
+        _check(lib().palace_sam_lines(ctx.h, bufs[0].ptr, n, bufs[1].ptr, nscr, None, 0, out), "palace_sam_lines")
+        n_lines = int(out[0])
+        bufs.append(ctx.empty(n_lines + 1, np.int64))
+        _check(lib().palace_sam_lines(ctx.h, bufs[0].ptr, n, bufs[1].ptr, nscr, bufs[2].ptr, n_lines + 1, out), "palace_sam_lines")
+        bufs.append(ctx.upload(np.full(fasta.n + 2 * guard, 0xA5, np.uint8)))
+        cut = (C.c_int64 * 7)(*blast_identity_cuts(ratio * 100.0))
+        _check(lib().palace_blast_groups(ctx.h, bufs[0].ptr, bufs[2].ptr, n_lines, fasta.names, fasta.n, float(ratio), cut, bufs[3].ptr + guard, out),
+               "palace_blast_groups")
+        raw = bufs[3].to_host()
+        return dict(lines=int(out[0]), groups=int(out[1]), flagged=int(out[2]), err_line=int(out[3]), err_code=int(out[4]),
+                    seg=raw[guard:guard + fasta.n].copy(), intact=bool((raw[:guard] == 0xA5).all() and (raw[guard + fasta.n:] == 0xA5).all()))
+    finally:
+        for b in bufs:
+            b.free()
+
+
+class FilterPlan:
+    """Paths as record codes on the device (code = record << 2 | PALACE_PATH_REVERSE, negative: no record) over records of the given
+    lengths: plan(tags, rec_bits) -> (class bytes, all_len); first_of_equal(classes, hash_bits) -> the first-of-equal bytes."""
+
+    def __init__(self, ctx: Ctx, code, path_off, rec_len):
+        self.ctx = ctx
+        self.n_paths = len(path_off) - 1
+        recs = np.zeros((max(len(rec_len), 1), 6), np.int64)
+        recs[:len(rec_len), 3] = rec_len
+        code = np.ascontiguousarray(code, np.int32)
+        assert int(path_off[-1]) == len(code)
+        self.d_code = ctx.upload(code if len(code) else np.zeros(1, np.int32))
+        self.d_off = ctx.upload(np.ascontiguousarray(path_off, np.int64))
+        self.d_recs = ctx.upload(recs)
+        self.bufs = [self.d_code, self.d_off, self.d_recs]
+
+    def plan(self, tags, rec_bits):
+        n = self.n_paths
+        d_tag, d_bits = self.ctx.upload(np.ascontiguousarray(tags, np.uint8)), self.ctx.upload(np.ascontiguousarray(rec_bits, np.uint8))
+        d_cls, d_all = self.ctx.empty(max(n, 1), np.uint8), self.ctx.empty(max(n, 1), np.int64)
+        try:
+            _check(lib().palace_filter_result_plan(self.ctx.h, self.d_code.ptr, self.d_off.ptr, n, d_tag.ptr, self.d_recs.ptr, d_bits.ptr, d_cls.ptr, d_all.ptr),
+                   "palace_filter_result_plan")
+            return d_cls.to_host()[:n].copy(), d_all.to_host()[:n].copy()
+        finally:
+            for b in (d_tag, d_bits, d_cls, d_all):
+                b.free()
+
+    def first_of_equal(self, classes, hash_bits: int = 64):
+        n = self.n_paths
+        d_cls, d_first = self.ctx.upload(np.ascontiguousarray(classes, np.uint8)), self.ctx.empty(max(n, 1), np.uint8)
+        try:
+            _check(lib().palace_paths_first_of_equal(self.ctx.h, self.d_code.ptr, self.d_off.ptr, n, d_cls.ptr, hash_bits, d_first.ptr),
+                   "palace_paths_first_of_equal")
+            return d_first.to_host()[:n].copy()
+        finally:
+            d_cls.free()
+            d_first.free()
+
+    def free(self):
+        for b in self.bufs:
+            b.free()

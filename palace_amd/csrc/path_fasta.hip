@@ -14,18 +14,10 @@
 //
 // The writer is paths_writer.hpp's, with this tool's token sizes and policy (below).
 #include "common.hpp"
-#include "name_hash.hpp"
+#include "fasta_names.hpp"
 #include "paths_writer.hpp"
 
 #include <climits>
-
-struct palace_fasta_names {
-    const uint8_t *text;
-    const palace_fasta_rec *recs;
-    int32_t n;
-    uint32_t mask;
-    int32_t *slots;                          // a record or -1; equal names share the slot, which holds the smallest record
-};
 
 namespace palace {
 namespace {
@@ -285,11 +277,6 @@ __global__ __launch_bounds__(kTileThreads) void fasta_lines_kernel(const uint8_t
 
 // ---- the names ------------------------------------------------------------------------------------------------------------------
 
-__device__ __forceinline__ bool is_name(const palace_fasta_names &t, int32_t r, const uint8_t *p, int64_t n)
-{
-    return same_bytes(t.text + t.recs[r].name_off, t.recs[r].name_len, p, n);
-}
-
 // linear probing without removals, as the BAM header's table (bam.hip) -- but the smallest record of a name stays
 __global__ __launch_bounds__(256) void fasta_names_build_kernel(palace_fasta_names t)
 {
@@ -301,16 +288,6 @@ __global__ __launch_bounds__(256) void fasta_names_build_kernel(palace_fasta_nam
         const int32_t old = atomicCAS(&t.slots[at], -1, r);
         if (old < 0) return;
         if (is_name(t, old, p, n)) { atomicMin(&t.slots[at], r); return; }
-    }
-}
-
-__device__ __forceinline__ int32_t record_of(const palace_fasta_names &t, const uint8_t *p, int64_t n)
-{
-    if (n <= 0) return -1;
-    for (uint32_t at = hash_name(p, n) & t.mask;; at = (at + 1) & t.mask) {
-        const int32_t r = t.slots[at];
-        if (r < 0) return -1;
-        if (is_name(t, r, p, n)) return r;
     }
 }
 
