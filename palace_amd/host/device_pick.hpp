@@ -4,6 +4,7 @@
 // set here BEFORE the process's first HIP call: the runtime then brings up one device instead of every device of the node (its
 // start-up is most of eref's wall time), and the chosen device is ordinal 0 of the process.
 #pragma once
+#include <cstdio>
 #include <cstdlib>
 #include <exception>
 #include <iostream>
@@ -42,6 +43,33 @@ template <class Body> int with_device(const char *prog, Body body)
     } catch (const std::exception &e) { std::cerr << prog << ": " << e.what() << "\n"; }
     palace_ctx_destroy(ctx);
     return code;
+}
+
+// Two frames because they leave differently: with_device returns through the teardown (the context destroyed, main's return), while
+// device_tool leaves through FastExit::done, the caller going on while the teardown happens behind it (fast_exit.hpp).
+// The frame of make_fa_from_path, split_fastg, readqc, make_final_fa and filter_result, called when the command line is parsed: the
+// forked start, the picked device, the context, body(ctx, trace).  No device, or an exception from the body, is one `<prog>: ...` line
+// on stderr behind whatever stdout holds, and exit code 1.  (eref, generateGraph and matching bring the context up on a thread beside
+// their input and keep frames of their own.)
+template <class Body> int device_tool(const char *prog, Body body)
+{
+    FastExit fast_exit = fast_exit_begin();   // from here on this is the worker process
+    const int device = pick_device();         // before anything touches HIP
+    Trace tr(prog);
+    palace_ctx *ctx = nullptr;
+    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
+        std::fprintf(stderr, "%s: no GPU device to work on (%s); there is no CPU path\n", prog, palace_last_error());
+        return 1;
+    }
+    tr.lap("device up");
+    try {
+        body(ctx, tr);
+    } catch (const std::exception &e) {
+        std::fflush(stdout);
+        std::fprintf(stderr, "%s: %s\n", prog, e.what());
+        return 1;
+    }
+    fast_exit.done(0);          // outputs are complete and closed: the caller goes on, the teardown happens behind it
 }
 
 }  // namespace palace_host

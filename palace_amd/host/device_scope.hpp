@@ -1,6 +1,7 @@
 // The host side's device plumbing, stated once for every executable: the throw-on-error call, the owner of a step's device
-// allocations, the out-of-room exception, guards for page-locked buffers and opaque handles, the stage clock of traced runs and the
-// upload of a list of names.  Nothing here knows a file format or a kernel; it needs include/palace_hip.h and the standard library.
+// allocations, the out-of-room exception, the two sentences of a text input, guards for page-locked buffers and opaque handles, the
+// stage clock of traced runs, the upload of a list of names and the line starts of a text.  Nothing here knows a file format; it
+// needs include/palace_hip.h, mapped_file.hpp and the standard library.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "../../include/palace_hip.h"
+#include "mapped_file.hpp"
 
 namespace palace_host {
 
@@ -25,6 +27,18 @@ struct Failure : std::runtime_error { using std::runtime_error::runtime_error; }
     do {                                                                                                           \
         if ((call) != PALACE_OK) throw palace_host::Failure(std::string(#call " failed: ") + palace_last_error()); \
     } while (0)
+
+// a text input of a tool: `cannot open <path>`, whatever kept it from being mapped
+inline void open_text(MappedText &t, const std::string &path)
+{
+    try { t.open(path); }
+    catch (const std::exception &) { throw Failure("cannot open " + path); }
+}
+// a text outside its grammar: `<file>: line <n>: <reason>`
+[[noreturn]] inline void line_fault(const std::string &file, int64_t line, const std::string &reason)
+{
+    throw Failure(file + ": line " + std::to_string(line) + ": " + reason);
+}
 
 // thrown when the device cannot hold what a mode keeps there; the text is the scope's (it names the mode's way out, if there is one)
 struct DeviceNoRoom : std::runtime_error { using std::runtime_error::runtime_error; };
@@ -128,6 +142,22 @@ inline DeviceNames upload_names(DeviceScope &scope, const std::vector<std::strin
     d.blob = scope.upload(reinterpret_cast<const uint8_t *>(blob.data()), blob.size(), what, copy_what);
     d.off = scope.upload(off.data(), off.size(), what, copy_what);
     return d;
+}
+
+// the lines of the text d_text[0 .. n) (readqc, filter_result): one call of palace_sam_lines counts them, one writes their n_lines + 1
+// starts into an array of `scope` (named `what` where it does not fit).  res: the five result words of the second call
+struct TextLines { int64_t *d_start; int64_t n_lines; int64_t res[5]; };
+inline TextLines text_lines(palace_ctx *ctx, DeviceScope &scope, const uint8_t *d_text, int64_t n, const char *what)
+{
+    TextLines l{};
+    const size_t sb = palace_sam_scratch_bytes(n);
+    void *d_scratch = scope.alloc(sb, "the lines' scratch");
+    HIP_OK(palace_sam_lines(ctx, d_text, n, d_scratch, sb, nullptr, 0, l.res));
+    l.n_lines = l.res[0];
+    l.d_start = scope.array<int64_t>(static_cast<size_t>(l.n_lines) + 1, what);
+    HIP_OK(palace_sam_lines(ctx, d_text, n, d_scratch, sb, l.d_start, l.n_lines + 1, l.res));
+    scope.give_back(d_scratch);
+    return l;
 }
 
 }  // namespace palace_host

@@ -1,4 +1,4 @@
-// device_scope.hpp, mapped_file.hpp, output_windows.hpp and the member writer's arithmetic on their own
+// device_scope.hpp, mapped_file.hpp, output_windows.hpp, the duplicate helper of fasta_device.hpp and the member writer's arithmetic on their own
 // (tests/test_host_device_scope.py; also built with the host sanitizers).  No device and no libpalace_hip.so: the few palace_* calls
 // the headers make are stubs here that count their calls, remember what is live, queue the asynchronous copies and can be told to
 // fail.  `device_scope_selftest <scratch directory>` prints one line per failed check and `ok <checks>` at the end; exit code 1 if
@@ -12,6 +12,7 @@
 #include <fstream>
 #include <iterator>
 #include <map>
+#include <sys/stat.h>
 #include <string>
 #include <vector>
 
@@ -19,6 +20,7 @@
 #include "bam_stream_device.hpp"
 #include "bgzf_members_device.hpp"
 #include "device_scope.hpp"
+#include "fasta_device.hpp"
 #include "mapped_file.hpp"
 #include "output_windows.hpp"
 #include "sam_device.hpp"
@@ -28,7 +30,7 @@ using namespace palace_host;
 namespace {
 
 struct Stub {
-    int mallocs = 0, frees = 0, host_allocs = 0, host_frees = 0, copies = 0, syncs = 0, destroys = 0, bad_frees = 0;
+    int mallocs = 0, frees = 0, host_allocs = 0, host_frees = 0, copies = 0, copies_back = 0, syncs = 0, destroys = 0, bad_frees = 0;
     int fail_malloc = 0;                            // the k-th palace_malloc from now fails (0: none)
     bool fail_sync = false, fail_host_alloc = false;
     std::map<void *, size_t> live, live_host;      // pointer -> bytes asked for
@@ -87,6 +89,12 @@ int palace_h2d(palace_ctx *, void *d_dst, const void *h_src, size_t bytes)
 {
     stub.copies++;
     std::memcpy(d_dst, h_src, bytes);
+    return 0;
+}
+int palace_d2h(palace_ctx *, void *h_dst, const void *d_src, size_t bytes)
+{
+    stub.copies_back++;
+    std::memcpy(h_dst, d_src, bytes);
     return 0;
 }
 int palace_sync(palace_ctx *) { stub.syncs++; return stub.fail_sync ? -1 : 0; }
@@ -391,6 +399,182 @@ void test_windows(const std::string &dir)
     CHECK(said == "an output window (64 bytes) does not fit the device: out of memory (stub)" && stub.live.empty() && stub.host_allocs == 0);
 }
 
+bool exists(const std::string &path)
+{
+    struct stat st;
+    return ::stat(path.c_str(), &st) == 0;
+}
+
+// output_windows.hpp: the headers and places of a text of paths, against sums written out by hand
+void test_paths_text()
+{
+    using V = std::vector<int64_t>;
+    stub.reset();
+    DeviceScope dev(ctx);
+    {   // no path at all
+        const PathsText none;
+        const PathsText::OnDevice d = none.upload(dev);
+        CHECK(d.total == 0 && none.hdr.empty() && none.hdr_off == V{0} && none.path_out == V{0});
+        CHECK(d.d_hdr != nullptr && d.d_hdr_off[0] == 0 && d.d_path_out[0] == 0);
+        CHECK(stub.asked == (std::vector<size_t>{0 + 1, 8, 8}));             // (0 bytes of headers: an array of 1)
+    }
+    {   // a skipped path first, between two written ones and last; a header of 0 bytes
+        PathsText t;
+        t.skip();
+        t.add("ab", 10);                                                     // 2 + 10 + 3 = 15
+        t.skip();
+        t.add("", 4);                                                        // 0 +  4 + 3 =  7
+        t.add("xyz", 0);                                                     // 3 +  0 + 3 =  6
+        t.skip();
+        CHECK(t.hdr == "abxyz");
+        CHECK(t.hdr_off == (V{0, 0, 2, 2, 2, 5, 5}));
+        CHECK(t.path_out == (V{0, 0, 15, 15, 22, 28, 28}));
+        const size_t before = stub.asked.size();
+        const PathsText::OnDevice d = t.upload(dev);
+        CHECK(d.total == 28 && std::memcmp(d.d_hdr, "abxyz", 5) == 0);
+        CHECK(std::memcmp(d.d_hdr_off, t.hdr_off.data(), 7 * 8) == 0 && std::memcmp(d.d_path_out, t.path_out.data(), 7 * 8) == 0);
+        CHECK(stub.asked.size() == before + 3 && stub.asked[before] == 5 && stub.asked[before + 1] == 56 && stub.asked[before + 2] == 56);
+    }
+    {   // only skipped paths: no byte
+        PathsText t;
+        t.skip();
+        t.skip();
+        CHECK(t.upload(dev).total == 0 && t.hdr_off == (V{0, 0, 0}) && t.path_out == (V{0, 0, 0}));
+    }
+    stub.fail_malloc = 2;                                                    // the names of what does not fit
+    std::string said;
+    try { DeviceScope small(ctx, no_room_does_not_fit); PathsText t; t.add("h", 1); t.upload(small); } catch (const DeviceNoRoom &e) { said = e.what(); }
+    CHECK(said == "the headers' offsets (16 bytes) does not fit the device: out of memory (stub)");
+}
+
+// output_windows.hpp: files that get their names only when all are complete
+void test_pending_outputs(const std::string &dir)
+{
+    const std::string a = dir + "/pending_a", b = dir + "/pending_b", blocked = dir + "/pending_dir";
+    {   // one file
+        PendingOutputs o;
+        std::FILE *f = o.open(a);
+        CHECK(f != nullptr && o.files.back().name == a + ".tmp" && o.files.back().path == a);
+        CHECK(std::fputs("one", f) >= 0 && exists(a + ".tmp") && !exists(a));
+        CHECK(o.commit());
+        CHECK(o.files.back().f == nullptr && o.files.back().name == a);
+    }
+    CHECK(file_bytes(a) == "one" && !exists(a + ".tmp"));                    // (and the destructor removed nothing)
+    {   // two files: closed, something else written, renamed (the order of readqc's reports)
+        PendingOutputs o;
+        std::fputs("first", o.open(a));
+        std::fputs("second", o.open(b));
+        CHECK(o.close() == nullptr && file_bytes(a) == "one" && file_bytes(a + ".tmp") == "first" && !exists(b));
+        CHECK(o.close() == nullptr);                                         // (nothing is closed twice)
+        CHECK(o.rename() == nullptr);
+    }
+    CHECK(file_bytes(a) == "first" && file_bytes(b) == "second" && !exists(a + ".tmp") && !exists(b + ".tmp"));
+    std::remove(a.c_str());
+    std::remove(b.c_str());
+    {   // left before the commit: every temporary goes, no file gets its name
+        PendingOutputs o;
+        std::fputs("x", o.open(a));
+        std::fputs("y", o.open(b));
+        CHECK(exists(a + ".tmp") && exists(b + ".tmp"));
+    }
+    CHECK(!exists(a) && !exists(b) && !exists(a + ".tmp") && !exists(b + ".tmp"));
+    {   // a temporary that cannot be opened: the sentence names it, the one before it goes
+        std::string said;
+        try {
+            PendingOutputs o;
+            o.open(a);
+            o.open(dir + "/no_such_directory/out");
+        } catch (const Failure &e) { said = e.what(); }
+        CHECK(said == "cannot write " + dir + "/no_such_directory/out.tmp" && !exists(a + ".tmp"));
+    }
+    CHECK(::mkdir(blocked.c_str(), 0700) == 0);
+    {   // the second rename fails (its target is a directory): failure is reported with the temporary's name, both temporaries are gone
+        PendingOutputs o;
+        std::fputs("x", o.open(a));
+        std::fputs("y", o.open(blocked));
+        CHECK(o.close() == nullptr);
+        const std::string *bad = o.rename();
+        CHECK(bad != nullptr && *bad == blocked + ".tmp");
+    }
+    CHECK(!exists(a + ".tmp") && !exists(blocked + ".tmp") && file_bytes(a) == "x");           // (the first had its name already)
+    std::remove(a.c_str());
+    {
+        PendingOutputs o;
+        std::fputs("x", o.open(a));
+        std::fputs("y", o.open(blocked));
+        CHECK(!o.commit());
+    }
+    CHECK(!exists(a + ".tmp") && !exists(blocked + ".tmp"));
+    std::remove(a.c_str());
+    {   // in place: the file exists, empty, from the start, and stays when the run is left early
+        PendingOutputs o;
+        o.open(a, true);
+        CHECK(o.files.back().name == a && exists(a) && !exists(a + ".tmp"));
+    }
+    CHECK(exists(a) && file_bytes(a).empty());
+    {   // ... and a commit closes it and renames nothing
+        PendingOutputs o;
+        std::fputs("whole", o.open(a, true));
+        CHECK(o.commit() && o.files.back().f == nullptr);
+    }
+    CHECK(file_bytes(a) == "whole");
+    if (std::FILE *full = std::fopen("/dev/full", "wb")) {                   // a file that takes no byte: close names it
+        std::fclose(full);
+        PendingOutputs o;
+        std::fputs("x", o.open(a));
+        std::fputs("lost", o.open("/dev/full", true));
+        const std::string *bad = o.close();
+        CHECK(bad != nullptr && *bad == "/dev/full" && o.files[0].f == nullptr && o.files[1].f == nullptr);       // (both are closed all the same)
+    }
+    CHECK(!exists(a + ".tmp"));
+}
+
+// fasta_device.hpp: the records come to the host once, and only when a flag is set
+void test_duplicates()
+{
+    std::vector<palace_fasta_rec> recs(5);
+    for (size_t k = 0; k < recs.size(); k++) recs[k] = palace_fasta_rec{static_cast<int64_t>(10 * k), static_cast<int64_t>(k + 1), 0, 0, 0, 0};
+    const char *text = "the text";
+    struct Seen { size_t k; int64_t name_off, name_len; const char *text; };
+    std::vector<Seen> seen;
+    auto note = [&](size_t k, const palace_fasta_rec &r, const char *t) { seen.push_back(Seen{k, r.name_off, r.name_len, t}); };
+    stub.reset();
+    for_each_duplicate(ctx, std::vector<uint8_t>{}, recs.data(), text, note);
+    for_each_duplicate(ctx, std::vector<uint8_t>{0, 0, 0, 0, 0}, recs.data(), text, note);
+    CHECK(seen.empty() && stub.copies_back == 0);
+    for_each_duplicate(ctx, std::vector<uint8_t>{1, 0, 0, 0, 1}, recs.data(), text, note);
+    CHECK(stub.copies_back == 1 && seen.size() == 2);
+    CHECK(seen.size() == 2 && seen[0].k == 0 && seen[0].name_off == 0 && seen[0].name_len == 1 && seen[0].text == text);
+    CHECK(seen.size() == 2 && seen[1].k == 4 && seen[1].name_off == 40 && seen[1].name_len == 5 && seen[1].text == text);
+    seen.clear();
+    for_each_duplicate(ctx, std::vector<uint8_t>{0, 0, 1, 0, 0}, recs.data(), text, note);
+    CHECK(stub.copies_back == 2 && seen.size() == 1 && seen[0].k == 2 && seen[0].name_off == 20);
+    bool stopped = false;                                                    // a tool that faults at the first one sees no second
+    seen.clear();
+    try {
+        for_each_duplicate(ctx, std::vector<uint8_t>{0, 1, 1, 0, 0}, recs.data(), text, [&](size_t k, const palace_fasta_rec &r, const char *t) {
+            note(k, r, t);
+            line_fault("a.fasta", line_of("x\ny\nz", 4), "twice");
+        });
+    } catch (const Failure &e) { stopped = std::string(e.what()) == "a.fasta: line 3: twice"; }
+    CHECK(stopped && seen.size() == 1 && seen[0].k == 1);
+    CHECK(line_of("x\ny\nz", 0) == 1 && line_of("x\ny\nz", 1) == 1 && line_of("x\ny\nz", 2) == 2);
+}
+
+// device_scope.hpp: the two sentences of a text input
+void test_text_input(const std::string &dir)
+{
+    std::string said;
+    MappedText t;
+    try { open_text(t, dir + "/missing"); } catch (const Failure &e) { said = e.what(); }
+    CHECK(said == "cannot open " + dir + "/missing");
+    open_text(t, dir + "/big");                                              // (test_mapped_file wrote it)
+    CHECK(t.size == 70000);
+    said.clear();
+    try { line_fault("f.txt", 12, "no good"); } catch (const Failure &e) { said = e.what(); }
+    CHECK(said == "f.txt: line 12: no good");
+}
+
 void test_member_arithmetic()
 {
     const uint64_t T = 0xff00;
@@ -456,6 +640,10 @@ int main(int argc, char **argv)
     test_clock();
     test_mapped_file(argv[1]);
     test_windows(argv[1]);
+    test_paths_text();
+    test_pending_outputs(argv[1]);
+    test_duplicates();
+    test_text_input(argv[1]);
     test_member_arithmetic();
     test_stored_member();
     std::printf("%s %d\n", failed ? "failed" : "ok", checks);

@@ -17,7 +17,6 @@
 #include "../../include/palace_hip.h"
 #include "device_pick.hpp"
 #include "device_scope.hpp"
-#include "fast_exit.hpp"
 #include "fasta_device.hpp"
 #include "fastx.hpp"
 #include "output_windows.hpp"
@@ -29,46 +28,7 @@ namespace {
 
 using palace_host::Failure;
 using palace_host::DeviceScope;
-using palace_host::fasta_fault_text;
-
-// the assembly on the device: text, index, names
-struct Assembly {
-    palace_ctx *ctx;
-    std::string path;
-    palace_host::MappedText text;
-    DeviceScope dev;
-    palace_host::FastaNamesHandle names;
-    const uint8_t *d_text = nullptr;
-    palace_fasta_rec *d_recs = nullptr;
-    int64_t n_records = 0;
-
-    Assembly(palace_ctx *c, const std::string &fasta, palace_host::Trace &tr) : ctx(c), path(fasta), dev(c, palace_host::no_room_does_not_fit), names(c)
-    {
-        try { text.open(fasta); }
-        catch (const std::exception &) { throw Failure("cannot open " + fasta); }
-        tr.lap("FASTA read");
-        const int64_t n = static_cast<int64_t>(text.size);
-        d_text = dev.upload(text.bytes(), text.size, "the FASTA is read on the device and has no other path: it");
-        tr.lap("FASTA uploaded");
-        const palace_host::FastaIndex ix = palace_host::index_fasta(ctx, dev, d_text, n, "the FASTA's index");
-        if (ix.st.error) throw Failure(fasta + ": line " + std::to_string(ix.st.bad_line) + ": " + fasta_fault_text(ix.st.error));
-        d_recs = ix.d_recs;
-        n_records = ix.st.n_records;
-        tr.lap("FASTA indexed");
-        const std::vector<uint8_t> h_dup = palace_host::hash_names(ctx, dev, d_text, d_recs, n_records, names);
-        size_t k = 0;
-        for (; k < h_dup.size() && !h_dup[k]; k++) {}
-        if (k < h_dup.size()) {                                             // (rare: the records come to the host only to name them)
-            std::vector<palace_fasta_rec> recs(h_dup.size());
-            HIP_OK(palace_d2h(ctx, recs.data(), d_recs, recs.size() * sizeof(palace_fasta_rec)));
-            for (; k < h_dup.size(); k++)
-                if (h_dup[k])
-                    std::fprintf(stderr, "make_fa_from_path: warning: %s: sequence name '%.*s' appears again in record %zu: the first one is used\n", fasta.c_str(),
-                                 static_cast<int>(recs[k].name_len), text.data + recs[k].name_off, k + 1);
-        }
-        tr.lap("names hashed");
-    }
-};
+using palace_host::Assembly;
 
 struct Job { std::string paths, out, mode; };
 
@@ -76,25 +36,27 @@ struct Job { std::string paths, out, mode; };
 void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly> &assembly, const Job &job, palace_host::Trace &tr)
 {
     std::fputs("make_fa_from_path.py running\n", stdout);
-    if (!assembly) assembly = std::make_unique<Assembly>(ctx, fasta, tr);
+    if (!assembly) {
+        assembly = std::make_unique<Assembly>(ctx, fasta);
+        tr.lap("FASTA read");
+        assembly->load(tr, [&](size_t k, const palace_fasta_rec &r, const char *text) {
+            std::fprintf(stderr, "make_fa_from_path: warning: %s: sequence name '%.*s' appears again in record %zu: the first one is used\n", fasta.c_str(),
+                         static_cast<int>(r.name_len), text + r.name_off, k + 1);
+        });
+    }
     const Assembly &as = *assembly;
     palace_host::MappedText ptext;
-    try { ptext.open(job.paths); }
-    catch (const std::exception &) { throw Failure("cannot open " + job.paths); }
-    std::FILE *out = std::fopen(job.out.c_str(), "wb");
-    if (!out) throw Failure("cannot write " + job.out);
-    palace_host::FileGuard closer{out};
+    palace_host::open_text(ptext, job.paths);
+    palace_host::PendingOutputs outputs;
+    std::FILE *out = outputs.open(job.out, true);
     const palace_host::PathTokens tk = palace_host::split_paths(ptext.data, ptext.size);
     const int64_t n_tok = static_cast<int64_t>(tk.tokens()), n_paths = static_cast<int64_t>(tk.lines());
     tr.lap("paths split");
 
     DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
-    const uint8_t *d_tok = dev.upload(reinterpret_cast<const uint8_t *>(tk.clean.data()), tk.clean.size(), "the tokens");
-    const int64_t *d_tok_off = dev.upload(tk.clean_off.data(), tk.clean_off.size(), "the tokens' offsets");
-    int32_t *d_code = dev.array<int32_t>(static_cast<size_t>(n_tok), "the tokens' records");
-    HIP_OK(palace_path_resolve(ctx, as.names.h, d_tok, d_tok_off, n_tok, d_code));
-    std::vector<int32_t> code(static_cast<size_t>(n_tok));
-    if (n_tok) HIP_OK(palace_d2h(ctx, code.data(), d_code, code.size() * sizeof(int32_t)));
+    const palace_host::Resolved res = palace_host::resolve(ctx, dev, as.names.h, tk.clean, tk.clean_off, palace_host::kTokensWhat, true);
+    const std::vector<int32_t> &code = res.code;
+    int32_t *const d_code = res.d_code;
     for (int64_t l = 0; l < n_paths; l++)
         for (int64_t t = tk.line_tok[static_cast<size_t>(l)]; t < tk.line_tok[static_cast<size_t>(l) + 1]; t++) {
             const int32_t c = code[static_cast<size_t>(t)];
@@ -120,29 +82,23 @@ void run_job(palace_ctx *ctx, const std::string &fasta, std::unique_ptr<Assembly
     HIP_OK(palace_path_fasta_lengths(ctx, as.d_recs, d_code, n_tok, d_path_off, n_paths, d_cum, d_len));
     std::vector<int64_t> len(static_cast<size_t>(n_paths));
     if (n_paths) HIP_OK(palace_d2h(ctx, len.data(), d_len, len.size() * sizeof(int64_t)));
-    std::string hdr;
-    std::vector<int64_t> hdr_off{0}, path_out{0};
+    palace_host::PathsText plan;
     for (int64_t l = 0; l < n_paths; l++) {
-        if (job.mode == "0") hdr += "res_" + std::to_string(tk.line_index[static_cast<size_t>(l)] + 1) + "_" + std::to_string(len[static_cast<size_t>(l)]);
-        else hdr.append(tk.raw, static_cast<size_t>(tk.raw_off[static_cast<size_t>(tk.line_tok[static_cast<size_t>(l)])]),
-                        static_cast<size_t>(tk.raw_off[static_cast<size_t>(tk.line_tok[static_cast<size_t>(l) + 1])] - tk.raw_off[static_cast<size_t>(tk.line_tok[static_cast<size_t>(l)])]));
-        path_out.push_back(path_out.back() + (static_cast<int64_t>(hdr.size()) - hdr_off.back()) + len[static_cast<size_t>(l)] + 3);
-        hdr_off.push_back(static_cast<int64_t>(hdr.size()));
+        const size_t t0 = static_cast<size_t>(tk.line_tok[static_cast<size_t>(l)]), t1 = static_cast<size_t>(tk.line_tok[static_cast<size_t>(l) + 1]);
+        if (job.mode == "0") plan.add("res_" + std::to_string(tk.line_index[static_cast<size_t>(l)] + 1) + "_" + std::to_string(len[static_cast<size_t>(l)]), len[static_cast<size_t>(l)]);
+        else plan.add(std::string_view(tk.raw).substr(static_cast<size_t>(tk.raw_off[t0]), static_cast<size_t>(tk.raw_off[t1] - tk.raw_off[t0])), len[static_cast<size_t>(l)]);
     }
-    const int64_t total = path_out.back();
-    const uint8_t *d_hdr = dev.upload(reinterpret_cast<const uint8_t *>(hdr.data()), hdr.size(), "the headers");
-    const int64_t *d_hdr_off = dev.upload(hdr_off.data(), hdr_off.size(), "the headers' offsets");
-    const int64_t *d_path_out = dev.upload(path_out.data(), path_out.size(), "the paths' places");
+    const palace_host::PathsText::OnDevice pd = plan.upload(dev);
+    const int64_t total = pd.total;
     tr.lap("lengths and headers");
 
     if (total) {                                                             // the output text, in windows (output_windows.hpp)
         palace_host::WindowWriter windows(ctx, dev, "PALACE_PATHFA_WINDOW", total);
         windows.write(total, out, job.out, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
-            HIP_OK(palace_path_fasta_write(ctx, as.d_text, as.d_recs, d_code, d_cum, d_path_off, n_paths, d_hdr, d_hdr_off, d_path_out, lo, hi, d_win));
+            HIP_OK(palace_path_fasta_write(ctx, as.d_text, as.d_recs, d_code, d_cum, d_path_off, n_paths, pd.d_hdr, pd.d_hdr_off, pd.d_path_out, lo, hi, d_win));
         });
     }
-    closer.release();
-    if (std::fclose(out) != 0) throw Failure("cannot write " + job.out);
+    if (!outputs.commit()) throw Failure("cannot write " + job.out);
     tr.lap("output written");
 }
 
@@ -159,16 +115,7 @@ int main(int argc, char **argv)
                    "       make_fa_from_path --batch <list of '<paths_file> <output_file> <mode>' lines> <fasta_file>\n", stderr);
         return 1;
     }
-    palace_host::FastExit fast_exit = palace_host::fast_exit_begin();   // from here on this is the worker process (fast_exit.hpp)
-    const int device = palace_host::pick_device();                       // PALACE_DEVICE (device_pick.hpp): before anything touches HIP
-    palace_host::Trace tr("make_fa_from_path");
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
-        std::fprintf(stderr, "make_fa_from_path: no GPU device to work on (%s); there is no CPU path\n", palace_last_error());
-        return 1;
-    }
-    tr.lap("device up");
-    try {
+    return palace_host::device_tool("make_fa_from_path", [&](palace_ctx *ctx, palace_host::Trace &tr) {
         if (!list.empty()) {
             std::ifstream lf(list);
             if (!lf) throw Failure("cannot open batch list " + list);
@@ -182,10 +129,5 @@ int main(int argc, char **argv)
         }
         std::unique_ptr<Assembly> assembly;
         for (const Job &j : jobs) run_job(ctx, fasta, assembly, j, tr);
-    } catch (const std::exception &e) {
-        std::fflush(stdout);
-        std::fprintf(stderr, "make_fa_from_path: %s\n", e.what());
-        return 1;
-    }
-    fast_exit.done(0);          // outputs are complete and closed: the caller goes on, the teardown happens behind it
+    });
 }

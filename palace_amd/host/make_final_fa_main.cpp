@@ -16,7 +16,6 @@
 #include "../../include/palace_hip.h"
 #include "device_pick.hpp"
 #include "device_scope.hpp"
-#include "fast_exit.hpp"
 #include "fasta_device.hpp"
 #include "fastx.hpp"
 #include "final_tokens.hpp"
@@ -29,6 +28,7 @@ namespace {
 using palace_host::DeviceScope;
 using palace_host::Failure;
 using palace_host::fsv;
+using palace_host::line_fault;
 
 constexpr int64_t kSepLen = 50;
 constexpr int32_t kSepByte = 'N';
@@ -72,41 +72,20 @@ bool parse_args(int argc, char **argv, Args *a)
     return true;
 }
 
-[[noreturn]] void fault(const std::string &file, int64_t line, const std::string &reason)
-{
-    throw Failure(file + ": line " + std::to_string(line) + ": " + reason);
-}
-
-void open_text(palace_host::MappedText &t, const std::string &path)
-{
-    try { t.open(path); }
-    catch (const std::exception &) { throw Failure("cannot open " + path); }
-}
-
 // strings -> ids: one name table over the strings themselves, each followed by a '+' so that the bytes `S+` are at once record S
 // of the table's text and the token palace_path_resolve takes the name S from.  The id of a string is its first record.
 std::vector<int32_t> ids_of(palace_ctx *ctx, const std::vector<fsv> &strings)
 {
     std::string text;
-    std::vector<palace_fasta_rec> recs;
     std::vector<int64_t> off{0};
     for (const fsv s : strings) {
-        recs.push_back(palace_fasta_rec{static_cast<int64_t>(text.size()), static_cast<int64_t>(s.size()), 0, 0, 0, 0});
         text.append(s);
         text.push_back('+');
         off.push_back(static_cast<int64_t>(text.size()));
     }
-    std::vector<int32_t> id(strings.size());
-    if (strings.empty()) return id;
+    if (strings.empty()) return {};
     DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
-    const uint8_t *d_text = dev.upload(reinterpret_cast<const uint8_t *>(text.data()), text.size(), "the node names");
-    const palace_fasta_rec *d_recs = dev.upload(recs.data(), recs.size(), "the node names' records");
-    const int64_t *d_off = dev.upload(off.data(), off.size(), "the node names' offsets");
-    int32_t *d_code = dev.array<int32_t>(strings.size(), "the node ids");
-    palace_host::FastaNamesHandle names(ctx);
-    HIP_OK(palace_fasta_names_create(ctx, d_text, d_recs, static_cast<int64_t>(recs.size()), nullptr, &names.h));
-    HIP_OK(palace_path_resolve(ctx, names.h, d_text, d_off, static_cast<int64_t>(strings.size()), d_code));
-    HIP_OK(palace_d2h(ctx, id.data(), d_code, id.size() * sizeof(int32_t)));
+    std::vector<int32_t> id = palace_host::resolve(ctx, dev, nullptr, text, off, {"the node names", "the node names' offsets", "the node ids", "the node names' records"}, true).code;
     for (int32_t &c : id) {
         if (c < 0 || (c & 3)) throw Failure("internal: a node name did not resolve to itself");
         c >>= 2;
@@ -116,39 +95,25 @@ std::vector<int32_t> ids_of(palace_ctx *ctx, const std::vector<fsv> &strings)
 
 void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
 {
-    palace_host::MappedText ptext, gtext, ftext;
-    open_text(ptext, a.paths);
-    open_text(gtext, a.graph);
-    open_text(ftext, a.fasta);
+    palace_host::MappedText ptext, gtext;
+    palace_host::open_text(ptext, a.paths);
+    palace_host::open_text(gtext, a.graph);
+    palace_host::Assembly as(ctx, a.fasta);
     tr.lap("files read");
     const palace_host::FinalGraph g = palace_host::final_graph(gtext.data, gtext.size);
-    if (g.fault.line) fault(a.graph, g.fault.line, g.fault.reason);
+    if (g.fault.line) line_fault(a.graph, g.fault.line, g.fault.reason);
     const palace_host::FinalPaths pt = palace_host::final_paths(ptext.data, ptext.size);
-    if (pt.fault.line) fault(a.paths, pt.fault.line, pt.fault.reason);
+    if (pt.fault.line) line_fault(a.paths, pt.fault.line, pt.fault.reason);
     const int64_t n_tok = static_cast<int64_t>(pt.tokens.size()), n_paths = static_cast<int64_t>(pt.paths());
     const size_t n_nodes = g.nodes.size();
     tr.lap("tokens split");
 
     // the assembly: text, index, names; two records of one name are a fault
-    DeviceScope as(ctx, palace_host::no_room_does_not_fit);
-    palace_host::FastaNamesHandle names(ctx);
-    const int64_t fn = static_cast<int64_t>(ftext.size);
-    const uint8_t *d_text = as.upload(ftext.bytes(), ftext.size, "the FASTA is read on the device and has no other path: it");
-    const palace_host::FastaIndex ix = palace_host::index_fasta(ctx, as, d_text, fn, "the FASTA's index");
-    if (ix.st.error) fault(a.fasta, ix.st.bad_line, palace_host::fasta_fault_text(ix.st.error));
-    palace_fasta_rec *const d_recs = ix.d_recs;
-    {
-        const std::vector<uint8_t> dup = palace_host::hash_names(ctx, as, d_text, d_recs, ix.st.n_records, names);
-        for (size_t k = 0; k < dup.size(); k++)
-            if (dup[k]) {                                                    // (rare: the record comes to the host only to be named)
-                palace_fasta_rec r;
-                HIP_OK(palace_d2h(ctx, &r, d_recs + k, sizeof r));
-                int64_t line = 1;
-                for (int64_t i = 0; i < r.name_off; i++) line += ftext.data[i] == '\n';
-                fault(a.fasta, line, "sequence name '" + std::string(ftext.data + r.name_off, static_cast<size_t>(r.name_len)) + "' appears a second time");
-            }
-    }
-    tr.lap("FASTA indexed, names hashed");
+    as.load(tr, [&](size_t, const palace_fasta_rec &r, const char *text) {
+        line_fault(a.fasta, palace_host::line_of(text, r.name_off), "sequence name '" + std::string(text + r.name_off, static_cast<size_t>(r.name_len)) + "' appears a second time");
+    });
+    const uint8_t *const d_text = as.d_text;
+    palace_fasta_rec *const d_recs = as.d_recs;
 
     // ids of the JUNC nodes, the tokens and the tokens' bases
     std::vector<fsv> strings;
@@ -183,20 +148,13 @@ void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
     tr.lap("cycles decided");
 
     // the tokens in the assembly
-    std::vector<int32_t> code(static_cast<size_t>(n_tok));
-    {
-        std::string q;
-        std::vector<int64_t> q_off{0};
-        for (int64_t t = 0; t < n_tok; t++) {
-            q += palace_host::final_query(pt.tokens.at(static_cast<size_t>(t)));
-            q_off.push_back(static_cast<int64_t>(q.size()));
-        }
-        const uint8_t *d_q = dev.upload(reinterpret_cast<const uint8_t *>(q.data()), q.size(), "the tokens");
-        const int64_t *d_q_off = dev.upload(q_off.data(), q_off.size(), "the tokens' offsets");
-        int32_t *d_code = dev.array<int32_t>(static_cast<size_t>(n_tok), "the tokens' records");
-        HIP_OK(palace_path_resolve(ctx, names.h, d_q, d_q_off, n_tok, d_code));
-        if (n_tok) HIP_OK(palace_d2h(ctx, code.data(), d_code, code.size() * sizeof(int32_t)));
+    std::string q;
+    std::vector<int64_t> q_off{0};
+    for (int64_t t = 0; t < n_tok; t++) {
+        q += palace_host::final_query(pt.tokens.at(static_cast<size_t>(t)));
+        q_off.push_back(static_cast<int64_t>(q.size()));
     }
+    const std::vector<int32_t> code = palace_host::resolve(ctx, dev, as.names.h, q, q_off, palace_host::kTokensWhat, true).code;
     // the output's paths: the cycles, cut, in file order, then the others, whole; a token whose name is no record is warned about
     std::vector<int32_t> out_code;
     std::vector<int64_t> out_off{0};
@@ -231,41 +189,26 @@ void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
     HIP_OK(palace_final_fasta_lengths(ctx, d_recs, d_out_code, n_out_tok, d_out_off, n_paths, kSepLen, d_cum, d_len));
     std::vector<int64_t> len(static_cast<size_t>(n_paths));
     if (n_paths) HIP_OK(palace_d2h(ctx, len.data(), d_len, len.size() * sizeof(int64_t)));
-    std::string hdr;
-    std::vector<int64_t> hdr_off{0}, path_out{0};
+    palace_host::PathsText plan;
     int64_t count = 0;
     for (int64_t p = 0; p < n_paths; p++) {
-        int64_t bytes = 0;
-        if (len[static_cast<size_t>(p)] > 0) {                              // a path without sequence is not written and takes no number
-            const size_t before = hdr.size();
-            hdr += a.prefix + "_phage_" + std::to_string(++count) + (out_cycle[static_cast<size_t>(p)] ? "_cycle" : "_linear");
-            bytes = static_cast<int64_t>(hdr.size() - before) + len[static_cast<size_t>(p)] + 3;
-        }
-        hdr_off.push_back(static_cast<int64_t>(hdr.size()));
-        path_out.push_back(path_out.back() + bytes);
+        if (len[static_cast<size_t>(p)] > 0)                                // a path without sequence is not written and takes no number
+            plan.add(a.prefix + "_phage_" + std::to_string(++count) + (out_cycle[static_cast<size_t>(p)] ? "_cycle" : "_linear"), len[static_cast<size_t>(p)]);
+        else plan.skip();
     }
-    const int64_t total = path_out.back();
-    const uint8_t *d_hdr = dev.upload(reinterpret_cast<const uint8_t *>(hdr.data()), hdr.size(), "the headers");
-    const int64_t *d_hdr_off = dev.upload(hdr_off.data(), hdr_off.size(), "the headers' offsets");
-    const int64_t *d_path_out = dev.upload(path_out.data(), path_out.size(), "the paths' places");
+    const palace_host::PathsText::OnDevice pd = plan.upload(dev);
     tr.lap("lengths and headers");
 
     // windows of the output text: window w is computed and copied back while window w - 1 goes to the file
-    const std::string tmp = a.out + ".tmp";
-    std::FILE *out = std::fopen(tmp.c_str(), "wb");
-    if (!out) throw Failure("cannot write " + tmp);
-    palace_host::FileGuard closer{out, tmp.c_str()};
-    if (total) {
-        palace_host::WindowWriter windows(ctx, dev, "PALACE_FINALFA_WINDOW", total);
-        windows.write(total, out, tmp, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
-            HIP_OK(palace_final_fasta_write(ctx, d_text, d_recs, d_out_code, d_cum, d_out_off, n_paths, d_hdr, d_hdr_off, d_path_out, kSepByte, lo, hi, d_win));
+    palace_host::PendingOutputs outputs;
+    std::FILE *out = outputs.open(a.out);
+    if (pd.total) {
+        palace_host::WindowWriter windows(ctx, dev, "PALACE_FINALFA_WINDOW", pd.total);
+        windows.write(pd.total, out, a.out + ".tmp", [&](int64_t lo, int64_t hi, uint8_t *d_win) {
+            HIP_OK(palace_final_fasta_write(ctx, d_text, d_recs, d_out_code, d_cum, d_out_off, n_paths, pd.d_hdr, pd.d_hdr_off, pd.d_path_out, kSepByte, lo, hi, d_win));
         });
     }
-    closer.release();
-    if (std::fclose(out) != 0 || std::rename(tmp.c_str(), a.out.c_str()) != 0) {
-        std::remove(tmp.c_str());
-        throw Failure("cannot write " + a.out);
-    }
+    if (!outputs.commit()) throw Failure("cannot write " + a.out);
     tr.lap("output written");
     std::fprintf(stderr, "Total circular paths found: %lld\nTotal linear paths found: %lld\nFasta successfully written to: %s\n\n",
                  static_cast<long long>(n_cycle), static_cast<long long>(n_paths - n_cycle), a.out.c_str());
@@ -280,20 +223,5 @@ int main(int argc, char **argv)
         std::fputs("usage: make_final_fa [--trim_threshold N] [--min_cycle_length N] path_file graph_file edge_fasta out_fasta prefix\n", stderr);
         return 2;
     }
-    palace_host::FastExit fast_exit = palace_host::fast_exit_begin();   // from here on this is the worker process (fast_exit.hpp)
-    const int device = palace_host::pick_device();                       // PALACE_DEVICE (device_pick.hpp): before anything touches HIP
-    palace_host::Trace tr("make_final_fa");
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
-        std::fprintf(stderr, "make_final_fa: no GPU device to work on (%s); there is no CPU path\n", palace_last_error());
-        return 1;
-    }
-    tr.lap("device up");
-    try {
-        run(ctx, a, tr);
-    } catch (const std::exception &e) {
-        std::fprintf(stderr, "make_final_fa: %s\n", e.what());
-        return 1;
-    }
-    fast_exit.done(0);          // the output is complete and renamed: the caller goes on, the teardown happens behind it
+    return palace_host::device_tool("make_final_fa", [&](palace_ctx *ctx, palace_host::Trace &tr) { run(ctx, a, tr); });
 }

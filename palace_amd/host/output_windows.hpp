@@ -1,10 +1,14 @@
 // An output text that is made on the device goes to its file in windows: window w is computed and copied back while window w - 1 is
-// written (make_fa_from_path, make_final_fa, readqc).  Two device windows, two page-locked buffers, the library's marks 0 and 1.
-// Nothing here knows what the text is: the tool's `produce` makes the bytes [lo, hi) of it in the device window it is handed.
+// written (WindowWriter: make_fa_from_path, make_final_fa, filter_result, readqc).  Two device windows, two page-locked buffers, the
+// library's marks 0 and 1.  Nothing there knows what the text is: the tool's `produce` makes the bytes [lo, hi) of it in the device
+// window it is handed.  Beside it, what those tools and split_fastg share around the text: PendingOutputs, the files that get their
+// names only when complete (all five), and PathsText, the headers and places of a text of paths (the three FASTA writers).
 #pragma once
 #include <cstdio>
 #include <cstdlib>
 #include <string>
+#include <string_view>
+#include <vector>
 
 #include "device_scope.hpp"
 
@@ -18,12 +22,73 @@ inline int64_t window_bytes(const char *env_name)
     return v > 0 ? static_cast<int64_t>(v) : (256ll << 20);
 }
 
-// an open file that is closed when the scope is left early -- and removed, where a path is given; release() before the regular fclose
-struct FileGuard {
-    std::FILE *f;
-    const char *remove_path = nullptr;
-    ~FileGuard() { if (f) { std::fclose(f); if (remove_path) std::remove(remove_path); } }
-    void release() { f = nullptr; }
+// The output files of a run.  A file is written as `<path>.tmp` and gets its name only when every file of the run is complete
+// (make_final_fa, filter_result, readqc) -- or, in place, under its own name, where the output exists, empty, from the start
+// (make_fa_from_path, split_fastg).  Leaving early closes what is open and removes every temporary; a file in place stays as it is.
+// The steps say which file failed and throw nothing: the sentence is the tool's.
+struct PendingOutputs {
+    struct File { std::string path, name; std::FILE *f; };      // name: what is open -- the temporary, or the path itself
+    std::vector<File> files;
+    PendingOutputs() = default;
+    PendingOutputs(const PendingOutputs &) = delete;
+    PendingOutputs &operator=(const PendingOutputs &) = delete;
+    ~PendingOutputs()
+    {
+        for (File &o : files) {
+            if (o.f) std::fclose(o.f);
+            if (o.name != o.path) std::remove(o.name.c_str());  // (renamed already: nothing to remove)
+        }
+    }
+    // the open file (files.back(), whose name is what a message calls it)
+    std::FILE *open(const std::string &path, bool in_place = false)
+    {
+        const std::string name = in_place ? path : path + ".tmp";
+        std::FILE *f = std::fopen(name.c_str(), "wb");
+        if (!f) throw Failure("cannot write " + name);
+        files.push_back(File{path, name, f});
+        return f;
+    }
+    // every file closed; the name of the first that could not be, or nullptr
+    const std::string *close()
+    {
+        const std::string *bad = nullptr;
+        for (File &o : files)
+            if (o.f) { if (std::fclose(o.f) != 0 && !bad) bad = &o.name; o.f = nullptr; }
+        return bad;
+    }
+    // every temporary to its path; the name of the first that could not be, or nullptr
+    const std::string *rename()
+    {
+        for (File &o : files)
+            if (o.name != o.path) { if (std::rename(o.name.c_str(), o.path.c_str()) != 0) return &o.name; o.name = o.path; }
+        return nullptr;
+    }
+    bool commit() { return !close() && !rename(); }
+};
+
+// The plan of an output text of paths (make_fa_from_path, make_final_fa, filter_result) as palace_path_fasta_write and
+// palace_final_fasta_write take it: the headers one behind the other, their offsets, and every path's place in the text -- a written
+// path takes its header, its sequence and 3 bytes, a skipped one none.  What the header is and when a path is skipped is the tool's.
+struct PathsText {
+    std::string hdr;
+    std::vector<int64_t> hdr_off{0}, path_out{0};
+    void add(std::string_view header, int64_t sequence_length)
+    {
+        hdr.append(header);
+        hdr_off.push_back(static_cast<int64_t>(hdr.size()));
+        path_out.push_back(path_out.back() + static_cast<int64_t>(header.size()) + sequence_length + 3);
+    }
+    void skip() { hdr_off.push_back(hdr_off.back()); path_out.push_back(path_out.back()); }
+    struct OnDevice { const uint8_t *d_hdr; const int64_t *d_hdr_off, *d_path_out; int64_t total; };
+    OnDevice upload(DeviceScope &scope) const
+    {
+        OnDevice d;
+        d.total = path_out.back();
+        d.d_hdr = scope.upload(reinterpret_cast<const uint8_t *>(hdr.data()), hdr.size(), "the headers");
+        d.d_hdr_off = scope.upload(hdr_off.data(), hdr_off.size(), "the headers' offsets");
+        d.d_path_out = scope.upload(path_out.data(), path_out.size(), "the paths' places");
+        return d;
+    }
 };
 
 struct WindowWriter {

@@ -25,7 +25,6 @@
 #include "../../include/palace_hip.h"
 #include "device_pick.hpp"
 #include "device_scope.hpp"
-#include "fast_exit.hpp"
 #include "mapped_file.hpp"
 #include "output_windows.hpp"
 #include "trace.hpp"
@@ -141,8 +140,7 @@ std::vector<uint8_t> inflate_on_host(const std::string &path, const uint8_t *fil
 DeviceText load_text(palace_ctx *ctx, DeviceScope &dev, const std::string &path, palace_host::Trace &tr)
 {
     palace_host::MappedText file;
-    try { file.open(path); }
-    catch (const std::exception &) { throw Failure("cannot open " + path); }
+    palace_host::open_text(file, path);
     DeviceText t;
     if (file.size >= 2 && file.bytes()[0] == 0x1f && file.bytes()[1] == 0x8b) {
         Grow g{ctx, &dev};
@@ -170,14 +168,9 @@ struct Lines { int64_t *d_start = nullptr; int64_t n_lines = 0, records = 0, bad
 Lines lines_and_records(palace_ctx *ctx, DeviceScope &dev, const DeviceText &t)
 {
     Lines l;
-    const size_t sb = palace_sam_scratch_bytes(t.n);
-    void *d_scratch = dev.alloc(sb, "the lines' scratch");
-    int64_t out[5];
-    HIP_OK(palace_sam_lines(ctx, t.d, t.n, d_scratch, sb, nullptr, 0, out));
-    l.n_lines = out[0];
-    l.d_start = dev.array<int64_t>(static_cast<size_t>(l.n_lines + 1), "the line starts");
-    HIP_OK(palace_sam_lines(ctx, t.d, t.n, d_scratch, sb, l.d_start, l.n_lines + 1, out));       // (its verdict is a SAM's: out[1 .. 4] mean nothing here)
-    dev.give_back(d_scratch);
+    const palace_host::TextLines tl = palace_host::text_lines(ctx, dev, t.d, t.n, "the line starts");       // (the verdict in tl.res is a SAM's: it means nothing here)
+    l.n_lines = tl.n_lines;
+    l.d_start = tl.d_start;
     int32_t *d_seq_len = dev.array<int32_t>(static_cast<size_t>(l.n_lines / 4), "the reads' lengths");
     int64_t v[3];
     HIP_OK(palace_fastq_records(ctx, t.d, l.d_start, l.n_lines, d_seq_len, v));
@@ -185,13 +178,6 @@ Lines lines_and_records(palace_ctx *ctx, DeviceScope &dev, const DeviceText &t)
     l.records = v[0]; l.bad_line = v[1]; l.code = static_cast<int32_t>(v[2]);
     return l;
 }
-
-// the temporaries of a run: removed unless it completes
-struct Outputs {
-    std::vector<std::string> tmp;
-    bool done = false;
-    ~Outputs() { if (!done) for (const std::string &p : tmp) std::remove(p.c_str()); }
-};
 
 void write_report(const Options &o, const int64_t *n)
 {
@@ -244,24 +230,17 @@ void run(palace_ctx *ctx, const Options &o, palace_host::Trace &tr)
     // windows of the output texts: window w is computed and copied back while window w - 1 goes to its file
     const int64_t total[2] = {n[PALACE_READQC_BYTES_1], n[PALACE_READQC_BYTES_2]};
     palace_host::WindowWriter windows(ctx, dev, "PALACE_READQC_WINDOW", total[0] > total[1] ? total[0] : total[1]);
-    Outputs outputs;
+    palace_host::PendingOutputs outputs;
     for (int k = 0; k < 2; k++) {
-        const std::string tmp = *outp[k] + ".tmp";
-        std::FILE *f = std::fopen(tmp.c_str(), "wb");
-        if (!f) throw Failure("cannot write " + tmp);
-        outputs.tmp.push_back(tmp);
-        palace_host::FileGuard closer{f};
-        windows.write(total[k], f, tmp, [&](int64_t lo, int64_t hi, uint8_t *d_win) {
+        std::FILE *f = outputs.open(*outp[k]);
+        windows.write(total[k], f, *outp[k] + ".tmp", [&](int64_t lo, int64_t hi, uint8_t *d_win) {
             HIP_OK(palace_readqc_write(ctx, text[k].d, lines[k].d_start, d_len[k], d_off[k], n_pairs, lo, hi, d_win));
         });
-        closer.release();
-        if (std::fclose(f) != 0) throw Failure("cannot write " + tmp);
     }
+    if (const std::string *bad = outputs.close()) throw Failure("cannot write " + *bad);
     tr.lap("outputs written");
     write_report(o, n);
-    for (int k = 0; k < 2; k++)
-        if (std::rename(outputs.tmp[static_cast<size_t>(k)].c_str(), outp[k]->c_str()) != 0) throw Failure("cannot rename " + outputs.tmp[static_cast<size_t>(k)]);
-    outputs.done = true;
+    if (const std::string *bad = outputs.rename()) throw Failure("cannot rename " + *bad);
     if (tr.on)
         std::fprintf(stderr, "[readqc] pairs %lld, kept %lld; text %lld + %lld B in, %lld + %lld B out; build %s\n", static_cast<long long>(n_pairs),
                      static_cast<long long>(n[PALACE_READQC_READS_AFTER] / 2), static_cast<long long>(text[0].n), static_cast<long long>(text[1].n),
@@ -309,20 +288,5 @@ int main(int argc, char **argv)
     if (o.in1.empty() || o.in2.empty() || o.out1.empty() || o.out2.empty()) return usage("-i, -I, -o and -O are required (paired input only)");
     if (ends_with(o.out1, ".gz") || ends_with(o.out2, ".gz")) return usage(".gz output is not written");
 
-    palace_host::FastExit fast_exit = palace_host::fast_exit_begin();   // from here on this is the worker process (fast_exit.hpp)
-    const int device = palace_host::pick_device();                       // PALACE_DEVICE (device_pick.hpp): before anything touches HIP
-    palace_host::Trace tr("readqc");
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
-        std::fprintf(stderr, "readqc: no GPU device to work on (%s); there is no CPU path\n", palace_last_error());
-        return 1;
-    }
-    tr.lap("device up");
-    try {
-        run(ctx, o, tr);
-    } catch (const std::exception &e) {
-        std::fprintf(stderr, "readqc: %s\n", e.what());
-        return 1;
-    }
-    fast_exit.done(0);          // outputs are complete and closed: the caller goes on, the teardown happens behind it
+    return palace_host::device_tool("readqc", [&](palace_ctx *ctx, palace_host::Trace &tr) { run(ctx, o, tr); });
 }

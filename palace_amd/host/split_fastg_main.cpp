@@ -17,7 +17,6 @@
 #include "../../include/palace_hip.h"
 #include "device_pick.hpp"
 #include "device_scope.hpp"
-#include "fast_exit.hpp"
 #include "fasta_device.hpp"
 #include "fastx.hpp"
 #include "output_windows.hpp"
@@ -64,22 +63,17 @@ void write_fai(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d
     HIP_OK(palace_fai_rows_plan(ctx, d_recs, d_skip, n_records, d_off, &bytes));
     uint8_t *d_rows = dev.array<uint8_t>(static_cast<size_t>(bytes), "the index rows");
     HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off, d_rows));
-    std::FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) throw Failure("cannot write " + path);
-    palace_host::FileGuard closer{f};
-    to_file(ctx, d_rows, bytes, f, path);
-    closer.release();
-    if (std::fclose(f) != 0) throw Failure("cannot write " + path);
+    palace_host::PendingOutputs outputs;
+    to_file(ctx, d_rows, bytes, outputs.open(path, true), path);
+    if (!outputs.commit()) throw Failure("cannot write " + path);
 }
 
 void run(palace_ctx *ctx, const std::string &graph, const std::string &output, bool fai, palace_host::Trace &tr)
 {
     palace_host::MappedText text;
-    try { text.open(graph); }
-    catch (const std::exception &) { throw Failure("cannot open " + graph); }
-    std::FILE *out = std::fopen(output.c_str(), "wb");                       // (exists, empty, from here on: as the script's)
-    if (!out) throw Failure("cannot write " + output);
-    palace_host::FileGuard closer{out};
+    palace_host::open_text(text, graph);
+    palace_host::PendingOutputs outputs;
+    std::FILE *out = outputs.open(output, true);                             // (exists, empty, from here on: as the script's)
     tr.lap("FASTG read");
     const int64_t n = static_cast<int64_t>(text.size);
     DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
@@ -97,7 +91,7 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     HIP_OK(palace_fastg_derive(ctx, d_text, n, d_recs, n_records, d_name_recs, d_primed, &fg));
     tr.lap("names derived, text checked");
     if (fg.error && (!st.error || fg.bad_line < st.bad_line || (fg.bad_line == st.bad_line && fg.error < st.error))) st = fg;
-    if (st.error) throw Failure(graph + ": line " + std::to_string(st.bad_line) + ": " + fault_text(st.error));
+    if (st.error) palace_host::line_fault(graph, st.bad_line, fault_text(st.error));
 
     palace_host::FastaNamesHandle names(ctx);
     uint8_t *d_dup = dev.array<uint8_t>(nr, "the duplicate flags");
@@ -113,8 +107,7 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     tr.lap("output gathered");
     to_file(ctx, d_out, total, out, output);
     dev.give_back(d_out);
-    closer.release();
-    if (std::fclose(out) != 0) throw Failure("cannot write " + output);
+    if (!outputs.commit()) throw Failure("cannot write " + output);
     tr.lap("output written");
     if (!fai) return;
 
@@ -125,16 +118,10 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     write_fai(ctx, d_text, d_recs, d_skip, n_records, graph + ".fai");
     std::vector<uint8_t> skip(nr);
     if (n_records) HIP_OK(palace_d2h(ctx, skip.data(), d_skip, skip.size()));
-    size_t k = 0;
-    for (; k < skip.size() && !skip[k]; k++) {}
-    if (k < skip.size()) {                                                   // (rare: the records come to the host only to name them)
-        std::vector<palace_fasta_rec> recs(skip.size());
-        HIP_OK(palace_d2h(ctx, recs.data(), d_recs, recs.size() * sizeof(palace_fasta_rec)));
-        for (; k < skip.size(); k++)
-            if (skip[k])
-                std::fprintf(stderr, "split_fastg: warning: %s: sequence name '%.*s' appears again in record %zu: left out of %s.fai\n", graph.c_str(),
-                             static_cast<int>(recs[k].name_len), text.data + recs[k].name_off, k + 1, graph.c_str());
-    }
+    palace_host::for_each_duplicate(ctx, skip, d_recs, text.data, [&](size_t k, const palace_fasta_rec &r, const char *t) {
+        std::fprintf(stderr, "split_fastg: warning: %s: sequence name '%.*s' appears again in record %zu: left out of %s.fai\n", graph.c_str(),
+                     static_cast<int>(r.name_len), t + r.name_off, k + 1, graph.c_str());
+    });
     tr.lap("index rows written");
 }
 
@@ -185,20 +172,5 @@ int main(int argc, char **argv)
         output = default_output(graph);
         if (output.empty()) return usage("without -o the graph has to be named X.fastg (the output is then X.nodes.fasta)");
     }
-    palace_host::FastExit fast_exit = palace_host::fast_exit_begin();   // from here on this is the worker process (fast_exit.hpp)
-    const int device = palace_host::pick_device();                       // PALACE_DEVICE (device_pick.hpp): before anything touches HIP
-    palace_host::Trace tr("split_fastg");
-    palace_ctx *ctx = nullptr;
-    if (palace_ctx_create(device, &ctx) != PALACE_OK) {
-        std::fprintf(stderr, "split_fastg: no GPU device to work on (%s); there is no CPU path\n", palace_last_error());
-        return 1;
-    }
-    tr.lap("device up");
-    try {
-        run(ctx, graph, output, fai, tr);
-    } catch (const std::exception &e) {
-        std::fprintf(stderr, "split_fastg: %s\n", e.what());
-        return 1;
-    }
-    fast_exit.done(0);          // outputs are complete and closed: the caller goes on, the teardown happens behind it
+    return palace_host::device_tool("split_fastg", [&](palace_ctx *ctx, palace_host::Trace &tr) { run(ctx, graph, output, fai, tr); });
 }
