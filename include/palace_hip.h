@@ -1040,6 +1040,43 @@ int palace_fai_rows_plan(palace_ctx *ctx, const palace_fasta_rec *d_recs, const 
 int palace_fai_rows_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records,
                           const int64_t *d_row_off, uint8_t *d_out);
 
+/* ---- faidx: regions of an indexed FASTA as FASTA text (`samtools faidx <file.fa> region ...`; the rules: DESIGN.md 8) --------- */
+
+/* One resolved region (24 bytes): rec the record, -1 for a region that fails; beg its first base, 0-based; len its bases, after
+ * clipping to the record's length. */
+typedef struct {
+    int64_t rec, beg, len;
+} palace_faidx_region;
+
+/* Region i is d_reg[d_reg_off[i] .. d_reg_off[i + 1]) (n_regions + 1 ascending entries).  A region that is a record's name, whole,
+ * is that record; otherwise it is cut at its LAST ':' -- the part in front must be a record's name, the part behind is B, B-E, B-
+ * or -E: decimal digits in which ',' is ignored, at least one and at most 18 digits a number, 1-based and inclusive, B = 0 counted
+ * as 1, a missing B 1, a missing E the record's length.  E beyond the length is the length; B beyond the length gives len = 0 (beg
+ * = the length), which is no failure; E < B as written, a range of no bytes and every other byte fail, as does a name no record
+ * has (the empty one too).  Of records with equal names the first is found (names: palace_fasta_names_create's table over
+ * d_recs, whose lengths are read).  The grammar is csrc/faidx_region.hpp's.  One lane per region.  Enqueues only. */
+int palace_faidx_resolve(palace_ctx *ctx, const palace_fasta_names *names, const palace_fasta_rec *d_recs, const uint8_t *d_reg,
+                         const int64_t *d_reg_off, int64_t n_regions, palace_faidx_region *d_out);
+
+/* The output's layout for lines of line_len >= 1 bases.  Region i has a header of d_hdr_off[i + 1] - d_hdr_off[i] bytes and takes
+ * 1 + header + 1 + len + ceil(len / line_len) bytes, a failed region none.  d_out_off[0 .. n_regions]: the 64-bit exclusive scan of
+ * those sizes; *total_out: its last entry; *first_failed_out: the smallest failed region, -1 when there is none.  skip_failed = 0:
+ * a failed region leaves no text at all -- every entry of d_out_off and *total_out are 0.  Waits for the stream. */
+int palace_faidx_plan(palace_ctx *ctx, const palace_faidx_region *d_regions, int64_t n_regions, const int64_t *d_hdr_off, int64_t line_len,
+                      int skip_failed, int64_t *d_out_off, int64_t *total_out, int64_t *first_failed_out);
+
+/* Bytes [lo, hi) of the output text to d_out[0 .. hi - lo) (d_out 16-byte aligned; nothing outside that range is written): per
+ * region with text '>' header LF, then its bases in lines of line_len, every line -- the last, possibly shorter, too -- ended by
+ * LF; a region of 0 bases is its header line alone.  The header is d_hdr[d_hdr_off[i] .. d_hdr_off[i + 1]).  reverse != 0: every
+ * region's bases are read from the range's end through the ambiguous-DNA complement of palace_final_fasta_write.  d_regions and
+ * d_out_off as palace_faidx_resolve and palace_faidx_plan left them; any 0 <= lo <= hi <= d_out_off[n_regions] will do.  A lane
+ * writes 16 aligned bytes; the regions of a tile's first and last byte are searched once per tile; 16 bases that lie in one output
+ * line and one line of the record are one load and one store, everything else is walked byte by byte across line ends, regions
+ * and the window's edges.  All offsets are 64-bit.  Enqueues only. */
+int palace_faidx_write(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const palace_faidx_region *d_regions,
+                       int64_t n_regions, const uint8_t *d_hdr, const int64_t *d_hdr_off, const int64_t *d_out_off, int64_t line_len,
+                       int reverse, int64_t lo, int64_t hi, uint8_t *d_out);
+
 /* ---- the phage scorer's input: k-mer pair features of every record of an indexed FASTA (phage_scoring; the rules: DESIGN.md 8) */
 
 #define PALACE_CONTIG_FEATURES 12288       /* 3 distances x 64 x 64 pairs of 3-mers */

@@ -81,6 +81,7 @@ DEPTH_RUN_DTYPE = np.dtype([("sum", np.uint64), ("lines", np.uint64), ("name_off
 assert DEPTH_CURSOR_DTYPE.itemsize == 64 + 8192 and DEPTH_RUN_DTYPE.itemsize == 24
 FASTA_REC_DTYPE = np.dtype([(k, np.int64) for k in ("name_off", "name_len", "seq_off", "length", "line_bases", "line_width")])
 FASTA_TILE_BYTES = 4096                 # PALACE_FASTA_TILE_BYTES
+FAIDX_REGION_DTYPE = np.dtype([(k, np.int64) for k in ("rec", "beg", "len")])       # palace_faidx_region
 CONTIG_FEATURES, CONTIG_FSUMS, CONTIG_CHUNK_BASES = 12288, 64, 4096     # PALACE_CONTIG_FEATURES, _FSUMS, _CHUNK_BASES
 CONTIG_INFO_DTYPE = np.dtype([("length", np.int64), ("bases", np.int64)])
 PATH_NOTHING, PATH_NOT_FOUND, PATH_REVERSE, PATH_SECOND_TRY = -1, -2, 1, 2
@@ -252,6 +253,10 @@ _SIGS = {
     "palace_fastg_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p],
     "palace_fai_rows_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.POINTER(C.c_int64)],
     "palace_fai_rows_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p],
+    "palace_faidx_resolve": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "palace_faidx_plan": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
+    "palace_faidx_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int64,
+                           C.c_int64, C.c_void_p],
     "palace_path_fasta_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_int64, C.c_int64, C.c_void_p],
     "palace_cycle_trim": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
@@ -1810,6 +1815,72 @@ class FastgSplit:
             if t:
                 _check(lib().palace_fasta_names_destroy(self.ctx.h, t), "palace_fasta_names_destroy")
         self.names, self.whole_names = C.c_void_p(), C.c_void_p()
+
+
+# ---- faidx: regions resolved, planned and written ---------------------------------------------------------------------------------------
+
+def _blob(ctx: Ctx, items):
+    """byte strings one behind the other and their len(items) + 1 offsets, on the device"""
+    off = np.zeros(len(items) + 1, np.int64)
+    np.cumsum([len(t) for t in items], out=off[1:])
+    return ctx.upload(np.frombuffer(b"".join(items), np.uint8)), ctx.upload(off)
+
+
+class Faidx(PathFasta):
+    """The chain behind faidx's fetch at the ABI: an indexed FASTA with its name table (PathFasta), then per list of regions
+    palace_faidx_resolve -> palace_faidx_plan -> palace_faidx_write.  The expected bytes are the caller's (tests/faidx_cases.py)."""
+
+    def resolve_regions(self, regions, guard: int = 2):
+        """-> (the regions as FAIDX_REGION_DTYPE on the host, on the device); `guard` entries behind the last must stay untouched"""
+        n = len(regions)
+        d_reg, d_off = _blob(self.ctx, regions)
+        fill = np.full((n + guard) * FAIDX_REGION_DTYPE.itemsize, 0xA5, np.uint8)
+        d_out = self.ctx.upload(fill)
+        _check(lib().palace_faidx_resolve(self.ctx.h, self.names, self.d_recs.ptr, d_reg.ptr, d_off.ptr, n, d_out.ptr), "palace_faidx_resolve")
+        got = d_out.to_host()
+        assert (got[n * FAIDX_REGION_DTYPE.itemsize:] == 0xA5).all(), "palace_faidx_resolve: written behind its regions"
+        d_reg.free()
+        d_off.free()
+        return got[:n * FAIDX_REGION_DTYPE.itemsize].view(FAIDX_REGION_DTYPE).copy(), d_out
+
+    def upload_regions(self, resolved):
+        """(rec, beg, len) triples of the caller's -> a device buffer as resolve_regions leaves one"""
+        a = np.zeros(max(len(resolved), 1), FAIDX_REGION_DTYPE)
+        for i, (r, b, ln) in enumerate(resolved):
+            a[i] = (r, b, ln)
+        return self.ctx.upload(a)
+
+    def plan(self, d_regions: DevBuf, n_regions: int, headers, line_len: int, skip_failed: bool):
+        """-> (offsets on the host, total, first failed, (d_hdr, d_hdr_off, d_out_off))"""
+        d_hdr, d_hdr_off = _blob(self.ctx, headers)
+        d_out_off = self.ctx.upload(np.full(n_regions + 1 + 2, -7, np.int64))
+        total, first = C.c_int64(-5), C.c_int64(-5)
+        _check(lib().palace_faidx_plan(self.ctx.h, d_regions.ptr, n_regions, d_hdr_off.ptr, line_len, int(skip_failed), d_out_off.ptr, C.byref(total),
+                                       C.byref(first)), "palace_faidx_plan")
+        off = d_out_off.to_host()
+        assert (off[n_regions + 1:] == -7).all(), "palace_faidx_plan: written behind its offsets"
+        return off[:n_regions + 1].copy(), int(total.value), int(first.value), (d_hdr, d_hdr_off, d_out_off)
+
+    def write(self, d_regions: DevBuf, n_regions: int, planned, line_len: int, reverse: bool, bounds, guard: int = 64):
+        """the windows [lo, hi) of `bounds`, every one in a slot of its own of one device buffer with `guard` bytes (a multiple of
+        16) in front of and behind it -> ([the windows' bytes], every guard byte untouched)"""
+        d_hdr, d_hdr_off, d_out_off = planned
+        slots, at = [], 0
+        for lo, hi in bounds:
+            slots.append(at + guard)
+            at += guard + (hi - lo + 15) // 16 * 16 + guard
+        d_out = self.ctx.upload(np.full(max(at, 1), 0xA5, np.uint8))
+        for (lo, hi), slot in zip(bounds, slots):
+            _check(lib().palace_faidx_write(self.ctx.h, self.d_text.ptr, self.d_recs.ptr, d_regions.ptr, n_regions, d_hdr.ptr, d_hdr_off.ptr, d_out_off.ptr, line_len,
+                                            int(reverse), lo, hi, d_out.ptr + slot), "palace_faidx_write")
+        got = d_out.to_host()
+        d_out.free()
+        keep = np.zeros(len(got), bool)
+        pieces = []
+        for (lo, hi), slot in zip(bounds, slots):
+            keep[slot:slot + hi - lo] = True
+            pieces.append(got[slot:slot + hi - lo].tobytes())
+        return pieces, bool((got[~keep] == 0xA5).all())
 
 
 # ---- filter_result: the BLAST groups, the paths' classes, the first of equal paths ----------------------------------------------------

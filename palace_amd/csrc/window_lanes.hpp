@@ -67,15 +67,15 @@ __device__ __forceinline__ uint32_t complement4(Comp comp, uint32_t w)
     return comp(w & 0xffu) | (comp((w >> 8) & 0xffu) << 8) | (comp((w >> 16) & 0xffu) << 16) | (comp(w >> 24) << 24);
 }
 
-// m bases (0 < m <= the lane's room) of record r of the indexed text (r.line_bases > 0: a select in front of the division is a
-// measurable part of the paths writer's time), from place pos_in_seq of its sequence on; rev: of its other strand, read from the
-// record's end through comp.  True: they were the lane's whole 16 bytes and 16 neighbours of one source line,
-// and are stored already -- one load, one store; the lane is done.  False: they are put.
+// m bases (0 < m <= the lane's room) of the bases [start, start + span) of record r of the indexed text (r.line_bases > 0: a select
+// in front of the division is a measurable part of the paths writer's time), from place pos_in_seq of that range on; rev: of its
+// other strand, read from the range's end through comp.  True: they were the lane's whole 16 bytes and 16 neighbours of one source
+// line, and are stored already -- one load, one store; the lane is done.  False: they are put.
 template <class Comp>
-__device__ __forceinline__ bool gather_bases(LaneOut &l, const uint8_t *text, const palace_fasta_rec &r, int64_t pos_in_seq, int m, bool rev, uint8_t *out,
-                                             Comp comp)
+__device__ __forceinline__ bool gather_bases(LaneOut &l, const uint8_t *text, const palace_fasta_rec &r, int64_t start, int64_t span, int64_t pos_in_seq, int m,
+                                             bool rev, uint8_t *out, Comp comp)
 {
-    const int64_t pos = rev ? r.length - 1 - pos_in_seq : pos_in_seq;
+    const int64_t pos = start + (rev ? span - 1 - pos_in_seq : pos_in_seq);
     const int64_t line_bases = r.line_bases;                                 // (> 0: an indexed record with bases has a first line)
     const int64_t row = pos / line_bases;
     int64_t col = pos - row * line_bases, src = r.seq_off + row * r.line_width + col;
@@ -96,6 +96,14 @@ __device__ __forceinline__ bool gather_bases(LaneOut &l, const uint8_t *text, co
         else if (++col == line_bases) { col = 0; src += gap + 1; } else src++;
     }
     return false;
+}
+
+// the same of the whole record
+template <class Comp>
+__device__ __forceinline__ bool gather_bases(LaneOut &l, const uint8_t *text, const palace_fasta_rec &r, int64_t pos_in_seq, int m, bool rev, uint8_t *out,
+                                             Comp comp)
+{
+    return gather_bases(l, text, r, 0, r.length, pos_in_seq, m, rev, out, comp);
 }
 
 // ---- the complements: three, as the reference's scripts differ ------------------------------------------------------------------------

@@ -47,10 +47,12 @@ template <class Body> int with_device(const char *prog, Body body)
 
 // Two frames because they leave differently: with_device returns through the teardown (the context destroyed, main's return), while
 // device_tool leaves through FastExit::done, the caller going on while the teardown happens behind it (fast_exit.hpp).
-// The frame of make_fa_from_path, split_fastg, readqc, make_final_fa and filter_result, called when the command line is parsed: the
+// The frame of make_fa_from_path, split_fastg, readqc, make_final_fa, filter_result and faidx, called when the command line is parsed: the
 // forked start, the picked device, the context, body(ctx, trace).  No device, or an exception from the body, is one `<prog>: ...` line
-// on stderr behind whatever stdout holds, and exit code 1.  (eref, generateGraph and matching bring the context up on a thread beside
+// on stderr behind whatever stdout holds, and exit code 1; a body that has said in words of its own why it fails (faidx, whose lines
+// are samtools') throws SaidAlready: exit code 1 and no further line.  (eref, generateGraph and matching bring the context up on a thread beside
 // their input and keep frames of their own.)
+struct SaidAlready {};
 template <class Body> int device_tool(const char *prog, Body body)
 {
     FastExit fast_exit = fast_exit_begin();   // from here on this is the worker process
@@ -64,6 +66,9 @@ template <class Body> int device_tool(const char *prog, Body body)
     tr.lap("device up");
     try {
         body(ctx, tr);
+    } catch (const SaidAlready &) {
+        std::fflush(stdout);
+        return 1;
     } catch (const std::exception &e) {
         std::fflush(stdout);
         std::fprintf(stderr, "%s: %s\n", prog, e.what());

@@ -1,13 +1,14 @@
 // A FASTA text that lies on the device: its index and the table of its names (csrc/path_fasta.hip).  `Assembly` is the whole of it
 // for make_fa_from_path, make_final_fa and filter_result; split_fastg, whose names are derived first, takes index_fasta and
 // for_each_duplicate; `resolve` turns names into records for the first three and for their ids_of / records_of.  What a name that
-// appears twice means is the tool's.
+// appears twice means is the tool's.  `write_fai`: the index rows of a text to their file (split_fastg --fai, faidx).
 #pragma once
 #include <string>
 #include <vector>
 
 #include "device_scope.hpp"
 #include "fastx.hpp"
+#include "output_windows.hpp"
 #include "trace.hpp"
 
 namespace palace_host {
@@ -52,6 +53,21 @@ void for_each_duplicate(palace_ctx *ctx, const std::vector<uint8_t> &dup, const 
     HIP_OK(palace_d2h(ctx, recs.data(), d_recs, recs.size() * sizeof(palace_fasta_rec)));
     for (; k < dup.size(); k++)
         if (dup[k]) seen(k, recs[k], text);
+}
+
+// the `.fai` rows of d_recs (none where d_skip is set) to `path`: in place, or as `<path>.tmp` that gets its name when complete
+inline void write_fai(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records, const std::string &path,
+                      bool in_place)
+{
+    DeviceScope dev(ctx, no_room_does_not_fit);
+    int64_t *d_off = dev.array<int64_t>(static_cast<size_t>(n_records + 1), "the rows' places");
+    int64_t bytes = 0;
+    HIP_OK(palace_fai_rows_plan(ctx, d_recs, d_skip, n_records, d_off, &bytes));
+    uint8_t *d_rows = dev.array<uint8_t>(static_cast<size_t>(bytes), "the index rows");
+    HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off, d_rows));
+    PendingOutputs outputs;
+    device_to_file(ctx, d_rows, bytes, outputs.open(path, in_place), path);
+    if (!outputs.commit()) throw Failure("cannot write " + path);
 }
 
 // the 1-based line of the text that holds byte `at`

@@ -1,8 +1,9 @@
 // An output text that is made on the device goes to its file in windows: window w is computed and copied back while window w - 1 is
-// written (WindowWriter: make_fa_from_path, make_final_fa, filter_result, readqc).  Two device windows, two page-locked buffers, the
-// library's marks 0 and 1.  Nothing there knows what the text is: the tool's `produce` makes the bytes [lo, hi) of it in the device
-// window it is handed.  Beside it, what those tools and split_fastg share around the text: PendingOutputs, the files that get their
-// names only when complete (all five), and PathsText, the headers and places of a text of paths (the three FASTA writers).
+// written (WindowWriter: make_fa_from_path, make_final_fa, filter_result, readqc, faidx).  Two device windows, two page-locked
+// buffers, the library's marks 0 and 1.  Nothing there knows what the text is: the tool's `produce` makes the bytes [lo, hi) of it in
+// the device window it is handed.  Beside it, what those tools and split_fastg share around the text: PendingOutputs, the files that
+// get their names only when complete (all six), PathsText, the headers and places of a text of paths (the three FASTA writers), and
+// device_to_file, a device buffer to a file in pieces (split_fastg's text, the `.fai` rows).
 #pragma once
 #include <cstdio>
 #include <cstdlib>
@@ -65,6 +66,18 @@ struct PendingOutputs {
     }
     bool commit() { return !close() && !rename(); }
 };
+
+// a device buffer of `bytes` bytes to the file, in pieces (split_fastg's text, the `.fai` rows)
+inline void device_to_file(palace_ctx *ctx, const uint8_t *d, int64_t bytes, std::FILE *f, const std::string &path)
+{
+    const int64_t piece = 64ll << 20;
+    std::vector<uint8_t> buf(static_cast<size_t>(bytes < piece ? bytes : piece));
+    for (int64_t at = 0; at < bytes; at += piece) {
+        const size_t k = static_cast<size_t>(bytes - at < piece ? bytes - at : piece);
+        HIP_OK(palace_d2h(ctx, buf.data(), d + at, k));
+        if (std::fwrite(buf.data(), 1, k, f) != k) throw Failure("cannot write " + path);
+    }
+}
 
 // The plan of an output text of paths (make_fa_from_path, make_final_fa, filter_result) as palace_path_fasta_write and
 // palace_final_fasta_write take it: the headers one behind the other, their offsets, and every path's place in the text -- a written

@@ -42,32 +42,6 @@ const char *fault_text(int code)
     return palace_host::fasta_fault_text(code);
 }
 
-// a device buffer of `bytes` bytes to the file, in pieces
-void to_file(palace_ctx *ctx, const uint8_t *d, int64_t bytes, std::FILE *f, const std::string &path)
-{
-    const int64_t piece = 64ll << 20;
-    std::vector<uint8_t> buf(static_cast<size_t>(bytes < piece ? bytes : piece));
-    for (int64_t at = 0; at < bytes; at += piece) {
-        const size_t k = static_cast<size_t>(bytes - at < piece ? bytes - at : piece);
-        HIP_OK(palace_d2h(ctx, buf.data(), d + at, k));
-        if (std::fwrite(buf.data(), 1, k, f) != k) throw Failure("cannot write " + path);
-    }
-}
-
-// the `.fai` rows of d_recs (none where d_skip is set) to `path`
-void write_fai(palace_ctx *ctx, const uint8_t *d_text, const palace_fasta_rec *d_recs, const uint8_t *d_skip, int64_t n_records, const std::string &path)
-{
-    DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
-    int64_t *d_off = dev.array<int64_t>(static_cast<size_t>(n_records + 1), "the rows' places");
-    int64_t bytes = 0;
-    HIP_OK(palace_fai_rows_plan(ctx, d_recs, d_skip, n_records, d_off, &bytes));
-    uint8_t *d_rows = dev.array<uint8_t>(static_cast<size_t>(bytes), "the index rows");
-    HIP_OK(palace_fai_rows_write(ctx, d_text, d_recs, d_skip, n_records, d_off, d_rows));
-    palace_host::PendingOutputs outputs;
-    to_file(ctx, d_rows, bytes, outputs.open(path, true), path);
-    if (!outputs.commit()) throw Failure("cannot write " + path);
-}
-
 void run(palace_ctx *ctx, const std::string &graph, const std::string &output, bool fai, palace_host::Trace &tr)
 {
     palace_host::MappedText text;
@@ -105,17 +79,17 @@ void run(palace_ctx *ctx, const std::string &graph, const std::string &output, b
     HIP_OK(palace_fastg_write(ctx, d_text, d_name_recs, d_primed, d_out_off, n_records, 0, total, d_out));
     HIP_OK(palace_sync(ctx));
     tr.lap("output gathered");
-    to_file(ctx, d_out, total, out, output);
+    palace_host::device_to_file(ctx, d_out, total, out, output);
     dev.give_back(d_out);
     if (!outputs.commit()) throw Failure("cannot write " + output);
     tr.lap("output written");
     if (!fai) return;
 
-    write_fai(ctx, d_text, d_out_recs, d_dup, n_records, output + ".fai");
+    palace_host::write_fai(ctx, d_text, d_out_recs, d_dup, n_records, output + ".fai", true);
     palace_host::FastaNamesHandle whole(ctx);
     uint8_t *d_skip = dev.array<uint8_t>(nr, "the duplicate flags");
     HIP_OK(palace_fasta_names_create(ctx, d_text, d_recs, n_records, d_skip, &whole.h));
-    write_fai(ctx, d_text, d_recs, d_skip, n_records, graph + ".fai");
+    palace_host::write_fai(ctx, d_text, d_recs, d_skip, n_records, graph + ".fai", true);
     std::vector<uint8_t> skip(nr);
     if (n_records) HIP_OK(palace_d2h(ctx, skip.data(), d_skip, skip.size()));
     palace_host::for_each_duplicate(ctx, skip, d_recs, text.data, [&](size_t k, const palace_fasta_rec &r, const char *t) {
