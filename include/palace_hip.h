@@ -235,8 +235,10 @@ int palace_eref_entry_counts_valid(const palace_ctx *ctx, const palace_eref_prob
 /* Multi-GPU exchange of the count table (no reference counterpart: the reference shares one
  * table between std::threads, extract_ref.cpp:1269-1291).  planes() exposes the three device
  * buffers (each 2^29 bytes); merge_slices() folds `n_parts` partial tables laid out as
- * [plane][part][slice_bytes] into the caller's planes at byte offset `slice_off`, with the
- * saturating add  (a + b >= t  for t = 1, 2, 3)  done bit-parallel on the planes. */
+ * [plane][part][slice_bytes] with the saturating add  (a + b >= t  for t = 1, 2, 3)  done bit-parallel
+ * on the planes, and REPLACES bytes [slice_off, slice_off + slice_bytes) of the context's planes by the
+ * result: what the slice held before is not added (a rank's own partial table is one of the parts);
+ * nothing outside the slice is written. */
 int palace_eref_table_planes(palace_ctx *ctx, void **d_planes3, size_t *bytes_per_plane);
 /* Use three caller-owned device buffers (each 2^29 bytes, 16-byte aligned) as the table from now on
  * (so a collective library can address them directly); the context no longer frees table memory. */

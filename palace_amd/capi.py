@@ -402,6 +402,9 @@ class Ctx:
     def d2d(self, dst_ptr: int, src_ptr: int, nbytes: int):
         _check(lib().palace_d2d(self.h, dst_ptr, src_ptr, nbytes), "palace_d2d")
 
+    def memset(self, ptr: int, value: int, nbytes: int):
+        _check(lib().palace_memset(self.h, ptr, value, nbytes), "palace_memset")
+
     def sync(self):
         _check(lib().palace_sync(self.h), "palace_sync")
 
@@ -493,6 +496,12 @@ class Ctx:
         """the caller's device buffers stand in for the index's count / hit-bit blocks (None: the index's own)"""
         _check(lib().palace_eref_entry_buffers_attach(self.h, index, counts_ptr, hits_ptr), "palace_eref_entry_buffers_attach")
 
+    def eref_entry_buffers(self, index):
+        """-> (device pointer of the count block, of the hit-bit block) as they are attached now (counts: None before a first attach)"""
+        counts, hits = C.c_void_p(), C.c_void_p()
+        _check(lib().palace_eref_entry_buffers(index, C.byref(counts), C.byref(hits)), "palace_eref_entry_buffers")
+        return counts.value, hits.value
+
     def eref_entry_hits_from_counts(self, index, parts_ptr: int, n_parts: int, part_stride: int, off: int, nbytes: int):
         """sum n_parts partial-count arrays over the count block's bytes [off, off + nbytes) into the hit bits of that entry range"""
         _check(lib().palace_eref_entry_hits_from_counts(self.h, index, parts_ptr, n_parts, part_stride, off, nbytes), "palace_eref_entry_hits_from_counts")
@@ -536,6 +545,25 @@ class Ctx:
         nbytes = C.c_size_t()
         _check(lib().palace_eref_table_planes(self.h, ptrs, C.byref(nbytes)), "palace_eref_table_planes")
         return [int(p) for p in ptrs], int(nbytes.value)
+
+    def eref_plane_write(self, p: int, off: int, data: np.ndarray):
+        """bytes [off, off + len(data)) of plane p (0..2) <- data, through the pointers of eref_table_planes; then the invalidate
+        the header's contract for caller-written planes demands"""
+        planes, nbytes = self.eref_table_planes()
+        a = np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        assert 0 <= off and off + a.nbytes <= nbytes
+        if a.nbytes:
+            _check(lib().palace_h2d(self.h, planes[p] + off, a.ctypes.data, a.nbytes), "palace_h2d")
+        self.eref_table_invalidate()
+
+    def eref_plane_read(self, p: int, off: int, n: int) -> np.ndarray:
+        """bytes [off, off + n) of plane p (0..2)"""
+        planes, nbytes = self.eref_table_planes()
+        assert 0 <= off and off + n <= nbytes
+        out = np.empty(n, dtype=np.uint8)
+        if n:
+            _check(lib().palace_d2h(self.h, out.ctypes.data, planes[p] + off, n), "palace_d2h")
+        return out
 
     def eref_table_attach(self, ptrs):
         arr = (C.c_void_p * 3)(*[int(p) for p in ptrs])

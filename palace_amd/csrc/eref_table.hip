@@ -41,7 +41,7 @@ __global__ __launch_bounds__(256) void pack_low_kernel(const uint4 *__restrict__
     }
 }
 
-// saturating unary add of n_parts partial tables into the context's planes (16 B per lane); PACKED: the parts come
+// saturating unary add of n_parts partial tables, written OVER the slice of the context's planes (16 B per lane); PACKED: the parts come
 // as (low bit, high bit) planes, layout [2][part][slice], otherwise as the three unary planes, layout [3][part][slice]
 template <bool PACKED>
 __global__ __launch_bounds__(256) void merge_slices_kernel(const uint4 *__restrict__ parts, int n_parts,
