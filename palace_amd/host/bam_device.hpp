@@ -4,6 +4,8 @@
 // BackMembers), sends their compressed bytes up, and copies the inflated bytes straight into the loader's stream
 // (PALACE_BAM_DEVICE=0: the host alone; see device_inflate_helpers below for what it measured).  A member the
 // device decoder refuses goes to the loader's own decoder (zlib behind it), as a member the CPU decoder refuses does.
+// (The batch's member table is the MemberTable of bgzf_read_device.hpp; the batch reader there is another loop: blocking, CRC-checked,
+// for the loaders that keep the text on the device.)
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -14,50 +16,9 @@
 
 #include "../../include/palace_hip.h"
 #include "bam.hpp"
+#include "bgzf_read_device.hpp"
 
 namespace palace_host {
-
-// Members per launch of palace_bgzf_inflate: a launch takes as long as its slowest member (~20 ms for 64 KiB) however few members it
-// has, and the device holds ~7 000 of the decoder's wavefronts at a time (28 per CU).  (eref's FASTQ in batches of one 32 MiB window,
-// ~500 members, left it mostly idle: 260 ms against the 1M-contig sample's 2.1 GB of text, 44 ms in batches of 8 192.)
-constexpr size_t kMemberBatch = 8192;
-
-// The member table of one batch as palace_bgzf_inflate and palace_crc32_members read it: per member in_off, out_off (int64), in_len,
-// out_len, status, crc (int32), one array of n each.  fill() builds it on the host; the caller sends up the first up_bytes() (the
-// columns in front of status) in one copy and reads status / crc back.  Offsets are relative to the batch's first input byte (in0)
-// and to its first member's output.  inflate() and crc32() return what the palace_* call returns (0: enqueued).
-struct MemberTable {
-    static constexpr size_t kBytes = 32 * kMemberBatch;                    // a batch's table, host and device
-    palace_ctx *ctx;
-    uint8_t *dev;                                                          // kBytes of device memory (the caller's)
-    std::vector<uint8_t> host = std::vector<uint8_t>(kBytes);
-    size_t n = 0;
-    void fill(const BgzfMember *m, size_t count, uint64_t in0)
-    {
-        n = count;
-        int64_t *io = in_off(host.data()), *oo = out_off(host.data());
-        int32_t *il = in_len(host.data()), *ol = out_len(host.data());
-        for (size_t k = 0; k < n; k++) {
-            io[k] = static_cast<int64_t>(m[k].in_off - in0); il[k] = static_cast<int32_t>(m[k].in_len);
-            oo[k] = static_cast<int64_t>(m[k].out_off - m[0].out_off); ol[k] = static_cast<int32_t>(m[k].out_len);
-        }
-    }
-    size_t up_bytes() const { return 24 * n; }
-    // the columns in `base` (host.data() or dev)
-    int64_t *in_off(uint8_t *base) const { return reinterpret_cast<int64_t *>(base); }
-    int64_t *out_off(uint8_t *base) const { return reinterpret_cast<int64_t *>(base + 8 * n); }
-    int32_t *in_len(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + 16 * n); }
-    int32_t *out_len(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + 20 * n); }
-    int32_t *status(uint8_t *base) const { return reinterpret_cast<int32_t *>(base + 24 * n); }
-    uint32_t *crc(uint8_t *base) const { return reinterpret_cast<uint32_t *>(base + 28 * n); }
-    // the batch's compressed bytes (d_in = input byte in0) inflated into d_out; status 0: the member's bytes are there
-    int inflate(const uint8_t *d_in, uint8_t *d_out) const
-    {
-        return palace_bgzf_inflate(ctx, d_in, static_cast<int64_t>(n), in_off(dev), in_len(dev), out_off(dev), out_len(dev), d_out, status(dev));
-    }
-    // crc: the CRC-32 of every member's bytes in d_out
-    int crc32(const uint8_t *d_out) const { return palace_crc32_members(ctx, d_out, static_cast<int64_t>(n), out_off(dev), out_len(dev), crc(dev)); }
-};
 
 constexpr double kDeviceBatchDeadlineS = 20.0;          // a batch takes ~0.1 s; behind this the device is taken to be hung
 

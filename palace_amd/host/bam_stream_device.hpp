@@ -1,8 +1,7 @@
 // `bamdepth --bam-gpu`: the BAM inflated, walked and decoded on the device -- for the one consumer that
-// needs nothing of a record but its match segments.  The file's BGZF members go up a batch at a time (MemberTable, bam_device.hpp),
-// palace_bgzf_inflate puts them into ONE device buffer sized from the ISIZE trailers (a member the device decoder refuses:
-// inflate_member on the host, its bytes copied up into place, as fastq_gz.hpp does), palace_crc32_members checks every member
-// against its trailer, palace_bam_walk finds the records and palace_bam_match_segments leaves the depth stage's (tid, pos, len)
+// needs nothing of a record but its match segments.  The file's BGZF members go through the batch reader of bgzf_read_device.hpp
+// (inflated and CRC-checked on the device, a batch at a time) into ONE device buffer sized from the ISIZE trailers,
+// palace_bam_walk finds the records and palace_bam_match_segments leaves the depth stage's (tid, pos, len)
 // arrays in device memory.  The header -- magic, l_text, n_ref, names, lengths, the offset of the first record -- is parsed on the
 // host from the front members, inflated there.  The alignment records' bytes never cross back.
 // What load_bam (bam.cpp) rejects is rejected here, with its message; its behaviour is not touched.  Device memory held at once: the
@@ -22,8 +21,7 @@
 #include <vector>
 
 #include "../../include/palace_hip.h"
-#include "bam_device.hpp"
-#include "bgzf.hpp"
+#include "bgzf_read_device.hpp"
 #include "device_scope.hpp"
 #include "mapped_file.hpp"
 
@@ -102,14 +100,12 @@ struct BamMemberTable { std::vector<int64_t> u, c; };
 inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int threads, DeviceBamStream &out, BamDeviceTimes *times = nullptr,
                                    const std::function<void()> &on_header = {}, BamMemberTable *members = nullptr)
 {
-    auto le32 = [](const uint8_t *p) { uint32_t v; std::memcpy(&v, p, 4); return v; };
     BamDeviceTimes unused;
     BamDeviceTimes &tm = times ? *times : unused;
     StageClock clock{ctx, times != nullptr};
     auto lap = [&](double *acc, bool device) { clock.lap(acc, device); };
     out.ctx = ctx;
     DeviceScope own(ctx, bam_gpu_no_room);
-    auto give_back = [&](void *p) { own.give_back(p); };
     auto dev = [&](size_t bytes, const char *what) { return own.alloc(bytes, what); };
 
     // ---- the file and its checked member index ----
@@ -119,7 +115,7 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
     const std::vector<BgzfMember> mem = bgzf_members(file.bytes(), file.size, &total, &end);
     const size_t nb = mem.size();
     out.total = static_cast<int64_t>(total);
-    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
+    auto member_start = [&](size_t i) { return bgzf_member_start(mem, i); };
     if (members) {
         for (size_t i = 0; i < nb; i++) {
             members->u.push_back(static_cast<int64_t>(mem[i].out_off));
@@ -182,52 +178,16 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
     lap(&tm.header, false);
     if (on_header) on_header();
 
-    // ---- every member inflated into one device buffer, a batch of compressed bytes at a time ----
-    const size_t batch = bam_batch_members();
-    uint64_t max_in = 0;
-    for (size_t i0 = 0; i0 < nb; i0 += batch) {
-        const size_t i1 = std::min(nb, i0 + batch);
-        max_in = std::max<uint64_t>(max_in, mem[i1 - 1].in_off + mem[i1 - 1].in_len + 8 - member_start(i0));
-    }
+    // ---- every member inflated into one device buffer, a batch of compressed bytes at a time (bgzf_read_device.hpp) ----
     uint8_t *d_stream = static_cast<uint8_t *>(dev(total + 64, "the inflated stream"));
-    if (nb) {
-        uint8_t *d_in = static_cast<uint8_t *>(dev(static_cast<size_t>(max_in) + 64, "a batch of compressed bytes"));
-        void *d_meta = dev(MemberTable::kBytes, "the member table");
-        MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
-        std::vector<uint8_t> host_out(65536);
-        for (size_t i0 = 0; i0 < nb; i0 += batch) {
-            const size_t n = std::min(nb, i0 + batch) - i0;
-            const uint64_t in0 = member_start(i0), in1 = mem[i0 + n - 1].in_off + mem[i0 + n - 1].in_len + 8;
-            uint8_t *d_out = d_stream + mem[i0].out_off;
-            tab.fill(&mem[i0], n, in0);
-            const int64_t *out_off = tab.out_off(tab.host.data());
-            int32_t *status = tab.status(tab.host.data());
-            uint32_t *crc = tab.crc(tab.host.data());
-            clock.restart();
-            ck(palace_h2d(ctx, d_in, file.bytes() + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
-            ck(palace_h2d(ctx, d_meta, tab.host.data(), tab.up_bytes()), "member table");
-            lap(&tm.upload, true);
-            ck(tab.inflate(d_in, d_out), "palace_bgzf_inflate");
-            ck(palace_d2h(ctx, status, tab.status(tab.dev), 4 * n), "member status");
-            for (size_t j = 0; j < n; j++) {                                 // what the device refused: the host's decoder, zlib behind it
-                if (status[j] == 0) continue;
-                const BgzfMember &m = mem[i0 + j];
-                if (!inflate_member(file.bytes(), file.size, m, host_out.data())) throw std::runtime_error("BGZF inflate failed");
-                if (m.out_len) ck(palace_h2d(ctx, d_out + out_off[j], host_out.data(), m.out_len), "inflated upload");
-                out.host_inflated++;
-            }
-            lap(&tm.inflate, true);
-            ck(tab.crc32(d_out), "palace_crc32_members");
-            ck(palace_d2h(ctx, crc, tab.crc(tab.dev), 4 * n), "member CRC");
-            for (size_t j = 0; j < n; j++) {
-                const BgzfMember &m = mem[i0 + j];
-                if (crc[j] != le32(file.bytes() + m.in_off + m.in_len))
-                    throw std::runtime_error("CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i0 + j)));
-            }
-            lap(&tm.crc, true);
-        }
-        give_back(d_in);
-        give_back(d_meta);
+    try {                                                                    // (a batch is where the walk will find it: nothing to do with it here)
+        const BgzfReadStats st = read_bgzf_batches(ctx, {bam_gpu_no_room, ck, "a batch of compressed bytes", nullptr, "the member table"}, times != nullptr,
+                                                   file.bytes(), file.size, mem, bgzf_batch_plan(mem, bam_batch_members()), d_stream, [](const BgzfBatch &) {});
+        tm.upload += st.upload; tm.inflate += st.inflate; tm.crc += st.crc;
+        out.host_inflated = st.host_inflated;
+    } catch (const BgzfMemberFault &f) {
+        if (f.kind == BgzfMemberFault::refused) throw std::runtime_error("BGZF inflate failed");
+        throw std::runtime_error("CRC-32 mismatch in the BGZF member at offset " + std::to_string(f.offset));
     }
 
     // ---- the records' starts: counted first, then written into exactly that much memory ----
@@ -242,7 +202,7 @@ inline void load_bam_stream_device(palace_ctx *ctx, const std::string &path, int
                               out.n_records), "palace_bam_walk_starts");
     ck(palace_sync(ctx), "palace_sync");                                    // (the starts are written: the walk's table can go)
     lap(&tm.walk, true);
-    give_back(d_scratch);
+    own.give_back(d_scratch);
     own.keep(d_stream);
     own.keep(d_starts);
     out.d_stream = d_stream;

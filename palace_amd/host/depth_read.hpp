@@ -3,9 +3,8 @@
 // (DESIGN.md section 8).  The text never comes back to the host.
 //   plain: windows of the mapped file go up through two page-locked staging buffers (the copy of window k + 1 into staging runs
 //          while the device works on window k) and through palace_depth_parse.
-//   BGZF:  as eref's ingest_bgzf (fastq_gz.hpp): the checked member index, the compressed bytes up a batch of members at a time,
-//          palace_bgzf_inflate into one buffer per batch (a member the device refuses: inflate_member on the host, copied into
-//          place), palace_crc32_members against every trailer, palace_depth_parse over the batch's text as one window.
+//   BGZF:  the checked member index, then the batch reader of bgzf_read_device.hpp (inflate and CRC-32 on the device, one buffer per
+//          batch of members) and palace_depth_parse over the batch's text as one window.
 // Per window the host reads back the cursor's first 64 bytes, 24 bytes per run and the runs' names, and merges the runs by name in
 // order of first appearance.  Device memory in flight: one batch of compressed bytes, one batch of text (<= 512 MiB), the parser's
 // scratch (80 bytes per 4 KiB of window) and the runs and names of one window (grown when a window needs more).
@@ -21,8 +20,7 @@
 #include <vector>
 
 #include "../../include/palace_hip.h"
-#include "bam_device.hpp"
-#include "bgzf.hpp"
+#include "bgzf_read_device.hpp"
 #include "device_scope.hpp"
 #include "fastx.hpp"
 
@@ -114,10 +112,7 @@ public:
         res.lines = static_cast<uint64_t>(head_.lines); res.sum = head_.sum;
         if (timed_) times.merge += ms_since(t0);
     }
-    void ck(int rc, const char *what)
-    {
-        if (rc) throw std::runtime_error(std::string("device error (") + what + "): " + palace_last_error());
-    }
+    void ck(int rc, const char *what) { ck_device_error(rc, what); }
     static std::chrono::steady_clock::time_point now() { return std::chrono::steady_clock::now(); }
     static double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(now() - t).count(); }
     const std::string &path() const { return path_; }
@@ -183,63 +178,22 @@ inline void read_depth_plain(DepthReader &rd, palace_ctx *ctx, const MappedText 
 // ---- BGZF: inflated, checked and parsed on the device -------------------------------------------------------------------------------
 inline void read_depth_bgzf(DepthReader &rd, palace_ctx *ctx, const MappedText &t, const std::vector<BgzfMember> &mem)
 {
-    const uint8_t *file = reinterpret_cast<const uint8_t *>(t.data);
-    const size_t B = depthin_batch_members();
-    std::vector<size_t> cut{0};                                              // batches [cut[k], cut[k + 1])
-    uint64_t max_in = 0, batch_out = 0;
-    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
-    for (size_t i = 0, out = 0; i < mem.size(); i++) {
-        if (i - cut.back() == B) { cut.push_back(i); out = 0; }
-        out += mem[i].out_len;
-        batch_out = std::max<uint64_t>(batch_out, out);
-        max_in = std::max<uint64_t>(max_in, mem[i].in_off + mem[i].in_len + 8 - member_start(cut.back()));
+    const BgzfBatchPlan plan = bgzf_batch_plan(mem, depthin_batch_members());
+    rd.init(static_cast<int64_t>(plan.max_out));
+    const BgzfReadStyle style{no_room_device_error, ck_device_error, "compressed batch", "inflated batch", "member table"};
+    if (mem.empty()) {                                                       // a file without a member: no text
+        DeviceScope dev(ctx, style.no_room);
+        rd.parse(static_cast<const uint8_t *>(dev.alloc(64, style.inflated)), 0, true);
     }
-    cut.push_back(mem.size());
-    rd.init(static_cast<int64_t>(batch_out));
-    DeviceScope dev(ctx, no_room_device_error);
-    void *d_in = dev.alloc(static_cast<size_t>(max_in) + 64, "compressed batch"), *d_batch = dev.alloc(static_cast<size_t>(batch_out) + 64, "inflated batch");
-    void *d_meta = dev.alloc(MemberTable::kBytes, "member table");
-    MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
-    std::vector<uint8_t> host_out(65536);
-    for (size_t k = 0; k + 1 < cut.size(); k++) {
-        const size_t i0 = cut[k], n = cut[k + 1] - i0;
-        const bool last_batch = k + 2 == cut.size();
-        if (n == 0) { rd.parse(static_cast<const uint8_t *>(d_batch), 0, true); continue; }     // (a file without a member: no text)
-        const uint64_t in0 = member_start(i0), in1 = mem[i0 + n - 1].in_off + mem[i0 + n - 1].in_len + 8;
-        tab.fill(&mem[i0], n, in0);
-        const int64_t *out_off = tab.out_off(tab.host.data());
-        int32_t *status = tab.status(tab.host.data());
-        uint32_t *crc = tab.crc(tab.host.data());
-        const int64_t out = out_off[n - 1] + static_cast<int64_t>(mem[i0 + n - 1].out_len);
-        auto t0 = DepthReader::now();
-        rd.ck(palace_h2d(ctx, d_in, file + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
-        rd.ck(palace_h2d(ctx, d_meta, tab.host.data(), tab.up_bytes()), "member table");
-        rd.times.upload += DepthReader::ms_since(t0);
-        t0 = DepthReader::now();
-        rd.ck(tab.inflate(static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_batch)), "palace_bgzf_inflate");
-        rd.ck(palace_d2h(ctx, status, tab.status(tab.dev), 4 * n), "member status");
-        for (size_t j = 0; j < n; j++) {                                     // what the device refused: the host's decoder, zlib behind it
-            if (status[j] == 0) continue;
-            const BgzfMember &m = mem[i0 + j];
-            if (!inflate_member(file, t.size, m, host_out.data()))
-                throw std::runtime_error(rd.path() + ": the BGZF member at offset " + std::to_string(member_start(i0 + j)) +
-                                         " cannot be inflated to the size its trailer states");
-            if (m.out_len) rd.ck(palace_h2d(ctx, static_cast<uint8_t *>(d_batch) + out_off[j], host_out.data(), m.out_len), "inflated upload");
-            rd.res.host_inflated++;
-        }
-        rd.times.inflate += DepthReader::ms_since(t0);
-        t0 = DepthReader::now();
-        rd.ck(tab.crc32(static_cast<const uint8_t *>(d_batch)), "palace_crc32_members");
-        rd.ck(palace_d2h(ctx, crc, tab.crc(tab.dev), 4 * n), "member CRC");
-        for (size_t j = 0; j < n; j++) {
-            const BgzfMember &m = mem[i0 + j];
-            uint32_t want;
-            std::memcpy(&want, file + m.in_off + m.in_len, 4);
-            if (crc[j] != want)
-                throw std::runtime_error(rd.path() + ": CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i0 + j)));
-        }
-        rd.times.crc += DepthReader::ms_since(t0);
-        rd.parse(static_cast<const uint8_t *>(d_batch), out, last_batch);   // the batch's text as one window
+    try {                                                                    // the batch's text as one window
+        const BgzfReadStats st = read_bgzf_batches(ctx, style, rd.timed(), reinterpret_cast<const uint8_t *>(t.data), t.size, mem, plan, nullptr,
+                                                   [&](const BgzfBatch &b) { rd.parse(b.d_text, b.out_bytes, b.k + 1 == plan.batches()); });
+        rd.times.upload += st.upload; rd.times.inflate += st.inflate; rd.times.crc += st.crc;
+        rd.res.host_inflated = static_cast<uint64_t>(st.host_inflated);
+    } catch (const BgzfMemberFault &f) {
+        if (f.kind == BgzfMemberFault::refused)
+            throw std::runtime_error(rd.path() + ": the BGZF member at offset " + std::to_string(f.offset) + " cannot be inflated to the size its trailer states");
+        throw std::runtime_error(rd.path() + ": CRC-32 mismatch in the BGZF member at offset " + std::to_string(f.offset));
     }
 }
 

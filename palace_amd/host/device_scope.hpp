@@ -21,6 +21,12 @@ inline void ck(int rc, const char *what)
     if (rc) throw std::runtime_error(std::string(what) + ": " + palace_last_error());
 }
 
+// ... as the readers of fastq_gz.hpp and depth_read.hpp say it: `device error (<what>): <the library's message>`
+inline void ck_device_error(int rc, const char *what)
+{
+    if (rc) throw std::runtime_error(std::string("device error (") + what + "): " + palace_last_error());
+}
+
 // the same for the tools that name the failed call itself (split_fastg, make_fa_from_path)
 struct Failure : std::runtime_error { using std::runtime_error::runtime_error; };
 #define HIP_OK(call)                                                                                               \

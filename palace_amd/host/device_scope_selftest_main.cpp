@@ -1,4 +1,5 @@
-// device_scope.hpp, mapped_file.hpp, output_windows.hpp, the duplicate helper of fasta_device.hpp and the member writer's arithmetic on their own
+// device_scope.hpp, mapped_file.hpp, output_windows.hpp, the duplicate helper of fasta_device.hpp, the member writer's arithmetic and the BGZF
+// batch reader (bgzf_read_device.hpp: its "device" inflates with zlib and can be told to refuse members) on their own
 // (tests/test_host_device_scope.py; also built with the host sanitizers).  No device and no libpalace_hip.so: the few palace_* calls
 // the headers make are stubs here that count their calls, remember what is live, queue the asynchronous copies and can be told to
 // fail.  `device_scope_selftest <scratch directory>` prints one line per failed check and `ok <checks>` at the end; exit code 1 if
@@ -19,6 +20,7 @@
 #include "bai.hpp"
 #include "bam_stream_device.hpp"
 #include "bgzf_members_device.hpp"
+#include "bgzf_read_device.hpp"
 #include "device_scope.hpp"
 #include "fasta_device.hpp"
 #include "mapped_file.hpp"
@@ -39,6 +41,8 @@ struct Stub {
     std::vector<Copy> queue;                        // palace_d2h_async calls in order; the first queue_done of them have happened
     size_t queue_done = 0, mark_at[2] = {0, 0};     // mark k stands behind the first mark_at[k] copies
     bool in_flight[2] = {false, false};             // mark k was set and not yet waited for
+    std::vector<size_t> refuse;                     // palace_bgzf_inflate refuses these members, counted over its calls since reset()
+    size_t members_seen = 0;
     void reset() { *this = Stub(); }
 } stub;
 const char *kErr = "out of memory (stub)";
@@ -117,6 +121,30 @@ int palace_mark_wait(palace_ctx *, int idx)
         std::memcpy(c.dst, c.src, c.bytes);
     }
     stub.in_flight[idx & 1] = false;
+    return 0;
+}
+// the "device" decoder: raw zlib inflate of every member, status 0; a refused member gets status 1 and its bytes are not touched
+int palace_bgzf_inflate(palace_ctx *, const uint8_t *d_in, int64_t n_members, const int64_t *d_in_off, const int32_t *d_in_len, const int64_t *d_out_off,
+                        const int32_t *d_out_len, uint8_t *d_out, int32_t *d_status)
+{
+    for (int64_t j = 0; j < n_members; j++, stub.members_seen++) {
+        d_status[j] = 1;
+        if (std::count(stub.refuse.begin(), stub.refuse.end(), stub.members_seen)) continue;
+        d_status[j] = 0;
+        if (d_out_len[j] == 0) continue;
+        z_stream zs{};
+        if (inflateInit2(&zs, -15) != Z_OK) return -1;
+        zs.next_in = const_cast<Bytef *>(d_in + d_in_off[j]); zs.avail_in = static_cast<uInt>(d_in_len[j]);
+        zs.next_out = d_out + d_out_off[j]; zs.avail_out = static_cast<uInt>(d_out_len[j]);
+        if (inflate(&zs, Z_FINISH) != Z_STREAM_END || zs.avail_out != 0) d_status[j] = 1;
+        inflateEnd(&zs);
+    }
+    return 0;
+}
+int palace_crc32_members(palace_ctx *, const uint8_t *d_data, int64_t n_members, const int64_t *d_off, const int32_t *d_len, uint32_t *d_crc)
+{
+    for (int64_t j = 0; j < n_members; j++)
+        d_crc[j] = static_cast<uint32_t>(::crc32(::crc32(0L, Z_NULL, 0), d_data + d_off[j], static_cast<uInt>(d_len[j])));
     return 0;
 }
 int palace_bam_names_destroy(palace_ctx *, palace_bam_names *) { stub.destroys++; return 0; }
@@ -630,6 +658,195 @@ void test_stored_member()
     }
 }
 
+// ---- bgzf_read_device.hpp: the batch plan and the batch reader --------------------------------------------------------------------
+
+// a BGZF file in memory: one member per text (an empty text: a member of ISIZE 0), the EOF member behind them when asked for
+struct BgzfFile {
+    std::vector<uint8_t> bytes;
+    std::string text;
+    std::vector<BgzfMember> mem;
+    BgzfFile(const std::vector<std::string> &texts, bool eof)
+    {
+        for (const std::string &t : texts) {
+            bgzf_member(reinterpret_cast<const uint8_t *>(t.data()), t.size(), 6, bytes);
+            text += t;
+        }
+        if (eof) bytes.insert(bytes.end(), bgzf_eof_member(), bgzf_eof_member() + 28);
+        index();
+    }
+    void index()
+    {
+        size_t total = 0;
+        mem = bgzf_members(bytes.data(), bytes.size(), &total);
+        CHECK(total == text.size());
+    }
+    // where member i starts, from the layout bgzf_member() writes (18 header bytes in front of the DEFLATE data)
+    uint64_t start(size_t i) const { return mem[i].in_off - 18; }
+};
+
+// a few hundred bytes of text that no other call of it returns
+std::string some_text(size_t n, unsigned seed)
+{
+    std::string t(n, '\0');
+    for (size_t i = 0; i < n; i++) t[i] = "ACGTN\n@+IF"[((i + seed) * 2654435761u >> 9) % 10];
+    return t;
+}
+
+const BgzfReadStyle kFastqStyle{no_room_device_error, ck_device_error, "compressed window", "inflated window", "member table"};
+const BgzfReadStyle kBamStyle{bam_gpu_no_room, ck, "a batch of compressed bytes", nullptr, "the member table"};
+
+// One pass of the reader over `f`: the text it hands over, batch by batch, held against the plan and the source.  resident: the
+// batches land in one stream of the caller's.  Returns the count of members inflated on the host.
+int64_t read_all(const BgzfFile &f, size_t batch, bool resident, bool timed = false)
+{
+    const BgzfBatchPlan plan = bgzf_batch_plan(f.mem, batch);
+    std::vector<uint8_t> stream(f.text.size() + 64, 0xee);
+    const std::vector<size_t> refuse = stub.refuse;
+    stub.reset();
+    stub.refuse = refuse;
+    std::string got;
+    size_t next_k = 0;
+    const uint8_t *d_batch = nullptr;
+    const BgzfReadStats st = read_bgzf_batches(ctx, resident ? kBamStyle : kFastqStyle, timed, f.bytes.data(), f.bytes.size(), f.mem, plan,
+                                               resident ? stream.data() : nullptr, [&](const BgzfBatch &b) {
+        if (b.k == 0) {                                                      // what the reader holds while it reads
+            d_batch = b.d_text;
+            if (resident) CHECK(stub.asked == (std::vector<size_t>{static_cast<size_t>(plan.max_in) + 64, MemberTable::kBytes}));
+            else CHECK(stub.asked == (std::vector<size_t>{static_cast<size_t>(plan.max_in) + 64, static_cast<size_t>(plan.max_out) + 64, MemberTable::kBytes}));
+            CHECK(stub.live.size() == stub.asked.size());
+        }
+        CHECK(b.k == next_k && b.k < plan.batches() && b.first == plan.cut[b.k] && b.n == plan.cut[b.k + 1] - b.first && b.n > 0);
+        CHECK(b.in0 == f.start(b.first) && b.in1 == f.mem[b.first + b.n - 1].in_off + f.mem[b.first + b.n - 1].in_len + 8);
+        CHECK(b.in1 - b.in0 <= plan.max_in && static_cast<uint64_t>(b.out_bytes) <= plan.max_out);
+        CHECK(b.d_text == (resident ? stream.data() + f.mem[b.first].out_off : d_batch));
+        CHECK(got.size() == f.mem[b.first].out_off);
+        got.append(reinterpret_cast<const char *>(b.d_text), static_cast<size_t>(b.out_bytes));
+        next_k++;
+    });
+    CHECK(next_k == plan.batches() && got == f.text);
+    if (resident) CHECK(std::memcmp(stream.data(), f.text.data(), f.text.size()) == 0 && stream[f.text.size()] == 0xee);
+    CHECK(stub.mallocs == (f.mem.empty() ? 0 : resident ? 2 : 3) && stub.syncs == (timed ? 3 * static_cast<int>(plan.batches()) : 0));     // (no member: no allocation)
+    CHECK(st.upload >= 0 && st.inflate >= 0 && st.crc >= 0 && (timed || st.upload + st.inflate + st.crc == 0));
+    const int64_t host = st.host_inflated;
+    CHECK(stub.live.empty() && stub.bad_frees == 0);
+    return host;
+}
+
+// the fault a pass over `f` ends with (kind, offset), or (-1, 0); everything the reader held is gone behind it
+std::pair<int, uint64_t> fault_of(const BgzfFile &f, size_t batch, bool resident)
+{
+    const BgzfBatchPlan plan = bgzf_batch_plan(f.mem, batch);
+    std::vector<uint8_t> stream(f.text.size() + 64);
+    const std::vector<size_t> refuse = stub.refuse;
+    stub.reset();
+    stub.refuse = refuse;
+    std::pair<int, uint64_t> got{-1, 0};
+    try {
+        read_bgzf_batches(ctx, kFastqStyle, false, f.bytes.data(), f.bytes.size(), f.mem, plan, resident ? stream.data() : nullptr, [](const BgzfBatch &) {});
+    } catch (const BgzfMemberFault &e) { got = {static_cast<int>(e.kind), e.offset}; }
+    CHECK(stub.live.empty() && stub.bad_frees == 0);
+    return got;
+}
+
+std::vector<size_t> batch_sizes(size_t n)
+{
+    std::vector<size_t> b{1, 2, 3, n + 1};
+    if (n > 3) b.push_back(n);
+    return b;
+}
+
+void test_bgzf_plan()
+{
+    // every cut of 2 .. 9 members into batches of 1 .. 10, against sums over the members' own sizes
+    for (size_t n = 2; n <= 9; n++) {
+        std::vector<std::string> texts;
+        for (size_t i = 0; i < n; i++) texts.push_back(i == n / 2 ? std::string() : some_text(40 + 97 * ((i * 5) % 7), static_cast<unsigned>(n * 16 + i)));
+        const BgzfFile f(texts, false);
+        CHECK(f.mem.size() == n);
+        for (size_t i = 0; i < n; i++) CHECK(bgzf_member_start(f.mem, i) == f.start(i) && bgzf_member_end(f.mem, i) == (i + 1 < n ? f.start(i + 1) : f.bytes.size()));
+        for (size_t batch = 1; batch <= 10; batch++) {
+            std::vector<size_t> cut;
+            std::vector<uint64_t> in((n + batch - 1) / batch, 0), out((n + batch - 1) / batch, 0);
+            for (size_t i = 0; i < n; i++) {
+                if (i % batch == 0) cut.push_back(i);
+                in[i / batch] += 18 + f.mem[i].in_len + 8;
+                out[i / batch] += f.mem[i].out_len;
+            }
+            cut.push_back(n);
+            const BgzfBatchPlan plan = bgzf_batch_plan(f.mem, batch);
+            CHECK(plan.cut == cut && plan.batches() == in.size());
+            CHECK(plan.max_in == *std::max_element(in.begin(), in.end()) && plan.max_out == *std::max_element(out.begin(), out.end()));
+        }
+    }
+    const BgzfBatchPlan none = bgzf_batch_plan({}, 3);                       // no member: no batch, nothing to hold
+    CHECK(none.cut == std::vector<size_t>{0} && none.batches() == 0 && none.max_in == 0 && none.max_out == 0);
+}
+
+void test_bgzf_reader()
+{
+    const std::vector<std::string> five{some_text(300, 1), some_text(211, 2), some_text(640, 3), some_text(1, 4), some_text(455, 5)};
+    std::vector<std::string> seven_texts = five;
+    seven_texts.insert(seven_texts.begin() + 3, std::string());              // an empty member in the middle, the EOF member last: 7
+    const BgzfFile none({}, false), one({some_text(333, 6)}, false), seven(seven_texts, true), no_eof({five[0], five[1], five[2], five[4]}, false);
+    CHECK(none.mem.empty() && one.mem.size() == 1 && seven.mem.size() == 7 && seven.mem[3].out_len == 0 && seven.mem[6].out_len == 0 && no_eof.mem.size() == 4);
+    CHECK(no_eof.mem.back().out_len != 0);
+    for (const BgzfFile *f : {&none, &one, &seven, &no_eof})
+        for (size_t batch : batch_sizes(f->mem.size()))
+            for (bool resident : {false, true}) CHECK(read_all(*f, batch, resident) == 0);
+    CHECK(read_all(seven, 2, false, true) == 0);                             // a timed run: three waits per batch
+    CHECK(read_all(seven, 3, true, true) == 0);
+
+    // members the device refuses, two of them empty: the host's decoder, the same text, three counted
+    for (size_t batch : batch_sizes(7))
+        for (bool resident : {false, true}) {
+            stub.refuse = {0, 3, 6};
+            CHECK(read_all(seven, batch, resident) == 3);
+        }
+    stub.refuse.clear();
+
+    // a refused member that the host cannot inflate either; a member whose trailer states another CRC-32
+    BgzfFile damaged = seven, wrong_crc = seven;
+    damaged.bytes[damaged.mem[2].in_off] = 0x07;                             // (a last block of the reserved type)
+    wrong_crc.bytes[wrong_crc.mem[4].in_off + wrong_crc.mem[4].in_len + 1] ^= 0x10;
+    damaged.index();
+    wrong_crc.index();
+    for (size_t batch : batch_sizes(7))
+        for (bool resident : {false, true}) {
+            stub.refuse = {2};
+            CHECK(fault_of(damaged, batch, resident) == std::make_pair(static_cast<int>(BgzfMemberFault::refused), damaged.start(2)));
+            stub.refuse.clear();
+            CHECK(fault_of(damaged, batch, resident) == std::make_pair(static_cast<int>(BgzfMemberFault::refused), damaged.start(2)));     // (refused by zlib too)
+            CHECK(fault_of(wrong_crc, batch, resident) == std::make_pair(static_cast<int>(BgzfMemberFault::crc), wrong_crc.start(4)));
+            CHECK(fault_of(seven, batch, resident) == std::make_pair(-1, uint64_t{0}));
+        }
+    CHECK(damaged.start(2) > 0 && wrong_crc.start(4) > damaged.start(2));
+
+    // no room at each of the reader's allocations: the consumer's text and name, nothing left behind
+    const BgzfBatchPlan plan = bgzf_batch_plan(seven.mem, 3);
+    std::vector<uint8_t> stream(seven.text.size() + 64);
+    for (bool resident : {false, true})
+        for (int k = 1; k <= (resident ? 2 : 3); k++) {
+            stub.reset();
+            stub.fail_malloc = k;
+            std::string said;
+            try {
+                read_bgzf_batches(ctx, resident ? kBamStyle : kFastqStyle, false, seven.bytes.data(), seven.bytes.size(), seven.mem, plan,
+                                  resident ? stream.data() : nullptr, [](const BgzfBatch &) {});
+            } catch (const DeviceNoRoom &e) { said = e.what(); }
+            const char *name = resident ? (k == 1 ? kBamStyle.compressed : kBamStyle.table) : (k == 1 ? kFastqStyle.compressed : k == 2 ? kFastqStyle.inflated : kFastqStyle.table);
+            const size_t bytes = k == (resident ? 2 : 3) ? MemberTable::kBytes : static_cast<size_t>(k == 1 ? plan.max_in : plan.max_out) + 64;
+            CHECK(said == (resident ? kStyles[0] : kStyles[5]).want(std::to_string(bytes), name));
+            CHECK(stub.mallocs == k && stub.live.empty() && stub.bad_frees == 0);
+        }
+
+    std::string said;                                                        // the failed call of fastq_gz.hpp / depth_read.hpp, in their words
+    try { ck_device_error(-1, "member status"); } catch (const std::runtime_error &e) { said = e.what(); }
+    CHECK(said == "device error (member status): out of memory (stub)");
+    ck_device_error(0, "fine");
+    const uint8_t four[4] = {0x78, 0x56, 0x34, 0x12};
+    CHECK(le32(four) == 0x12345678u);
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -646,6 +863,8 @@ int main(int argc, char **argv)
     test_text_input(argv[1]);
     test_member_arithmetic();
     test_stored_member();
+    test_bgzf_plan();
+    test_bgzf_reader();
     std::printf("%s %d\n", failed ? "failed" : "ok", checks);
     return failed ? 1 : 0;
 }

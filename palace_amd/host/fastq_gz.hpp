@@ -1,8 +1,7 @@
 // eref's compressed inputs: a FASTQ file given as gzip (BGZF or any other) becomes part of ONE ASCII read set in HBM -- side 2's
 // reads behind side 1's, as the plain path has them -- and is counted from there.
-//   BGZF: the compressed bytes go up a window of members at a time, palace_bgzf_inflate inflates them (a member the device
-//         refuses: inflate_member on the host, uploaded), palace_crc32_members checks every member against its trailer, and
-//         palace_fastq_parse appends the window's sequence lines to the read set.  The text never leaves the device.
+//   BGZF: the batch reader of bgzf_read_device.hpp inflates and CRC-checks the members on the device, a batch at a time, and
+//         palace_fastq_parse appends each batch's sequence lines to the read set.  The text never leaves the device.
 //   other gzip: palace_gzip_inflate cuts the DEFLATE stream at block starts it finds, inflates the chunks on the device, checks
 //         CRC-32 and ISIZE of every member and hands the text to the parser.  What it declines (damaged input, a stream it cannot
 //         cut) goes through zlib on a host thread of its own (headers, CRC-32 and ISIZE of every member checked by zlib), the text
@@ -28,7 +27,7 @@
 #include <vector>
 
 #include "../../include/palace_hip.h"
-#include "bam_device.hpp"
+#include "bgzf_read_device.hpp"
 #include "device_scope.hpp"
 #include "fastx.hpp"
 
@@ -118,10 +117,7 @@ public:
     {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
     }
-    void ck(int rc, const char *what)
-    {
-        if (rc) throw std::runtime_error(std::string("device error (") + what + "): " + palace_last_error());
-    }
+    void ck(int rc, const char *what) { ck_device_error(rc, what); }
 
 private:
     void grow(int64_t bases_cap, int64_t offsets_cap)
@@ -171,70 +167,28 @@ inline void ingest_plain(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t
 inline void ingest_bgzf(DeviceReadSet &rs, palace_ctx *ctx, const MappedText &t, const std::vector<BgzfMember> &mem, const std::string &path)
 {
     rs.start_file();
-    const uint8_t *file = reinterpret_cast<const uint8_t *>(t.data);
     const int64_t W = rs.window();
-    // Members are inflated kMemberBatch at a time (bam_device.hpp); the parser takes a batch's text a window at a time.  Device memory:
-    // <= kMemberBatch x 64 KiB of text.
-    std::vector<size_t> cut{0};                                              // batches [cut[k], cut[k + 1])
-    uint64_t max_in = 0, batch_out = 0;
-    auto member_start = [&](size_t i) { return i ? mem[i - 1].in_off + mem[i - 1].in_len + 8 : uint64_t{0}; };
-    for (size_t i = 0, out = 0; i < mem.size(); i++) {
-        if (i - cut.back() == kMemberBatch) { cut.push_back(i); out = 0; }
-        out += mem[i].out_len;
-        batch_out = std::max<uint64_t>(batch_out, out);
-        max_in = std::max<uint64_t>(max_in, mem[i].in_off + mem[i].in_len + 8 - member_start(cut.back()));
-    }
-    cut.push_back(mem.size());
-    DeviceScope dev(ctx, no_room_device_error);
-    void *d_in = dev.alloc(static_cast<size_t>(max_in) + 64, "compressed window"), *d_batch = dev.alloc(static_cast<size_t>(batch_out) + 64, "inflated window");
-    void *d_meta = dev.alloc(MemberTable::kBytes, "member table");
-    MemberTable tab{ctx, static_cast<uint8_t *>(d_meta)};
-    std::vector<uint8_t> host_out(65536);
-    uint64_t file_pos = 0;
-    for (size_t k = 0; k + 1 < cut.size(); k++) {
-        const size_t i0 = cut[k], n = cut[k + 1] - i0;
-        if (n == 0) continue;
-        const uint64_t in0 = member_start(i0), in1 = mem[i0 + n - 1].in_off + mem[i0 + n - 1].in_len + 8;
-        tab.fill(&mem[i0], n, in0);
-        const int64_t *out_off = tab.out_off(tab.host.data());
-        int32_t *status = tab.status(tab.host.data());
-        uint32_t *crc = tab.crc(tab.host.data());
-        const int64_t out = out_off[n - 1] + static_cast<int64_t>(mem[i0 + n - 1].out_len);
-        auto t0 = std::chrono::steady_clock::now();
-        rs.ck(palace_h2d(ctx, d_in, file + in0, static_cast<size_t>(in1 - in0)), "compressed upload");
-        rs.ck(palace_h2d(ctx, d_meta, tab.host.data(), tab.up_bytes()), "member table");
-        rs.times.h2d += DeviceReadSet::ms_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        rs.ck(tab.inflate(static_cast<const uint8_t *>(d_in), static_cast<uint8_t *>(d_batch)), "palace_bgzf_inflate");
-        rs.ck(palace_d2h(ctx, status, tab.status(tab.dev), 4 * n), "member status");
-        for (size_t j = 0; j < n; j++) {                                     // what the device refused: the host's decoder, zlib behind it
-            if (status[j] == 0) continue;
-            const BgzfMember &m = mem[i0 + j];
-            if (!inflate_member(file, t.size, m, host_out.data()))
-                throw std::runtime_error(path + ": the BGZF member at offset " + std::to_string(member_start(i0 + j)) + " cannot be inflated");
-            if (m.out_len) rs.ck(palace_h2d(ctx, static_cast<uint8_t *>(d_batch) + out_off[j], host_out.data(), m.out_len), "inflated upload");
-        }
-        rs.times.inflate += DeviceReadSet::ms_since(t0);
-        t0 = std::chrono::steady_clock::now();
-        rs.ck(tab.crc32(static_cast<const uint8_t *>(d_batch)), "palace_crc32_members");
-        rs.ck(palace_d2h(ctx, crc, tab.crc(tab.dev), 4 * n), "member CRC");
-        for (size_t j = 0; j < n; j++) {
-            const BgzfMember &m = mem[i0 + j];
-            uint32_t want;
-            std::memcpy(&want, file + m.in_off + m.in_len, 4);
-            if (crc[j] != want)
-                throw std::runtime_error(path + ": CRC-32 mismatch in the BGZF member at offset " + std::to_string(member_start(i0 + j)));
-        }
-        rs.times.crc += DeviceReadSet::ms_since(t0);
-        // the batch's text through the parser, a window at a time (windows start 16-byte aligned: W is a multiple of 16)
-        file_pos = in1;
-        const bool last_batch = file_pos == t.size;
-        int64_t p = 0;
-        do {
-            const int64_t w = std::min(W, out - p);
-            rs.parse_at(static_cast<uint8_t *>(d_batch) + p, w, last_batch && p + w == out);
-            p += w;
-        } while (p < out);
+    // Members are inflated and checked kMemberBatch at a time (bgzf_read_device.hpp); the parser takes a batch's text a window at a
+    // time.  Device memory: <= kMemberBatch x 64 KiB of text.
+    const BgzfReadStyle style{no_room_device_error, ck_device_error, "compressed window", "inflated window", "member table"};
+    try {
+        const BgzfReadStats st = read_bgzf_batches(ctx, style, rs.timed(), reinterpret_cast<const uint8_t *>(t.data), t.size, mem,
+                                                   bgzf_batch_plan(mem, kMemberBatch), nullptr, [&](const BgzfBatch &b) {
+            // The file's last line is closed by the batch that ends with the file's last byte.  (classify_fastq takes a file as BGZF
+            // only when its last member ends there, so today this is the last batch; a caller that let stray bytes follow the last
+            // member would never see its last line closed through this flag.)
+            const bool last_batch = b.in1 == t.size;
+            int64_t p = 0;
+            do {                                                             // (windows start 16-byte aligned: W is a multiple of 16)
+                const int64_t w = std::min(W, b.out_bytes - p);
+                rs.parse_at(b.d_text + p, w, last_batch && p + w == b.out_bytes);
+                p += w;
+            } while (p < b.out_bytes);
+        });
+        rs.times.h2d += st.upload; rs.times.inflate += st.inflate; rs.times.crc += st.crc;
+    } catch (const BgzfMemberFault &f) {
+        if (f.kind == BgzfMemberFault::refused) throw std::runtime_error(path + ": the BGZF member at offset " + std::to_string(f.offset) + " cannot be inflated");
+        throw std::runtime_error(path + ": CRC-32 mismatch in the BGZF member at offset " + std::to_string(f.offset));
     }
 }
 

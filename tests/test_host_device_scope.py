@@ -1,5 +1,5 @@
-"""host/device_scope.hpp, host/mapped_file.hpp and the arithmetic of host/bgzf_members_device.hpp -- the device plumbing every host
-executable shares -- driven by the stand-alone `device_scope_selftest`, as built and under ASan + UBSan.  The program links no
+"""host/device_scope.hpp, host/mapped_file.hpp, the arithmetic of host/bgzf_members_device.hpp and the BGZF batch reader of
+host/bgzf_read_device.hpp -- the device plumbing every host executable shares -- driven by the stand-alone `device_scope_selftest`, as built and under ASan + UBSan.  The program links no
 libpalace_hip.so: the library calls the headers make are stubs of its own that count calls, remember what is live and fail on demand
 (the cases are listed in palace_amd/host/device_scope_selftest_main.cpp)."""
 import os
