@@ -1302,6 +1302,36 @@ int palace_readqc_plan(palace_ctx *ctx, const uint8_t *d_text1, const int64_t *d
 int palace_readqc_write(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, const int32_t *d_len, const int64_t *d_off,
                         int64_t n_pairs, int64_t lo, int64_t hi, uint8_t *d_out);
 
+/* ---- readqc --full-report: what the QC report counts (the rules: csrc/fastq_rules.hpp, "the report") ---------------------------- */
+
+#define PALACE_READQC_ISIZE_MAX 512   /* insert sizes 0 .. 511 have a slot of their own; slot 512 is "unknown" (no overlap, or longer) */
+#define PALACE_READQC_SLOTS 5         /* the base slots of every per-cycle table: A C G T N */
+
+/* palace_readqc_plan with one more output: d_cand (NULL, or n_pairs entries) gets every pair's first accepted candidate in search
+ * order, dropped pairs included; -1 for none, under no_trim, and for a pair that is not staged (not a text palace_fastq_records
+ * passed).  With NULL it is palace_readqc_plan. */
+int palace_readqc_plan_ex(palace_ctx *ctx, const uint8_t *d_text1, const int64_t *d_line_start1, const uint8_t *d_text2,
+                          const int64_t *d_line_start2, int64_t n_pairs, const palace_readqc_params *prm, int32_t *d_len1, int32_t *d_len2,
+                          int64_t *d_off1, int64_t *d_off2, int32_t *d_cand, int64_t *out);
+
+/* The histogram of the pairs' insert sizes (fastq_insert_size of d_cand[i] and the two SEQ lengths, taken from the line starts):
+ * d_hist[0 .. PALACE_READQC_ISIZE_MAX] is set, not added to.  A thread per pair, a histogram in LDS per workgroup.  n_pairs = 0 leaves
+ * zeros.  Enqueues only. */
+int palace_readqc_insert_sizes(palace_ctx *ctx, const int64_t *d_line_start1, const int64_t *d_line_start2, const int32_t *d_cand,
+                               int64_t n_pairs, const palace_readqc_params *prm, uint64_t *d_hist);
+
+/* The per-cycle counts of one text (n_records records of 4 lines, max_cycles in 0 .. PALACE_FASTQ_MAX_SEQ; bases at cycles >=
+ * max_cycles are not counted).  d_out is set, not added to: one section "before" (every base of every read), and, where d_len is not
+ * NULL, a second one "after" behind it (cycle c of record r iff d_len[r] >= 0 and c < d_len[r]).  A section is
+ * PALACE_READQC_SECTION_WORDS(max_cycles) words of 64 bits:
+ *     cnt [max_cycles][5]   the bases of slot A C G T N at the cycle
+ *     qsum[max_cycles][5]   the sum of their QUAL values (byte - 33)
+ *     q20, q30              QUAL bytes >= 33 + 20, >= 33 + 30
+ * SEQ and QUAL are read once, 64 neighbouring bytes a wavefront; global memory is written once per thread.  Enqueues only. */
+#define PALACE_READQC_SECTION_WORDS(max_cycles) (2 * PALACE_READQC_SLOTS * (int64_t)(max_cycles) + 2)
+int palace_readqc_cycle_stats(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, int64_t n_records, const int32_t *d_len,
+                              int32_t max_cycles, uint64_t *d_out);
+
 #ifdef __cplusplus
 }
 #endif

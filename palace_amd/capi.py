@@ -116,6 +116,8 @@ class ReadqcParams(C.Structure):
 
 READQC_OUT = ("reads_before", "bases_before", "reads_after", "bases_after", "low_quality", "too_many_n", "too_short", "trimmed_reads", "trimmed_bases",
               "bytes_1", "bytes_2")                # PALACE_READQC_* of include/palace_hip.h
+READQC_ISIZE_MAX = 512  # PALACE_READQC_ISIZE_MAX: the insert-size histogram's "unknown" slot
+READQC_CYCLE_TILE = 256  # kCycleTile of csrc/readqc.hip: the cycles a workgroup of palace_readqc_cycle_stats owns
 
 assert CAND_DTYPE.itemsize == 64 and EDGE_DTYPE.itemsize == 32 and SA_ITEM_DTYPE.itemsize == 32 and C.sizeof(ReadqcParams) == 48
 
@@ -290,6 +292,10 @@ _SIGS = {
     "palace_readqc_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ReadqcParams), C.c_void_p, C.c_void_p, C.c_void_p,
                            C.c_void_p, C.POINTER(C.c_int64)],
     "palace_readqc_write": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_int64, C.c_void_p],
+    "palace_readqc_plan_ex": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ReadqcParams), C.c_void_p, C.c_void_p, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)],
+    "palace_readqc_insert_sizes": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(ReadqcParams), C.c_void_p],
+    "palace_readqc_cycle_stats": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
     "palace_contig_features_scratch_bytes": [C.c_int64, C.c_int64],    # (returns size_t: restype set below)
     "palace_contig_features": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_size_t],
@@ -1254,13 +1260,14 @@ def sam_encode(ctx: Ctx, text: bytes, starts, n_header: int, names, mask: int, h
 
 
 class Readqc:
-    """Two FASTQ texts on the device with their line starts (palace_sam_lines), and the three calls of readqc over them:
+    """Two FASTQ texts on the device with their line starts (palace_sam_lines), and the calls of readqc over them:
     records() -> per text (records, bad line, code, seq_len int32); plan(prm) -> dict of len1, len2 int32, off1, off2 int64 (pairs + 1) and
-    the READQC_OUT numbers; write(which, lo, hi, guard) -> guard bytes of 0xAA, the window's bytes, guard bytes of 0xAA."""
+    the READQC_OUT numbers; write(which, lo, hi, guard) -> guard bytes of 0xAA, the window's bytes, guard bytes of 0xAA; the report's
+    plan_ex, insert_sizes and cycle_stats."""
 
     def __init__(self, ctx: Ctx, text1: bytes, text2: bytes):
         self.ctx, self.bufs, self.text, self.starts, self.n_lines = ctx, [], [], [], []
-        self.d_len = self.d_off = None
+        self.d_len = self.d_off = self.d_cand = None
         for text in (bytes(text1), bytes(text2)):
             n = len(text)
             nscr = int(lib().palace_sam_scratch_bytes(n))
@@ -1300,6 +1307,75 @@ class Readqc:
         res = {k: int(v) for k, v in zip(READQC_OUT, out)}
         res.update(len1=self.d_len[0].to_host()[:n].copy(), len2=self.d_len[1].to_host()[:n].copy(), off1=self.d_off[0].to_host()[:n + 1].copy(),
                    off2=self.d_off[1].to_host()[:n + 1].copy())
+        return res
+
+    def plan_ex(self, prm: "ReadqcParams | None" = None, with_cand: bool = True):
+        """palace_readqc_plan_ex -> plan()'s dict and, with_cand, cand int32 (the array stays on the device for insert_sizes); without it
+        the call is made with NULL"""
+        n = self.n_lines[0] // 4
+        assert self.n_lines[1] // 4 == n
+        prm = prm or ReadqcParams.default()
+        if self.d_len is None:
+            self.d_len = [self.ctx.empty(max(1, n), np.int32) for _ in range(2)]
+            self.d_off = [self.ctx.empty(n + 1, np.int64) for _ in range(2)]
+            self.bufs += self.d_len + self.d_off
+        if with_cand and self.d_cand is None:
+            self.d_cand = self.ctx.upload(np.full(max(1, n), -7, np.int32))     # (an entry the call leaves is seen)
+            self.bufs.append(self.d_cand)
+        out = (C.c_int64 * len(READQC_OUT))()
+        _check(lib().palace_readqc_plan_ex(self.ctx.h, self.text[0].ptr, self.starts[0].ptr, self.text[1].ptr, self.starts[1].ptr, n, C.byref(prm),
+                                           self.d_len[0].ptr, self.d_len[1].ptr, self.d_off[0].ptr, self.d_off[1].ptr, self.d_cand.ptr if with_cand else None, out),
+               "palace_readqc_plan_ex")
+        res = {k: int(v) for k, v in zip(READQC_OUT, out)}
+        res.update(len1=self.d_len[0].to_host()[:n].copy(), len2=self.d_len[1].to_host()[:n].copy(), off1=self.d_off[0].to_host()[:n + 1].copy(),
+                   off2=self.d_off[1].to_host()[:n + 1].copy())
+        if with_cand:
+            res["cand"] = self.d_cand.to_host()[:n].copy()
+        return res
+
+    def insert_sizes(self, prm: "ReadqcParams | None" = None, cand=None):
+        """palace_readqc_insert_sizes over plan_ex's candidates (or `cand`, int32 per pair) -> uint64[513]"""
+        n = self.n_lines[0] // 4
+        prm = prm or ReadqcParams.default()
+        d_cand = self.ctx.upload(np.ascontiguousarray(cand, dtype=np.int32)) if cand is not None and n else self.d_cand
+        d_hist = self.ctx.upload(np.full(READQC_ISIZE_MAX + 1, 0xAAAA, np.uint64))       # (the call sets, it does not add)
+        try:
+            assert n == 0 or d_cand is not None
+            _check(lib().palace_readqc_insert_sizes(self.ctx.h, self.starts[0].ptr, self.starts[1].ptr, d_cand.ptr if n else None, n, C.byref(prm), d_hist.ptr),
+                   "palace_readqc_insert_sizes")
+            self.ctx.sync()
+            return d_hist.to_host().copy()
+        finally:
+            d_hist.free()
+            if cand is not None and n:
+                d_cand.free()
+
+    def cycle_stats(self, which: int, max_cycles: int, after: bool = True, lens=None, guard: int = 8):
+        """palace_readqc_cycle_stats of text `which` -> [before, after] (or [before] where `after` is off: d_len NULL), each a dict of
+        cnt, qsum uint64 (max_cycles, 5), q20, q30; `after` takes `lens` (int32 per record) or the kept lengths plan() / plan_ex() left.
+        Behind the sections lie `guard` words that the call must leave alone."""
+        n = self.n_lines[which] // 4
+        words = 10 * max_cycles + 2
+        n_sec = 2 if after else 1
+        d_len = None
+        if after:
+            d_len = self.ctx.upload(np.ascontiguousarray(lens, dtype=np.int32)) if lens is not None else self.d_len[which]
+        d_out = self.ctx.upload(np.full(n_sec * words + guard, 0xAAAA, np.uint64))
+        try:
+            _check(lib().palace_readqc_cycle_stats(self.ctx.h, self.text[which].ptr if n else None, self.starts[which].ptr if n else None, n,
+                                                   d_len.ptr if after else None, max_cycles, d_out.ptr), "palace_readqc_cycle_stats")
+            self.ctx.sync()
+            got = d_out.to_host().copy()
+        finally:
+            d_out.free()
+            if after and lens is not None:
+                d_len.free()
+        assert np.all(got[n_sec * words:] == 0xAAAA), "palace_readqc_cycle_stats wrote behind its sections"
+        res = []
+        for s in range(n_sec):
+            sec = got[s * words:(s + 1) * words]
+            res.append({"cnt": sec[:5 * max_cycles].reshape(max_cycles, 5), "qsum": sec[5 * max_cycles:10 * max_cycles].reshape(max_cycles, 5),
+                        "q20": int(sec[-2]), "q30": int(sec[-1])})
         return res
 
     def write(self, which: int, lo: int, hi: int, guard: int = 32) -> bytes:

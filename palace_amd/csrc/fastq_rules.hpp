@@ -1,8 +1,8 @@
 // The rules of `readqc` -- the driver's fastp call on a read pair (palace:358-363) -- stated once: the grammar of a FASTQ
-// record, the overlap search of a pair, the trim it gives, and the filter.  This one text is compiled by hipcc for the kernels of
-// readqc.hip -- where a wavefront owns a record or a pair and its lanes share the bytes and the candidates -- and by the host compiler
-// for host/fastq_rules_selftest_main.cpp, where the same pieces run one after the other.  fastp is not at hand, so these rules are the
-// behaviour (parity UNPINNED).
+// record, the overlap search of a pair, the trim it gives, the filter, and what the report counts.  This one text is compiled by
+// hipcc for the kernels of readqc.hip -- where a wavefront owns a record or a pair and its lanes share the bytes and the candidates --
+// and by the host compiler for host/fastq_rules_selftest_main.cpp, where the same pieces run one after the other.  fastp is not at
+// hand, so these rules are the behaviour (parity UNPINNED).
 //
 // Every function is a pure function of its arguments: no allocation, no library call, nothing of HIP.
 #pragma once
@@ -122,5 +122,27 @@ PALACE_FQ_FN int32_t fastq_pair_reason(int32_t r1, int32_t r2) { return r1 ? r1 
 
 // the bytes a kept pair's record takes in an output file: the name line, SEQ[0:n], line 2, QUAL[0:n], each with its LF
 PALACE_FQ_FN int64_t fastq_record_bytes(int64_t name_len, int64_t plus_len, int64_t n) { return name_len + plus_len + 2 * n + 4; }
+
+// ---- the report (readqc --full-report) --------------------------------------------------------------------------------------------------
+// Written from fastp's stats.cpp and peprocessor.cpp as remembered; like the rest, these rules are the behaviour (parity UNPINNED).
+// A base's slot in every per-cycle table: A C G T N = 0 .. 4 (the grammar admits nothing else).
+enum { kFastqSlots = PALACE_READQC_SLOTS };
+PALACE_FQ_FN int32_t fastq_base_slot(uint32_t c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : 4; }
+// a QUAL byte's value, and whether it counts as Q20 / Q30
+PALACE_FQ_FN uint32_t fastq_qual_value(uint32_t q) { return q - 33u; }
+PALACE_FQ_FN bool fastq_is_q20(uint32_t q) { return q >= 33u + 20u; }
+PALACE_FQ_FN bool fastq_is_q30(uint32_t q) { return q >= 33u + 30u; }
+
+// The insert size of a pair from its first accepted candidate (index c; -1: none): a forward candidate at offset o >= 1 is a fragment
+// longer than the overlap, L1 + L2 - n; at o = 0, and for every reverse candidate, the overlap is the fragment, n.  No candidate, and
+// anything beyond the histogram, is slot PALACE_READQC_ISIZE_MAX: "unknown".
+PALACE_FQ_FN int32_t fastq_insert_size(int32_t c, int32_t l1, int32_t l2, const palace_readqc_params &p)
+{
+    if (c < 0) return PALACE_READQC_ISIZE_MAX;
+    const FastqCand x = fastq_candidate(c, l1, l2, p);
+    const bool forward = c < fastq_forward_candidates(l1, p);
+    const int32_t size = forward && x.a0 >= 1 ? l1 + l2 - x.n : x.n;
+    return size > PALACE_READQC_ISIZE_MAX ? PALACE_READQC_ISIZE_MAX : size;
+}
 
 }  // namespace palace

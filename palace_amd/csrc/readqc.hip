@@ -19,6 +19,26 @@
 //
 // The writer's lanes are window_lanes.hpp's: a lane owns 16 bytes of the window and stores them once; the items are the pairs, an
 // item's text is the four lines of a read.
+//
+// The report (readqc --full-report).  The plan kernel gets no LDS for it: its 32 KiB are exactly five workgroups of a CU.  It only
+// stores the candidate it found (palace_readqc_plan_ex; the store is a template parameter, so palace_readqc_plan's kernel is the one
+// it was), and what is counted is counted by two kernels of their own.
+//   The cycles (palace_readqc_cycle_stats).  A workgroup of 256 threads owns a tile of 256 cycles (grid y) and a share of the reads
+//   (grid x, four neighbouring reads a step); thread t owns cycle 256 y + t, so a wavefront reads 64 neighbouring bytes of SEQ and 64 of
+//   QUAL of a read, and every byte is read once.  A thread's counters (5 counts, 5 QUAL sums, Q20, Q30) are 32-bit registers across all
+//   the reads its workgroup walks.  A second set counts the cycles BEHIND a read's kept length and "after" is the difference: an
+//   untrimmed read of a kept pair -- most reads -- is counted once, and a wavefront skips, as one, a read that ends before its cycles.
+//   A workgroup walks at most 2^31 / 2048 + 4 reads when the grid is at its cap and a QUAL value is at most 93, so no counter passes
+//   2^27.  The slot is compared, not indexed, so the counters stay registers (48 VGPRs, no scratch, 8 waves a SIMD).
+//   At the end a workgroup turns its counters through 5 KiB of LDS into the table's own order ([cycle][slot], 5 dwords a thread: stride
+//   5 is free of bank conflicts) and adds them with 64-bit atomics, 512 neighbouring bytes a wave instruction, zeros left out: 2048
+//   workgroups x 256 cycles x 20 words at the most, whatever the text's size.  The sums are integers: the order of the adds is
+//   nothing to the result.  Bytes: SEQ + QUAL once, 32 B of line starts a read and tile (uniform loads), 4 B of kept length.  The
+//   floor is HBM (1.12 GB a text of the 1M-contig sample: 0.14 ms); measured 1.78 ms with kept lengths (8 % of it), 1.58 ms without (9 %):
+//   the bound is instruction issue -- some 45 vector instructions a wavefront and read, half of the time -- and the two dependent
+//   loads of a step (the line starts, then the bytes), not memory (profiles/readqc.md).
+//   The insert sizes (palace_readqc_insert_sizes).  A thread takes a pair: two line starts of either text and the candidate in, one
+//   LDS atomic on the workgroup's 513 x 4 B histogram; the histogram leaves the workgroup once, zeros left out.
 #include "common.hpp"
 #include "fastq_rules.hpp"
 #include "window_lanes.hpp"
@@ -110,9 +130,11 @@ __device__ __forceinline__ void prefix_counts(const uint8_t *t, int64_t q0, cons
 
 struct PairSums { unsigned long long v[9]; };
 
+// kCand: the pair's candidate goes to cand[] (the report's insert sizes); without it this is the kernel as it was
+template <bool kCand>
 __global__ __launch_bounds__(kQcThreads) void readqc_plan_kernel(const uint8_t *t1, const int64_t *start1, const uint8_t *t2, const int64_t *start2, int64_t n_pairs,
                                                                  palace_readqc_params prm, int32_t *len1, int32_t *len2, int64_t *off1, int64_t *off2,
-                                                                 unsigned long long *sums)
+                                                                 unsigned long long *sums, int32_t *cand)
 {
     __shared__ uint8_t s_ab[kQcWaves][2][PALACE_FASTQ_MAX_SEQ];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -127,6 +149,7 @@ __global__ __launch_bounds__(kQcThreads) void readqc_plan_kernel(const uint8_t *
         if (w1 > PALACE_FASTQ_MAX_SEQ || w2 > PALACE_FASTQ_MAX_SEQ || w1 < 0 || w2 < 0 || a4 - 1 - a3 != w1 || b4 - 1 - b3 != w2) {
             // (not a text palace_fastq_records passed: nothing is staged, no QUAL byte is read)
             if (lane == 0) { len1[i] = len2[i] = -1; off1[i] = off2[i] = 0; }
+            if (kCand && lane == 0) cand[i] = -1;
             continue;
         }
         const int32_t l1 = static_cast<int32_t>(w1), l2 = static_cast<int32_t>(w2);
@@ -135,6 +158,7 @@ __global__ __launch_bounds__(kQcThreads) void readqc_plan_kernel(const uint8_t *
         for (int32_t j = lane; j < l2; j += kWave) B[j] = static_cast<uint8_t>(fastq_complement(t2[b1 + l2 - 1 - j]));
         wave_lds_sync();
         const int32_t c = prm.no_trim ? -1 : first_accepted(A, B, l1, l2, prm, lane);
+        if (kCand && lane == 0) cand[i] = c;                                 // (dropped pairs too: the insert size is the input's)
         const int32_t cut = fastq_trim_to(c, l1, l2, prm);
         const int32_t k1 = cut >= 0 && cut < l1 ? cut : l1, k2 = cut >= 0 && cut < l2 ? cut : l2;
         int32_t low1, nn1, low2, nn2;
@@ -210,6 +234,124 @@ __global__ __launch_bounds__(kTileThreads) void readqc_write_kernel(const uint8_
     l.store(out);
 }
 
+// ---- the report ------------------------------------------------------------------------------------------------------------------
+
+constexpr int kCycleTile = 256;                          // the cycles, and the threads, of a workgroup of the cycle statistics
+constexpr int kCycleReads = 4;                           // neighbouring reads whose bytes a thread has in flight
+constexpr int kCycleGridCap = kCUs * 8;                  // workgroups per cycle tile: the 32 waves of a CU (55 VGPRs)
+static_assert(kCycleGridCap >= 64, "the 32-bit counters: (2^31 / cap + kCycleReads) reads x 93 stays below 2^32");
+constexpr int kIsizeThreads = 256, kIsizeGridCap = kCUs * 4;
+
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, kWave);
+    return v;
+}
+
+struct CycleCounts { uint32_t cnt[kFastqSlots], qsum[kFastqSlots], q20, q30; };
+
+__device__ __forceinline__ void cycle_count(CycleCounts &c, bool on, uint32_t base, uint32_t qual)
+{
+    const int32_t slot = fastq_base_slot(base);
+    const uint32_t v = fastq_qual_value(qual);
+#pragma unroll
+    for (int k = 0; k < kFastqSlots; k++) {                                  // (compared, not indexed: the counters stay registers)
+        const bool hit = on && slot == k;
+        c.cnt[k] += hit ? 1u : 0u;
+        c.qsum[k] += hit ? v : 0u;
+    }
+    c.q20 += on && fastq_is_q20(qual) ? 1u : 0u;
+    c.q30 += on && fastq_is_q30(qual) ? 1u : 0u;
+}
+
+// the workgroup's counters of one table of one section -> sec[0 .. 5 * max_cycles), in the table's order through s_turn
+__device__ __forceinline__ void cycle_flush(const uint32_t (&mine)[kFastqSlots], uint32_t *s_turn, unsigned long long *table, int32_t tile0, int32_t max_cycles)
+{
+    __syncthreads();                                                         // (the table before this one is read)
+#pragma unroll
+    for (int k = 0; k < kFastqSlots; k++) s_turn[threadIdx.x * kFastqSlots + k] = mine[k];
+    __syncthreads();
+    const int32_t cycles = max_cycles - tile0 < kCycleTile ? max_cycles - tile0 : kCycleTile;
+    for (int32_t j = threadIdx.x; j < cycles * kFastqSlots; j += kCycleTile)
+        if (s_turn[j]) atomicAdd(&table[static_cast<int64_t>(tile0) * kFastqSlots + j], static_cast<unsigned long long>(s_turn[j]));
+}
+
+template <bool kAfter>
+__global__ __launch_bounds__(kCycleTile) void readqc_cycle_stats_kernel(const uint8_t *__restrict__ t, const int64_t *__restrict__ start, int64_t n_records,
+                                                                        const int32_t *__restrict__ len, int32_t max_cycles, unsigned long long *out)
+{
+    __shared__ uint32_t s_turn[kCycleTile * kFastqSlots];
+    const int32_t tile0 = static_cast<int32_t>(blockIdx.y) * kCycleTile, cycle = tile0 + static_cast<int32_t>(threadIdx.x);
+    const int32_t wave0 = __builtin_amdgcn_readfirstlane(cycle);            // the wavefront's first cycle: what it skips, it skips as one
+    const int64_t step = static_cast<int64_t>(gridDim.x) * kCycleReads;
+    CycleCounts before{}, lost{};                                            // lost: the cycles behind a read's kept length; after = before - lost
+    for (int64_t r0 = static_cast<int64_t>(blockIdx.x) * kCycleReads; r0 < n_records; r0 += step) {        // (uniform: the workgroup's reads)
+        uint32_t base[kCycleReads], qual[kCycleReads];
+        bool in[kCycleReads], cut[kCycleReads];
+#pragma unroll
+        for (int u = 0; u < kCycleReads; u++) {
+            const int64_t r = r0 + u;
+            in[u] = cut[u] = false;
+            base[u] = qual[u] = 0;
+            if (r >= n_records || wave0 >= max_cycles) continue;
+            const int64_t s1 = start[4 * r + 1], s2 = start[4 * r + 2], s3 = start[4 * r + 3], s4 = start[4 * r + 4];
+            const int64_t l = s2 - 1 - s1;
+            if (l <= wave0 || s4 - 1 - s3 != l) continue;                    // (a read that ends before the wave's cycles; or not a text palace_fastq_records passed)
+            in[u] = cycle < l && cycle < max_cycles;
+            if (in[u]) { base[u] = t[s1 + cycle]; qual[u] = t[s3 + cycle]; }
+            if (kAfter) cut[u] = in[u] && cycle >= len[r];                   // (-1, a dropped pair: every cycle is behind it)
+        }
+#pragma unroll
+        for (int u = 0; u < kCycleReads; u++) {
+            if (__ballot(in[u])) cycle_count(before, in[u], base[u], qual[u]);
+            if (kAfter && __ballot(cut[u])) cycle_count(lost, cut[u], base[u], qual[u]);        // (an untrimmed read of a kept pair is counted once)
+        }
+    }
+    CycleCounts after = before;
+    if (kAfter) {
+#pragma unroll
+        for (int k = 0; k < kFastqSlots; k++) { after.cnt[k] -= lost.cnt[k]; after.qsum[k] -= lost.qsum[k]; }
+        after.q20 -= lost.q20;
+        after.q30 -= lost.q30;
+    }
+    const int64_t tables = static_cast<int64_t>(kFastqSlots) * max_cycles, words = PALACE_READQC_SECTION_WORDS(max_cycles);
+    for (int s = 0; s < (kAfter ? 2 : 1); s++) {
+        const CycleCounts &c = s ? after : before;
+        unsigned long long *sec = out + s * words;
+        cycle_flush(c.cnt, s_turn, sec, tile0, max_cycles);
+        cycle_flush(c.qsum, s_turn, sec + tables, tile0, max_cycles);
+        const uint32_t n20 = wave_sum(c.q20), n30 = wave_sum(c.q30);
+        if ((threadIdx.x & 63) == 0) {
+            if (n20) atomicAdd(&sec[2 * tables], static_cast<unsigned long long>(n20));
+            if (n30) atomicAdd(&sec[2 * tables + 1], static_cast<unsigned long long>(n30));
+        }
+    }
+}
+
+__global__ __launch_bounds__(kIsizeThreads) void readqc_insert_sizes_kernel(const int64_t *__restrict__ start1, const int64_t *__restrict__ start2,
+                                                                            const int32_t *__restrict__ cand, int64_t n_pairs, palace_readqc_params prm,
+                                                                            unsigned long long *hist)
+{
+    __shared__ uint32_t s_hist[PALACE_READQC_ISIZE_MAX + 1];                 // (a workgroup strides at most 2^31 / 256 pairs: 32 bits hold them)
+    for (int j = threadIdx.x; j <= PALACE_READQC_ISIZE_MAX; j += kIsizeThreads) s_hist[j] = 0;
+    __syncthreads();
+    const int64_t stride = static_cast<int64_t>(gridDim.x) * kIsizeThreads;
+    for (int64_t i = static_cast<int64_t>(blockIdx.x) * kIsizeThreads + threadIdx.x; i < n_pairs; i += stride) {
+        const int64_t w1 = start1[4 * i + 2] - 1 - start1[4 * i + 1], w2 = start2[4 * i + 2] - 1 - start2[4 * i + 1];
+        int32_t size = PALACE_READQC_ISIZE_MAX;
+        if (w1 >= 0 && w2 >= 0 && w1 <= PALACE_FASTQ_MAX_SEQ && w2 <= PALACE_FASTQ_MAX_SEQ) {
+            const int32_t l1 = static_cast<int32_t>(w1), l2 = static_cast<int32_t>(w2), c = cand[i];
+            if (c < fastq_forward_candidates(l1, prm) + fastq_reverse_candidates(l2, prm)) size = fastq_insert_size(c, l1, l2, prm);
+        }
+        if (size < 0 || size > PALACE_READQC_ISIZE_MAX) size = PALACE_READQC_ISIZE_MAX;          // (whatever cand[] held, the slot is one of the 513)
+        atomicAdd(&s_hist[size], 1u);
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j <= PALACE_READQC_ISIZE_MAX; j += kIsizeThreads)
+        if (s_hist[j]) atomicAdd(&hist[j], static_cast<unsigned long long>(s_hist[j]));
+}
+
 }  // namespace
 }  // namespace palace
 
@@ -239,15 +381,20 @@ extern "C" int palace_fastq_records(palace_ctx *ctx, const uint8_t *d_text, cons
     return PALACE_OK;
 }
 
-extern "C" int palace_readqc_plan(palace_ctx *ctx, const uint8_t *d_text1, const int64_t *d_line_start1, const uint8_t *d_text2, const int64_t *d_line_start2,
-                                  int64_t n_pairs, const palace_readqc_params *prm, int32_t *d_len1, int32_t *d_len2, int64_t *d_off1, int64_t *d_off2, int64_t *out)
+static bool readqc_params_ok(const palace_readqc_params *prm)
+{
+    return prm->overlap_require >= 0 && prm->diff_limit >= 0 && prm->diff_pct >= 0 && prm->diff_pct <= 100 && prm->diff_window >= 0 &&
+           prm->diff_window <= PALACE_FASTQ_MAX_SEQ && prm->qualified_quality >= 0 && prm->qualified_quality <= 93 && prm->unqualified_percent >= 0 &&
+           prm->unqualified_percent <= 100 && prm->n_limit >= 0 && prm->min_length >= 0;
+}
+
+extern "C" int palace_readqc_plan_ex(palace_ctx *ctx, const uint8_t *d_text1, const int64_t *d_line_start1, const uint8_t *d_text2, const int64_t *d_line_start2,
+                                     int64_t n_pairs, const palace_readqc_params *prm, int32_t *d_len1, int32_t *d_len2, int64_t *d_off1, int64_t *d_off2,
+                                     int32_t *d_cand, int64_t *out)
 {
     PALACE_REQUIRE(ctx && n_pairs >= 0 && n_pairs < (1ll << 31) && prm && d_off1 && d_off2 && out, "bad argument");
     PALACE_REQUIRE(n_pairs == 0 || (d_text1 && d_text2 && d_line_start1 && d_line_start2 && d_len1 && d_len2), "null device pointer");
-    PALACE_REQUIRE(prm->overlap_require >= 0 && prm->diff_limit >= 0 && prm->diff_pct >= 0 && prm->diff_pct <= 100 && prm->diff_window >= 0 &&
-                       prm->diff_window <= PALACE_FASTQ_MAX_SEQ && prm->qualified_quality >= 0 && prm->qualified_quality <= 93 && prm->unqualified_percent >= 0 &&
-                       prm->unqualified_percent <= 100 && prm->n_limit >= 0 && prm->min_length >= 0,
-                   "a parameter out of range");
+    PALACE_REQUIRE(readqc_params_ok(prm), "a parameter out of range");
     PALACE_HIP_TRY(hipSetDevice(ctx->device));
     const int64_t nb = (n_pairs + kScanThreads - 1) / kScanThreads;
     const int rc = ensure_workspace(ctx, 2 * static_cast<size_t>(nb + 1) * sizeof(long long));
@@ -260,8 +407,8 @@ extern "C" int palace_readqc_plan(palace_ctx *ctx, const uint8_t *d_text1, const
         PALACE_HIP_TRY(hipMemsetAsync(d_off2, 0, sizeof(int64_t), ctx->stream));
     } else {
         const int64_t want = (n_pairs + kQcWaves - 1) / kQcWaves;
-        hipLaunchKernelGGL(readqc_plan_kernel, dim3(static_cast<unsigned>(want < kQcGridCap ? want : kQcGridCap)), dim3(kQcThreads), 0, ctx->stream, d_text1,
-                           d_line_start1, d_text2, d_line_start2, n_pairs, *prm, d_len1, d_len2, d_off1, d_off2, sums);
+        hipLaunchKernelGGL(d_cand ? readqc_plan_kernel<true> : readqc_plan_kernel<false>, dim3(static_cast<unsigned>(want < kQcGridCap ? want : kQcGridCap)),
+                           dim3(kQcThreads), 0, ctx->stream, d_text1, d_line_start1, d_text2, d_line_start2, n_pairs, *prm, d_len1, d_len2, d_off1, d_off2, sums, d_cand);
         hipLaunchKernelGGL(readqc_scan_kernel, dim3(static_cast<unsigned>(nb)), dim3(kScanThreads), 0, ctx->stream, n_pairs, d_off1, d_off2, sum1, sum2);
         hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sum1, nb);
         hipLaunchKernelGGL(block_sums_scan_kernel, dim3(1), dim3(kScanThreads), 0, ctx->stream, sum2, nb);
@@ -276,6 +423,45 @@ extern "C" int palace_readqc_plan(palace_ctx *ctx, const uint8_t *d_text1, const
     for (int k = 0; k < 9; k++) out[k] = static_cast<int64_t>(got[k]);
     out[PALACE_READQC_BYTES_1] = bytes[0];
     out[PALACE_READQC_BYTES_2] = bytes[1];
+    return PALACE_OK;
+}
+
+extern "C" int palace_readqc_plan(palace_ctx *ctx, const uint8_t *d_text1, const int64_t *d_line_start1, const uint8_t *d_text2, const int64_t *d_line_start2,
+                                  int64_t n_pairs, const palace_readqc_params *prm, int32_t *d_len1, int32_t *d_len2, int64_t *d_off1, int64_t *d_off2, int64_t *out)
+{
+    return palace_readqc_plan_ex(ctx, d_text1, d_line_start1, d_text2, d_line_start2, n_pairs, prm, d_len1, d_len2, d_off1, d_off2, nullptr, out);
+}
+
+extern "C" int palace_readqc_insert_sizes(palace_ctx *ctx, const int64_t *d_line_start1, const int64_t *d_line_start2, const int32_t *d_cand, int64_t n_pairs,
+                                          const palace_readqc_params *prm, uint64_t *d_hist)
+{
+    PALACE_REQUIRE(ctx && n_pairs >= 0 && n_pairs < (1ll << 31) && prm && d_hist, "bad argument");
+    PALACE_REQUIRE(n_pairs == 0 || (d_line_start1 && d_line_start2 && d_cand), "null device pointer");
+    PALACE_REQUIRE(readqc_params_ok(prm), "a parameter out of range");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    PALACE_HIP_TRY(hipMemsetAsync(d_hist, 0, (PALACE_READQC_ISIZE_MAX + 1) * sizeof(uint64_t), ctx->stream));
+    if (n_pairs == 0) return PALACE_OK;
+    const int64_t want = (n_pairs + kIsizeThreads - 1) / kIsizeThreads;
+    hipLaunchKernelGGL(readqc_insert_sizes_kernel, dim3(static_cast<unsigned>(want < kIsizeGridCap ? want : kIsizeGridCap)), dim3(kIsizeThreads), 0, ctx->stream,
+                       d_line_start1, d_line_start2, d_cand, n_pairs, *prm, reinterpret_cast<unsigned long long *>(d_hist));
+    PALACE_HIP_TRY(hipGetLastError());
+    return PALACE_OK;
+}
+
+extern "C" int palace_readqc_cycle_stats(palace_ctx *ctx, const uint8_t *d_text, const int64_t *d_line_start, int64_t n_records, const int32_t *d_len,
+                                         int32_t max_cycles, uint64_t *d_out)
+{
+    PALACE_REQUIRE(ctx && n_records >= 0 && n_records < (1ll << 31) && max_cycles >= 0 && max_cycles <= PALACE_FASTQ_MAX_SEQ && d_out, "bad argument");
+    PALACE_REQUIRE(n_records == 0 || (d_text && d_line_start), "null device pointer");
+    PALACE_HIP_TRY(hipSetDevice(ctx->device));
+    const size_t words = static_cast<size_t>(PALACE_READQC_SECTION_WORDS(max_cycles)) * (d_len ? 2 : 1);
+    PALACE_HIP_TRY(hipMemsetAsync(d_out, 0, words * sizeof(uint64_t), ctx->stream));
+    if (n_records == 0 || max_cycles == 0) return PALACE_OK;
+    const int64_t want = (n_records + kCycleReads - 1) / kCycleReads;
+    const dim3 grid(static_cast<unsigned>(want < kCycleGridCap ? want : kCycleGridCap), static_cast<unsigned>((max_cycles + kCycleTile - 1) / kCycleTile));
+    hipLaunchKernelGGL(d_len ? readqc_cycle_stats_kernel<true> : readqc_cycle_stats_kernel<false>, grid, dim3(kCycleTile), 0, ctx->stream, d_text, d_line_start,
+                       n_records, d_len, max_cycles, reinterpret_cast<unsigned long long *>(d_out));
+    PALACE_HIP_TRY(hipGetLastError());
     return PALACE_OK;
 }
 

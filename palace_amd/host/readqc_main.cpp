@@ -7,6 +7,10 @@
 // writes what comes back; no base is compared and no record is cut here.  fastp is not at hand: parity with it is UNPINNED.
 //   A gzip input (told by its first two bytes; BGZF or not) is inflated on the device by palace_gzip_inflate, whose sink appends the
 //   text to the buffer; where that declines the file, zlib inflates it on the host and decides it.
+//   --full-report (readqc's own; needs -j): the JSON gets fastp's layout -- Q20/Q30, GC, read lengths, the per-cycle quality and
+//   content curves of both reads before and after filtering, the insert sizes (DESIGN.md 8 "Reports").  Every count is the device's
+//   (palace_readqc_plan_ex, palace_readqc_cycle_stats, palace_readqc_insert_sizes); the host divides and prints.  Without the option
+//   the JSON is the ten integers it was.
 //   Each output is written to <name>.tmp and renamed when both are complete; on any failure no file is left and stdout is empty.
 // Needs a device: there is no host path.  The two texts, a pair of output windows and 96 B per pair (line starts, lengths, offsets) have
 // to fit the device; else the `does not fit` message, and no way around it.  Exit 0; 1 for a text outside the grammar (`readqc:
@@ -49,7 +53,8 @@ const char *fault_text(int code)
 }
 
 struct Options {
-    std::string in1, in2, out1, out2, json, html;
+    std::string in1, in2, out1, out2, json, html, command;
+    bool full_report = false;
     palace_readqc_params prm{15, 40, 5, 15, 0, 0, 0, 30, 5, 20, 50, 0};
 };
 
@@ -57,6 +62,7 @@ int usage(const std::string &why)
 {
     std::fprintf(stderr,
                  "usage: readqc -i <in1.fq[.gz]> -I <in2.fq[.gz]> -o <out1.fq> -O <out2.fq> [-w <threads>] [-j <report.json>] [-h <report.html>]\n"
+                 "              [--full-report]                                   (readqc's own; with -j: the QC report in fastp's JSON layout)\n"
                  "              [-q <quality 15>] [-u <percent 40>] [-n <N limit 5>] [-l <length 15>] [-A] [-Q] [-L]      (fastp's long forms too)\n"
                  "  fastp's defaults for paired input: overlap-based adapter trimming, quality, N and length filters (DESIGN.md 8).  Nothing else\n"
                  "  of fastp is taken: no polyG/polyX, quality cutting, base correction, UMI, dedup, merging, adapter sequences, single-end input\n"
@@ -163,9 +169,10 @@ DeviceText load_text(palace_ctx *ctx, DeviceScope &dev, const std::string &path,
     return t;
 }
 
-struct Lines { int64_t *d_start = nullptr; int64_t n_lines = 0, records = 0, bad_line = 0; int32_t code = 0; };
+struct Lines { int64_t *d_start = nullptr; int64_t n_lines = 0, records = 0, bad_line = 0; int32_t code = 0, longest = 0; };
 
-Lines lines_and_records(palace_ctx *ctx, DeviceScope &dev, const DeviceText &t)
+// longest: the longest read, for the report's cycle tables (asked for only then: the lengths come back, 4 bytes a read)
+Lines lines_and_records(palace_ctx *ctx, DeviceScope &dev, const DeviceText &t, bool want_longest)
 {
     Lines l;
     const palace_host::TextLines tl = palace_host::text_lines(ctx, dev, t.d, t.n, "the line starts");       // (the verdict in tl.res is a SAM's: it means nothing here)
@@ -174,14 +181,121 @@ Lines lines_and_records(palace_ctx *ctx, DeviceScope &dev, const DeviceText &t)
     int32_t *d_seq_len = dev.array<int32_t>(static_cast<size_t>(l.n_lines / 4), "the reads' lengths");
     int64_t v[3];
     HIP_OK(palace_fastq_records(ctx, t.d, l.d_start, l.n_lines, d_seq_len, v));
+    if (want_longest && v[2] == 0 && v[0] > 0) {
+        std::vector<int32_t> seq_len(static_cast<size_t>(v[0]));
+        HIP_OK(palace_d2h(ctx, seq_len.data(), d_seq_len, seq_len.size() * sizeof(int32_t)));
+        for (const int32_t n : seq_len) l.longest = n > l.longest ? n : l.longest;
+    }
     dev.give_back(d_seq_len);
     l.records = v[0]; l.bad_line = v[1]; l.code = static_cast<int32_t>(v[2]);
     return l;
 }
 
-void write_report(const Options &o, const int64_t *n)
+// ---- the full report -----------------------------------------------------------------------------------------------------------------
+// What the device counted: the plan's sums, the four sections of the two cycle_stats calls and the histogram.  Nothing is counted here.
+struct Section {                                                             // one section of palace_readqc_cycle_stats, as it lies in d_out
+    const uint64_t *w;
+    int32_t max_cycles;
+    uint64_t cnt(int32_t c, int slot) const { return w[static_cast<size_t>(c) * PALACE_READQC_SLOTS + slot]; }
+    uint64_t qsum(int32_t c, int slot) const { return w[static_cast<size_t>(max_cycles + c) * PALACE_READQC_SLOTS + slot]; }
+    uint64_t q20() const { return w[2 * static_cast<size_t>(max_cycles) * PALACE_READQC_SLOTS]; }
+    uint64_t q30() const { return w[2 * static_cast<size_t>(max_cycles) * PALACE_READQC_SLOTS + 1]; }
+    uint64_t at(int32_t c) const { uint64_t s = 0; for (int k = 0; k < PALACE_READQC_SLOTS; k++) s += cnt(c, k); return s; }
+    uint64_t bases() const { uint64_t s = 0; for (int32_t c = 0; c < max_cycles; c++) s += at(c); return s; }
+    uint64_t gc() const { uint64_t s = 0; for (int32_t c = 0; c < max_cycles; c++) s += cnt(c, 1) + cnt(c, 2); return s; }
+    int32_t cycles() const { int32_t n = max_cycles; while (n > 0 && at(n - 1) == 0) n--; return n; }       // the longest read of the section
+};
+struct FullCounts {
+    std::vector<uint64_t> stats[2], hist;                                    // per text: before, after; the 513 insert-size slots
+    int32_t max_cycles[2] = {0, 0};
+    Section section(int text, int after) const
+    {
+        return Section{stats[text].data() + static_cast<size_t>(after) * PALACE_READQC_SECTION_WORDS(max_cycles[text]), max_cycles[text]};
+    }
+};
+
+double ratio(uint64_t num, uint64_t den) { return den ? static_cast<double>(num) / static_cast<double>(den) : 0.0; }
+std::string num(uint64_t v) { return std::to_string(v); }
+std::string num(double v)                                                    // 17 digits: a parser reads back the double that was computed
 {
-    if (!o.json.empty()) {
+    char b[40];
+    std::snprintf(b, sizeof b, "%.17g", v);
+    return b;
+}
+std::string quoted(const std::string &s)
+{
+    std::string q = "\"";
+    for (const char ch : s) {
+        const unsigned char c = static_cast<unsigned char>(ch);
+        if (c == '"' || c == '\\') { q += '\\'; q += ch; }
+        else if (c < 0x20) { char b[8]; std::snprintf(b, sizeof b, "\\u%04x", c); q += b; }
+        else q += ch;
+    }
+    return q + "\"";
+}
+template <class F> std::string curve(const char *name, int32_t cycles, F value)
+{
+    std::string s = std::string("\t\t\t\"") + name + "\":[";
+    for (int32_t c = 0; c < cycles; c++) s += (c ? "," : "") + num(value(c));
+    return s + "]";
+}
+
+std::string read_block(const char *name, const Section &x, uint64_t reads)
+{
+    static const struct { const char *name; int slot; } kBases[] = {{"A", 0}, {"T", 3}, {"C", 1}, {"G", 2}, {"N", 4}};
+    const int32_t cycles = x.cycles();
+    std::string s = std::string("\t\"") + name + "\": {\n\t\t\"total_reads\":" + num(reads) + ",\n\t\t\"total_bases\":" + num(x.bases()) + ",\n\t\t\"q20_bases\":" +
+                    num(x.q20()) + ",\n\t\t\"q30_bases\":" + num(x.q30()) + ",\n\t\t\"total_cycles\":" + num(static_cast<uint64_t>(cycles)) + ",\n\t\t\"quality_curves\": {\n";
+    for (int b = 0; b < 4; b++) s += curve(kBases[b].name, cycles, [&](int32_t c) { return ratio(x.qsum(c, kBases[b].slot), x.cnt(c, kBases[b].slot)); }) + ",\n";
+    s += curve("mean", cycles, [&](int32_t c) { uint64_t q = 0; for (int k = 0; k < PALACE_READQC_SLOTS; k++) q += x.qsum(c, k); return ratio(q, x.at(c)); }) + "\n\t\t},\n";
+    s += "\t\t\"content_curves\": {\n";
+    for (int b = 0; b < 5; b++) s += curve(kBases[b].name, cycles, [&](int32_t c) { return ratio(x.cnt(c, kBases[b].slot), x.at(c)); }) + ",\n";
+    s += curve("GC", cycles, [&](int32_t c) { return ratio(x.cnt(c, 1) + x.cnt(c, 2), x.at(c)); }) + "\n\t\t}\n\t}";
+    return s;
+}
+
+std::string summary_block(const char *name, const Section &one, const Section &two, uint64_t reads_each)
+{
+    const uint64_t b1 = one.bases(), b2 = two.bases(), bases = b1 + b2, q20 = one.q20() + two.q20(), q30 = one.q30() + two.q30();
+    return std::string("\t\t\"") + name + "\": {\n\t\t\t\"total_reads\":" + num(2 * reads_each) + ",\n\t\t\t\"total_bases\":" + num(bases) + ",\n\t\t\t\"q20_bases\":" + num(q20) +
+           ",\n\t\t\t\"q30_bases\":" + num(q30) + ",\n\t\t\t\"q20_rate\":" + num(ratio(q20, bases)) + ",\n\t\t\t\"q30_rate\":" + num(ratio(q30, bases)) +
+           ",\n\t\t\t\"read1_mean_length\":" + num(reads_each ? b1 / reads_each : 0) + ",\n\t\t\t\"read2_mean_length\":" + num(reads_each ? b2 / reads_each : 0) +
+           ",\n\t\t\t\"gc_content\":" + num(ratio(one.gc() + two.gc(), bases)) + "\n\t\t}";
+}
+
+std::string full_report(const Options &o, const int64_t *n, const FullCounts &f)
+{
+    const auto plan = [&](int k) { return num(static_cast<uint64_t>(n[k])); };
+    const uint64_t pairs = static_cast<uint64_t>(n[PALACE_READQC_READS_BEFORE]) / 2, kept = static_cast<uint64_t>(n[PALACE_READQC_READS_AFTER]) / 2;
+    const Section before[2] = {f.section(0, 0), f.section(1, 0)}, after[2] = {f.section(0, 1), f.section(1, 1)};
+    std::string s = "{\n\t\"summary\": {\n\t\t\"readqc_version\": " + quoted(palace_version()) + ",\n\t\t\"sequencing\": \"paired end (" +
+                    std::to_string(before[0].cycles()) + " cycles + " + std::to_string(before[1].cycles()) + " cycles)\",\n";
+    s += summary_block("before_filtering", before[0], before[1], pairs) + ",\n" + summary_block("after_filtering", after[0], after[1], kept) + "\n\t},\n";
+    s += "\t\"filtering_result\": {\n\t\t\"passed_filter_reads\": " + plan(PALACE_READQC_READS_AFTER) + ",\n\t\t\"low_quality_reads\": " + plan(PALACE_READQC_LOW_QUALITY) +
+         ",\n\t\t\"too_many_N_reads\": " + plan(PALACE_READQC_TOO_MANY_N) + ",\n\t\t\"too_short_reads\": " + plan(PALACE_READQC_TOO_SHORT) +
+         ",\n\t\t\"too_long_reads\": 0\n\t},\n";
+    s += "\t\"adapter_cutting\": {\n\t\t\"adapter_trimmed_reads\": " + plan(PALACE_READQC_TRIMMED_READS) + ",\n\t\t\"adapter_trimmed_bases\": " +
+         plan(PALACE_READQC_TRIMMED_BASES) + "\n\t},\n";
+    int peak = 0;                                                            // the smallest index of the largest count among 0 .. 511
+    for (int k = 1; k < PALACE_READQC_ISIZE_MAX; k++)
+        if (f.hist[static_cast<size_t>(k)] > f.hist[static_cast<size_t>(peak)]) peak = k;
+    s += "\t\"insert_size\": {\n\t\t\"peak\": " + std::to_string(peak) + ",\n\t\t\"unknown\": " + num(f.hist[PALACE_READQC_ISIZE_MAX]) + ",\n\t\t\"histogram\":[";
+    for (int k = 0; k < PALACE_READQC_ISIZE_MAX; k++) s += (k ? "," : "") + num(f.hist[static_cast<size_t>(k)]);
+    s += "]\n\t},\n";
+    s += read_block("read1_before_filtering", before[0], pairs) + ",\n" + read_block("read2_before_filtering", before[1], pairs) + ",\n" +
+         read_block("read1_after_filtering", after[0], kept) + ",\n" + read_block("read2_after_filtering", after[1], kept) + ",\n";
+    return s + "\t\"command\": " + quoted(o.command) + "\n}\n";
+}
+
+void write_report(const Options &o, const int64_t *n, const FullCounts *full)
+{
+    if (full) {
+        const std::string text = full_report(o, n, *full);
+        std::FILE *f = std::fopen(o.json.c_str(), "wb");
+        if (!f) throw Failure("cannot write " + o.json);
+        const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
+        if ((std::fclose(f) != 0) | !ok) throw Failure("cannot write " + o.json);
+    } else if (!o.json.empty()) {
         std::FILE *f = std::fopen(o.json.c_str(), "wb");
         if (!f) throw Failure("cannot write " + o.json);
         std::fprintf(f,
@@ -212,7 +326,7 @@ void run(palace_ctx *ctx, const Options &o, palace_host::Trace &tr)
     DeviceText text[2];
     Lines lines[2];
     for (int k = 0; k < 2; k++) text[k] = load_text(ctx, dev, *in[k], tr);
-    for (int k = 0; k < 2; k++) lines[k] = lines_and_records(ctx, dev, text[k]);
+    for (int k = 0; k < 2; k++) lines[k] = lines_and_records(ctx, dev, text[k], o.full_report);
     tr.lap("lines cut, records validated");
     for (int k = 0; k < 2; k++)
         if (lines[k].code) throw Failure(*in[k] + ": line " + std::to_string(lines[k].bad_line) + ": " + fault_text(lines[k].code));
@@ -223,9 +337,29 @@ void run(palace_ctx *ctx, const Options &o, palace_host::Trace &tr)
     const size_t np = static_cast<size_t>(n_pairs);
     int32_t *d_len[2] = {dev.array<int32_t>(np, "the kept lengths"), dev.array<int32_t>(np, "the kept lengths")};
     int64_t *d_off[2] = {dev.array<int64_t>(np + 1, "the records' places"), dev.array<int64_t>(np + 1, "the records' places")};
+    int32_t *d_cand = o.full_report ? dev.array<int32_t>(np, "the pairs' candidates") : nullptr;
     int64_t n[PALACE_READQC_N_OUT];
-    HIP_OK(palace_readqc_plan(ctx, text[0].d, lines[0].d_start, text[1].d, lines[1].d_start, n_pairs, &o.prm, d_len[0], d_len[1], d_off[0], d_off[1], n));
+    HIP_OK(palace_readqc_plan_ex(ctx, text[0].d, lines[0].d_start, text[1].d, lines[1].d_start, n_pairs, &o.prm, d_len[0], d_len[1], d_off[0], d_off[1], d_cand, n));
     tr.lap("pairs planned");
+
+    FullCounts full;
+    if (o.full_report) {                                                     // the report's counts: two cycle_stats calls and the histogram, then one wait
+        uint64_t *d_stats[2], *d_hist = dev.array<uint64_t>(PALACE_READQC_ISIZE_MAX + 1, "the insert sizes");
+        for (int k = 0; k < 2; k++) {
+            full.max_cycles[k] = lines[k].longest;
+            full.stats[k].resize(2 * static_cast<size_t>(PALACE_READQC_SECTION_WORDS(full.max_cycles[k])));
+            d_stats[k] = dev.array<uint64_t>(full.stats[k].size(), "the cycle tables");
+            HIP_OK(palace_readqc_cycle_stats(ctx, text[k].d, lines[k].d_start, n_pairs, d_len[k], full.max_cycles[k], d_stats[k]));
+        }
+        HIP_OK(palace_readqc_insert_sizes(ctx, lines[0].d_start, lines[1].d_start, d_cand, n_pairs, &o.prm, d_hist));
+        full.hist.resize(PALACE_READQC_ISIZE_MAX + 1);
+        for (int k = 0; k < 2; k++) HIP_OK(palace_d2h(ctx, full.stats[k].data(), d_stats[k], full.stats[k].size() * sizeof(uint64_t)));
+        HIP_OK(palace_d2h(ctx, full.hist.data(), d_hist, full.hist.size() * sizeof(uint64_t)));
+        for (int k = 0; k < 2; k++) dev.give_back(d_stats[k]);
+        dev.give_back(d_hist);
+        dev.give_back(d_cand);
+        tr.lap("report counted");
+    }
 
     // windows of the output texts: window w is computed and copied back while window w - 1 goes to its file
     const int64_t total[2] = {n[PALACE_READQC_BYTES_1], n[PALACE_READQC_BYTES_2]};
@@ -239,7 +373,7 @@ void run(palace_ctx *ctx, const Options &o, palace_host::Trace &tr)
     }
     if (const std::string *bad = outputs.close()) throw Failure("cannot write " + *bad);
     tr.lap("outputs written");
-    write_report(o, n);
+    write_report(o, n, o.full_report ? &full : nullptr);
     if (const std::string *bad = outputs.rename()) throw Failure("cannot rename " + *bad);
     if (tr.on)
         std::fprintf(stderr, "[readqc] pairs %lld, kept %lld; text %lld + %lld B in, %lld + %lld B out; build %s\n", static_cast<long long>(n_pairs),
@@ -262,9 +396,12 @@ int main(int argc, char **argv)
     struct Flag { const char *shrt, *lng; int32_t *on; };
     const Flag flags[] = {{"-A", "--disable_adapter_trimming", &o.prm.no_trim}, {"-Q", "--disable_quality_filtering", &o.prm.no_quality_filter},
                           {"-L", "--disable_length_filtering", &o.prm.no_length_filter}};
+    for (int i = 1; i < argc; i++) o.command += std::string(i > 1 ? " " : "") + argv[i];
+    o.command = std::string("readqc") + (argc > 1 ? " " : "") + o.command;
     for (int i = 1; i < argc; i++) {
         const std::string a = argv[i];
         bool taken = false;
+        if (a == "--full-report") { o.full_report = taken = true; }
         for (const Flag &f : flags)
             if (a == f.shrt || a == f.lng) { *f.on = 1; taken = true; }
         for (const Valued &v : valued) {
@@ -287,6 +424,7 @@ int main(int argc, char **argv)
     }
     if (o.in1.empty() || o.in2.empty() || o.out1.empty() || o.out2.empty()) return usage("-i, -I, -o and -O are required (paired input only)");
     if (ends_with(o.out1, ".gz") || ends_with(o.out2, ".gz")) return usage(".gz output is not written");
+    if (o.full_report && o.json.empty()) return usage("--full-report needs -j: the report is the JSON file");
 
     return palace_host::device_tool("readqc", [&](palace_ctx *ctx, palace_host::Trace &tr) { run(ctx, o, tr); });
 }
