@@ -93,6 +93,14 @@ class BaiStatus(C.Structure):
 
 
 SORT_TILE = 4096        # PALACE_SORT_TILE: the keys one workgroup of palace_sort_u64 ranks per pass
+# the eref count partition (csrc/eref.hip, csrc/eref_common.hpp)
+EREF_BIN_THREADS = 512          # kBinThreads: lanes of a level-1 workgroup (a tile is kBinThreads * P positions, P = 6 or 8)
+EREF_L1_REPLICAS = 32           # kL1Replicas: regions per level-1 bucket; a tile writes to replica blockIdx.x % kL1Replicas
+EREF_GROUP_KEYS = 5             # kGroupKeys: keys of one 16-byte level-1 group
+EREF_TILE2_GROUPS = 5120        # kTile2Groups: groups one level-2 workgroup takes
+EREF_ROW_SLOTS = 72             # kRowSlots: slots of a level-2 staging row
+EREF_XCDS = 8                   # kXcds: sub-regions of a fine bucket's region
+EREF_COUNT_ROUND_VECTORS = 1024  # kBatch * kCountThreads: 8-key vectors one round of the count kernel's loop applies
 
 
 class FastaStatus(C.Structure):
