@@ -993,6 +993,50 @@ int palace_filter_result_plan(palace_ctx *ctx, const int32_t *d_code, const int6
 int palace_paths_first_of_equal(palace_ctx *ctx, const int32_t *d_code, const int64_t *d_path_off, int64_t n_paths, const uint8_t *d_class,
                                 int32_t hash_bits, uint8_t *d_first);
 
+/* ---- corrected_dup: borders, tandem candidates, the similarity relation, the base-set test (the rules: DESIGN.md 8) ---------- */
+
+/* Paths are integers here as for palace_cycle_trim: d_node[t] the id of a whole token, path p the tokens d_path_off[p] ..
+ * d_path_off[p + 1] (n_paths + 1 ascending entries; n_paths < 2^31; a path may be empty).  No path length and no path count is
+ * compiled in, every result is an integer and none depends on scheduling. */
+
+/* d_border[p] = the largest i in 1 .. n / 2 with path[0 .. i) == path[n - i .. n), token by token, or 0 when there is none (n:
+ * the path's tokens).  A workgroup owns a path, its waves take values of i, their lanes stride the i comparisons.  Enqueues only. */
+int palace_path_borders(palace_ctx *ctx, const int32_t *d_node, const int64_t *d_path_off, int64_t n_paths, int32_t *d_border);
+
+/* The tandem candidates of every path of fewer than 2^20 tokens.  For a period r = 1 .. n / 2 and a start s = 0 .. n - 2 r, R(r, s)
+ * is the number of consecutive q = s, s + 1, .. with q + r < n and path[q] == path[q + r]; (r, s) is a candidate when
+ * c = 1 + R / r (integer division) is 2 at least.  d_cand_off[p] (n_paths + 1 entries, always written): the candidates of the
+ * paths in front of p, the last entry their number, also in *n_cand_out.  With d_cand and cap >= that number, the candidates
+ * follow as three int32 each -- r, s, c -- per path in ascending (r, s); without d_cand nothing else is written, and a cap that is
+ * too small is refused: count with one call, fill with a second.  A workgroup owns a path and loops over the periods; R is a
+ * segmented suffix scan over the flags path[q] == path[q + r] (ballots inside a wave, the waves and the chunks joined through
+ * LDS), so a path of equal tokens costs what any other path of its length does, and no table of n x n entries exists.  The
+ * counts come from the context's workspace.  Waits for the stream for the count; the fill is enqueued. */
+int palace_path_tandems(palace_ctx *ctx, const int32_t *d_node, const int64_t *d_path_off, int64_t n_paths, int64_t *d_cand_off, int32_t *d_cand,
+                        int64_t cap, int64_t *n_cand_out);
+
+#define PALACE_PATHS_REL_NONE 0      /* a pair's two bits: the paths are not similar */
+#define PALACE_PATHS_REL_J_LOSES 1   /* similar, and S(i) > S(j) */
+#define PALACE_PATHS_REL_I_LOSES 2   /* similar, and S(i) <= S(j) */
+
+/* The similarity relation of n_paths < 2^15 paths over the tokens' lengths (d_len[t] in 0 .. 2^32 - 1, n_tok < 2^31).  D(p): the
+ * set of distinct lengths of p's tokens, S(p) their sum, I(i, j) the sum of D(i) intersected with D(j).  i < j are similar when
+ * 10 I >= 9 S(i) or 10 I >= 9 S(j) -- for sums below 2^49 exactly `(double)I / (double)S >= 0.9`; a call with a
+ * larger S is refused.  d_rel: palace_paths_length_relation_bytes(n_paths) bytes, all written; the pair (i, j), i < j, has the two
+ * bits 2 (k & 3) of byte k >> 2, k = i * n_paths + j; every other pair of bits is 0.  The distinct lengths come from one stable
+ * palace_sort_u64 of path << 32 | length and a scan of the flags `differs from the key before`; a lane owns a byte of d_rel and
+ * searches the shorter set's values in the longer.  Temporaries come from the context's workspace.  Waits for the stream. */
+size_t palace_paths_length_relation_bytes(int64_t n_paths);
+int palace_paths_length_relation(palace_ctx *ctx, const int64_t *d_len, int64_t n_tok, const int64_t *d_path_off, int64_t n_paths, uint8_t *d_rel);
+
+/* d_in[p] (n_paths entries): 1 when p >= n_cycles and the SET of p's values d_base[t] (>= 0; n_tok < 2^31) equals the set of one
+ * of the paths 0 .. n_cycles - 1, else 0.  Exact: the sets are compared as sorted lists of distinct values (the sort and scan of
+ * palace_paths_length_relation); the low hash_bits (0 .. 64; an executable passes 64) of a 64-bit hash of a list only bring
+ * candidates together, through a stable palace_sort_u64 of the cycles' hashes.  Two empty paths have equal sets.  Temporaries
+ * come from the context's workspace.  Waits for the stream once (the values' check). */
+int palace_paths_base_set_in(palace_ctx *ctx, const int32_t *d_base, int64_t n_tok, const int64_t *d_path_off, int64_t n_paths, int64_t n_cycles,
+                             int32_t hash_bits, uint8_t *d_in);
+
 /* ---- FASTG -> node FASTA and the `.fai` rows of both, on the device (split_fastg; the rules: DESIGN.md 8) -------------------- */
 
 /* Faults of a FASTG text beyond those of palace_fasta_index, reported in a palace_fasta_status like them */

@@ -279,6 +279,11 @@ _SIGS = {
                             C.POINTER(C.c_int64)],
     "palace_filter_result_plan": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p],
     "palace_paths_first_of_equal": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p],
+    "palace_path_borders": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p],
+    "palace_path_tandems": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.POINTER(C.c_int64)],
+    "palace_paths_length_relation_bytes": [C.c_int64],  # (returns size_t: restype set below)
+    "palace_paths_length_relation": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p],
+    "palace_paths_base_set_in": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p],
     "palace_bam_sort_keys": [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)],
     "palace_sort_u64_scratch_bytes": [C.c_int64],       # (returns size_t: restype set below)
     "palace_sort_u64": [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_size_t],
@@ -349,6 +354,7 @@ def lib() -> C.CDLL:
         _LIB.palace_sort_u64_scratch_bytes.restype = C.c_size_t
         _LIB.palace_sam_scratch_bytes.restype = C.c_size_t
         _LIB.palace_contig_features_scratch_bytes.restype = C.c_size_t
+        _LIB.palace_paths_length_relation_bytes.restype = C.c_size_t
     return _LIB
 
 
@@ -2071,3 +2077,81 @@ class FilterPlan:
     def free(self):
         for b in self.bufs:
             b.free()
+
+
+# ---- corrected_dup: borders, tandem candidates, the similarity relation, the base-set test --------------------------------------------
+
+PATHS_REL_NONE, PATHS_REL_J_LOSES, PATHS_REL_I_LOSES = 0, 1, 2     # PALACE_PATHS_REL_*
+
+
+class PathDedup:
+    """Paths as integers on the device (one value per token, path p = values[path_off[p]:path_off[p + 1]]) behind the four entry
+    points of csrc/path_dedup.hip.  What a value means is the call's: a token id for borders() and tandems(), a length for
+    length_relation(), a base id for base_set_in()."""
+
+    def __init__(self, ctx: Ctx, values, path_off, dtype=np.int32):
+        self.ctx = ctx
+        values = np.ascontiguousarray(values, dtype)
+        self.path_off = np.ascontiguousarray(path_off, np.int64)
+        self.n_paths, self.n_tok = len(self.path_off) - 1, len(values)
+        assert int(self.path_off[-1]) == self.n_tok
+        self.d_val = ctx.upload(values if self.n_tok else np.zeros(1, dtype))
+        self.d_off = ctx.upload(self.path_off)
+
+    def borders(self):
+        """palace_path_borders -> int32 per path"""
+        d_out = self.ctx.empty(max(self.n_paths, 1), np.int32)
+        try:
+            _check(lib().palace_path_borders(self.ctx.h, self.d_val.ptr, self.d_off.ptr, self.n_paths, d_out.ptr), "palace_path_borders")
+            return d_out.to_host()[:self.n_paths].copy()
+        finally:
+            d_out.free()
+
+    def tandems(self, cap=None, guard: int = 48):
+        """palace_path_tandems twice, count then fill -> (count, cand_off of the count call, cand_off of the fill call, the candidates
+        as rows r, s, c, intact: the guard words around them came back as they went in).  cap: what the fill call is told instead of
+        the count (a smaller one must be refused: PalaceError)."""
+        n = C.c_int64()
+        d_off = [self.ctx.upload(np.full(self.n_paths + 1, -7, np.int64)) for _ in range(2)]
+        bufs = list(d_off)
+        try:
+            _check(lib().palace_path_tandems(self.ctx.h, self.d_val.ptr, self.d_off.ptr, self.n_paths, d_off[0].ptr, None, 0, C.byref(n)), "palace_path_tandems")
+            count = int(n.value)
+            d_cand = self.ctx.upload(np.full(3 * count + 2 * guard, -5, np.int32))
+            bufs.append(d_cand)
+            _check(lib().palace_path_tandems(self.ctx.h, self.d_val.ptr, self.d_off.ptr, self.n_paths, d_off[1].ptr, d_cand.ptr + 4 * guard,
+                                             count if cap is None else cap, C.byref(n)), "palace_path_tandems")
+            raw = d_cand.to_host()
+            intact = bool((raw[:guard] == -5).all() and (raw[guard + 3 * count:] == -5).all()) and int(n.value) == count
+            return count, d_off[0].to_host(), d_off[1].to_host(), raw[guard:guard + 3 * count].reshape(-1, 3).copy(), intact
+        finally:
+            for b in bufs:
+                b.free()
+
+    def length_relation(self, guard: int = 64):
+        """palace_paths_length_relation (the values are int64 lengths) -> (the n_paths x n_paths table of PATHS_REL_* codes, intact)"""
+        nb = int(lib().palace_paths_length_relation_bytes(self.n_paths))
+        d_rel = self.ctx.upload(np.full(nb + 2 * guard, 0xA5, np.uint8))
+        try:
+            _check(lib().palace_paths_length_relation(self.ctx.h, self.d_val.ptr, self.n_tok, self.d_off.ptr, self.n_paths, d_rel.ptr + guard),
+                   "palace_paths_length_relation")
+            raw = d_rel.to_host()
+            body = raw[guard:guard + nb]
+            codes = np.stack([(body >> (2 * e)) & 3 for e in range(4)], axis=1).reshape(-1)[:self.n_paths * self.n_paths]
+            return codes.reshape(self.n_paths, self.n_paths), bool((raw[:guard] == 0xA5).all() and (raw[guard + nb:] == 0xA5).all())
+        finally:
+            d_rel.free()
+
+    def base_set_in(self, n_cycles: int, hash_bits: int = 64):
+        """palace_paths_base_set_in (the values are base ids) -> uint8 per path"""
+        d_in = self.ctx.empty(max(self.n_paths, 1), np.uint8)
+        try:
+            _check(lib().palace_paths_base_set_in(self.ctx.h, self.d_val.ptr, self.n_tok, self.d_off.ptr, self.n_paths, n_cycles, hash_bits, d_in.ptr),
+                   "palace_paths_base_set_in")
+            return d_in.to_host()[:self.n_paths].copy()
+        finally:
+            d_in.free()
+
+    def free(self):
+        self.d_val.free()
+        self.d_off.free()

@@ -4,6 +4,7 @@
 // appears twice means is the tool's.  `write_fai`: the index rows of a text to their file (split_fastg --fai, faidx).
 #pragma once
 #include <string>
+#include <string_view>
 #include <vector>
 
 #include "device_scope.hpp"
@@ -134,6 +135,27 @@ inline Resolved resolve(palace_ctx *ctx, DeviceScope &scope, const palace_fasta_
         if (n) HIP_OK(palace_d2h(ctx, r.code.data(), r.d_code, n * sizeof(int32_t)));
     }
     return r;
+}
+
+// strings -> ids: one name table over the strings themselves, each followed by a '+' so that the bytes `S+` are at once record S
+// of the table's text and the token palace_path_resolve takes the name S from.  The id of a string is its first record.
+inline std::vector<int32_t> ids_of(palace_ctx *ctx, const std::vector<std::string_view> &strings)
+{
+    std::string text;
+    std::vector<int64_t> off{0};
+    for (const std::string_view s : strings) {
+        text.append(s);
+        text.push_back('+');
+        off.push_back(static_cast<int64_t>(text.size()));
+    }
+    if (strings.empty()) return {};
+    DeviceScope dev(ctx, no_room_does_not_fit);
+    std::vector<int32_t> id = resolve(ctx, dev, nullptr, text, off, {"the node names", "the node names' offsets", "the node ids", "the node names' records"}, true).code;
+    for (int32_t &c : id) {
+        if (c < 0 || (c & 3)) throw Failure("internal: a node name did not resolve to itself");
+        c >>= 2;
+    }
+    return id;
 }
 
 }  // namespace palace_host

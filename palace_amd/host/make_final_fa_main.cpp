@@ -72,27 +72,6 @@ bool parse_args(int argc, char **argv, Args *a)
     return true;
 }
 
-// strings -> ids: one name table over the strings themselves, each followed by a '+' so that the bytes `S+` are at once record S
-// of the table's text and the token palace_path_resolve takes the name S from.  The id of a string is its first record.
-std::vector<int32_t> ids_of(palace_ctx *ctx, const std::vector<fsv> &strings)
-{
-    std::string text;
-    std::vector<int64_t> off{0};
-    for (const fsv s : strings) {
-        text.append(s);
-        text.push_back('+');
-        off.push_back(static_cast<int64_t>(text.size()));
-    }
-    if (strings.empty()) return {};
-    DeviceScope dev(ctx, palace_host::no_room_does_not_fit);
-    std::vector<int32_t> id = palace_host::resolve(ctx, dev, nullptr, text, off, {"the node names", "the node names' offsets", "the node ids", "the node names' records"}, true).code;
-    for (int32_t &c : id) {
-        if (c < 0 || (c & 3)) throw Failure("internal: a node name did not resolve to itself");
-        c >>= 2;
-    }
-    return id;
-}
-
 void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
 {
     palace_host::MappedText ptext, gtext;
@@ -120,7 +99,7 @@ void run(palace_ctx *ctx, const Args &a, palace_host::Trace &tr)
     for (size_t k = 0; k < n_nodes; k++) strings.push_back(g.nodes.at(k));
     for (int64_t t = 0; t < n_tok; t++) strings.push_back(pt.tokens.at(static_cast<size_t>(t)));
     for (int64_t t = 0; t < n_tok; t++) strings.push_back(palace_host::final_base(pt.tokens.at(static_cast<size_t>(t))));
-    const std::vector<int32_t> id = ids_of(ctx, strings);
+    const std::vector<int32_t> id = palace_host::ids_of(ctx, strings);
     std::vector<uint64_t> arcs(n_nodes / 2);
     for (size_t k = 0; k < arcs.size(); k++) arcs[k] = (static_cast<uint64_t>(static_cast<uint32_t>(id[2 * k])) << 32) | static_cast<uint32_t>(id[2 * k + 1]);
     tr.lap("ids");
